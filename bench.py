@@ -14,12 +14,24 @@ synthetic seeded data, fp64.  The tolerance is set so that the timed window neve
 cost of a trip does not depend on it); W warm-up trips run first, then EXACTLY K trips are timed between
 barrier + synchronize on both sides, MAX over ranks.
 
-One JSON line on rank 0 with `roofline` (the CSR x tall-skinny A*V kernel at k = 128 columns, timed live
-with HIP events on the library's stream) and `cpu_baseline` (the CPU oracle, kind "port", on the same
-full-size workload for a bounded number of trips timed one by one, rank 0 at N = 1 only); `config` also
-carries the rate of the direct back end on the same workload (`direct_backend_it_s`, a short run of its own).
+A plain run does only what the headline needs: set-up, W warm-up trips, the K timed trips, the outputs
+(--dump-outputs), one JSON line on rank 0.  Its `value` / `ms_per_step` come from the timed trips; the
+measurements below are null in it.
+
+--full adds, as runs of their own: `roofline` (the CSR x tall-skinny A*V kernel at k = 128 columns, timed
+live with HIP events on the library's stream) and `roofline_kernels` (every kernel of a trip) before the
+timed solve; after it `config.gpu_busy_frac` (a short run with the busy meter on), the rate of the direct
+back end on the same workload (`config.direct_backend_it_s`) and `cpu_baseline` (the CPU oracle, kind
+"port", on the same full-size workload for a bounded number of trips timed one by one, rank 0 at N = 1 only).
+
+--dump-outputs DIR writes what the timed solve holds after its last trip (rank 0's rows), float64:
+T.npy (k x k), V_rows.npy (a fixed, seeded sample of 2048 rows of V), X_rows.npy (V T V' on those rows and
+columns: the solution at the sample) and residual_estimates.npy (the Lanczos estimate of every trip).
+The inputs depend on the arguments alone, and the timed solve draws its random vectors from --seed alone,
+whatever ran before it: two builds compare output for output.
 """
 import argparse
+import gc
 import json
 import os
 import sys
@@ -125,7 +137,13 @@ def main():
     ap.add_argument("--spmm-cols", default="128", help="comma list of column counts for --spmm-only")
     ap.add_argument("--spmm-variants", default="", help="--spmm-only: comma list of operator variants to time (default: 1, 2, 7, 9, or --spmm-variant)")
     ap.add_argument("--spmm-pad", type=int, default=0, help="--spmm-only: extra panel capacity (columns), i.e. a row stride that is not a power of two")
+    ap.add_argument("--full", action="store_true", help="also the measurements besides the headline: roofline and per-kernel legs, the GPU-busy run, "
+                    "the direct back end's run, the CPU baseline (the --cpu-*, --busy-steps, --direct-steps, --kspmm, --spmm-reps and "
+                    "--no-kernel-legs options apply to them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed solve computed (after its last trip) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     _protect_stdout()
 
     import torch
@@ -247,6 +265,144 @@ def main():
                       "alg_GBs": ab / ms / 1e6, "frac": ab / ms / 1e6 / HBM_PEAK_GBS})
             del X, Y
         return
+
+    legs = measure_kernels(args, ctx, A, ml, nnz_local, nranks, rank) if args.full else {}
+
+    # ---- timed solve ---------------------------------------------------------------------------------
+    W, K = args.warmup, args.steps
+    # the timed solve draws its random vectors from --seed alone, not from where the legs above left the context's generator: a plain run
+    # and a --full run compute the same
+    ctx.set_seed(args.seed)
+    params = {"Maximum iterations": 100000, "Tolerance": 1e-30, "Expand size": args.expand, "Lanczos iterations": args.lanczos,
+              "Restart size": args.restart, "Reduced size": args.reduced, "Minimize solution space": 0}
+    solver = rails_amd.Solver(ctx, A, B, m_global=mg)
+    code = solver.set_parameters(params)
+    assert code == 0
+    solver.set_option("verbose", 1 if args.verbose else 0)
+    solver.set_option("max_trips", W + K)
+    solver.set_option("projected_lanczos", args.projected_lanczos)
+    solver.set_option("subspace", args.subspace)
+    marks = {}
+
+    allocs = []  # device / pinned allocations made by the library so far, per trip
+    stamps = []  # host time at the end of every trip (diagnostics: one slow trip shows up here)
+
+    def on_trip(trip):
+        if trip == W or trip == W + K:
+            torch.cuda.synchronize()
+            if dist is not None:
+                dist.barrier()
+            torch.cuda.synchronize()
+            marks[trip] = time.perf_counter()
+        stamps.append(time.perf_counter())
+        allocs.append(ctx.stats().get("device_allocations", 0))
+
+    solver.set_trip_callback(on_trip)
+    gc.collect()
+    gc.disable()  # the trip callback is the only Python in the loop: no collector pause inside the timed region
+    try:
+        code, _, _ = solver.solve(fetch=False)
+    finally:
+        gc.enable()
+    assert solver.trips() == W + K, "solver stopped after %d trips (code %d)" % (solver.trips(), code)
+    elapsed = marks[W + K] - marks[W]
+    if dist is not None:
+        t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    its = K / elapsed
+    import ctypes as _C
+
+    _sm, _bs = _C.c_long(0), _C.c_long(0)
+    rails_amd.load().rails_sb03md_counts(_C.byref(_sm), _C.byref(_bs))
+    sb_counts = (int(_sm.value), int(_bs.value))
+    _ext, _fresh = _C.c_long(0), _C.c_long(0)
+    rails_amd.load().rails_sb03md_adi_counts(_C.byref(_ext), _C.byref(_fresh))
+    hist = solver.history()
+    log("[rank %d] host sections (s, whole solve incl. warm-up): %s" % (rank, json.dumps(solver.profile())))
+    median_trip_ms = None
+    if len(stamps) > W + 2:
+        dts = np.diff(np.array(stamps))[W:]
+        median_trip_ms = 1e3 * float(np.median(dts))
+        log("[rank %d] timed trips: median %.2f ms, slowest %.2f ms (trip %d); library allocations inside the timed region: %d (at trips %s)" % (
+            rank, 1e3 * float(np.median(dts)), 1e3 * float(dts.max()), W + 1 + int(dts.argmax()), allocs[-1] - allocs[W - 1],
+            [i + 1 for i in range(W, len(allocs)) if allocs[i] != allocs[i - 1]]))
+    log("[rank %d] counters: %s %s" % (rank, json.dumps(ctx.stats()), json.dumps(solver.backend_stats())))
+    # steady-state rate: whole restart cycles, whatever --warmup / --steps cut out of them.  A restart trip stands out in the stamps
+    # (shrink + re-basing: 2-3x a regular trip); the rate is taken from the first to the last restart trip of the run (warm-up included,
+    # the first three trips -- library set-up -- excluded).
+    steady_it_s, restart_trips = None, []
+    if len(stamps) > 12:
+        dall = np.diff(np.array(stamps))
+        med = float(np.median(dall[3:]))
+        restart_trips = [i for i in range(3, dall.size) if dall[i] > 1.6 * med]
+        if len(restart_trips) >= 2:
+            a, b = restart_trips[0], restart_trips[-1]
+            steady_it_s = (b - a) / float(stamps[b + 1] - stamps[a + 1])
+            log("[rank %d] steady state: restart trips %s -> %d trips in %.4f s = %.1f it/s over %d whole restart cycles" % (
+                rank, [i + 1 for i in restart_trips], b - a, stamps[b + 1] - stamps[a + 1], steady_it_s, len(restart_trips) - 1))
+    # where a trip's wall time goes on the host's side: sections in which the host computes (projected solve, residual Lanczos on
+    # coordinates, restart algebra) against sections in which it mostly waits for the device (operator apply incl. the first projection)
+    prof = solver.profile()
+    ntr = max(1, solver.trips())
+    host_keys = [k for k in prof if k in ("dense_solve", "Residual Lanczos", "Restart", "Compute VAV", "Apply B", "Expand", "Orthogonalize")]
+    wait_keys = [k for k in prof if k in ("Apply A", "Apply M")]
+    host_ms = 1e3 * sum(prof[k] for k in host_keys) / ntr
+    device_critical_ms = 1e3 * sum(prof[k] for k in wait_keys) / ntr
+    sections_ms = {k: round(1e3 * v / ntr, 4) for k, v in prof.items()}
+    log("[rank %d] %d trips in %.3fs -> %.2f it/s; Lanczos estimates %.3e -> %.3e; V.N()=%d" % (rank, K, elapsed, its, hist[0], hist[-1], solver.k))
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, solver, hist)
+    # (the runs of --full start solves of their own from the same solver object: after the outputs are taken)
+    gpu_busy_frac = busy_run(args, ctx, solver, W, rank) if args.full else None
+    direct_its = direct_run(args, ctx, solver, W, dist, rank) if args.full else None
+    cpu = cpu_run(args, params, ml, W, rank, nranks) if args.full else None
+
+    if rank == 0:
+        line = {
+            "metric": "RAILS iterations/sec (+ A*V SpMM HBM GB/s in roofline), m=1M rows/GPU, k=128, fp64",
+            "value": its, "unit": "iterations/s", "n_gpus": nranks, "steps": K, "warmup": W, "ms_per_step": 1e3 * elapsed / K,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": "BASELINE configs[2]: m=%d rows/GPU (global %d), 27 nnz/row %s CSR, B m x %d, Restart size %d, Reduced size %d, "
+                                   "Expand size %d, Lanczos iterations %d" % (ml, mg, desc, args.p, args.restart, args.reduced, args.expand, args.lanczos),
+                       "parallelism": "row-partition x%d, RCCL all-reduce of projected blocks" % nranks if nranks > 1 else "single GPU",
+                       "collectives": collectives,
+                       "spmm_columns": legs.get("spmm_columns"), "inloop_spmm": legs.get("inloop_spmm"), "residual_lanczos": ("the reference's recurrence on coordinate vectors (host)" if args.subspace else
+                                            ("coefficient-space, Gram differences" if args.projected_lanczos else "fused one-pass-per-step kernel")),
+                       "backend": "coordinates in a device-resident orthonormal basis" if args.subspace else "direct panels",
+                       # one JOINT solve over n_gpus x m rows: under weak scaling the ideal is a constant iteration rate; the rate at which
+                       # matrix rows are processed (rows x iterations / s) is the quantity that grows with the GPU count
+                       "global_rows": int(mg), "row_iterations_per_s": its * mg,
+                       # the same workload on the direct back end (fused Lanczos kernel + block orthogonalisation), a short run of its own
+                       "direct_backend_it_s": direct_its,
+                       # share of a trip during which the GPU is at work (the library's busy meter -- events around every launch -- over a short run
+                       # of its own); the rest is host work with the GPU idle
+                       "gpu_busy_frac": gpu_busy_frac,
+                       "median_trip_ms": median_trip_ms,
+                       # rate over whole restart cycles (first to last restart trip of the run, warm-up included): independent of --warmup / --steps
+                       "steady_it_s": steady_it_s, "restart_trips": [i + 1 for i in restart_trips],
+                       # per trip, averaged over the whole solve (warm-up included): host = sections in which the host computes (projected
+                       # solve, Lanczos on coordinates, restart algebra); device_critical = sections in which it waits for the device (A * W:
+                       # materialise, SpMM, first projection round); the rest of the device's work runs behind the host's
+                       "host_ms": host_ms, "device_critical_ms": device_critical_ms, "sections_ms_per_trip": sections_ms,
+                       "host_projected_solve_routes": {"smith_or_adi": sb_counts[0], "bartels_stewart": sb_counts[1],
+                                                       # ADI calls that built on the call before (bordered matrix: shifts kept, inverses extended) / from scratch
+                                                       "adi_extended": int(_ext.value), "adi_from_scratch": int(_fresh.value)}},
+            "roofline": legs.get("roofline"),
+            "roofline_kernels": legs.get("roofline_kernels"),
+            "cpu_baseline": cpu,
+        }
+        emit(line)
+    solver.close()
+    if dist is not None:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def measure_kernels(args, ctx, A, ml, nnz_local, nranks, rank):
+    """--full, before the timed solve: the A*X roofline leg, the in-loop A*W and the other kernels of a trip, each timed on its own."""
+    import rails_amd
 
     # ---- roofline leg: Y = A * X with k = 128 columns, HIP events on the library's stream -------------
     kk = args.kspmm
@@ -403,90 +559,34 @@ def main():
             traffic = None
     log("[rank %d] SpMM %s k=%d: %.3f ms, %.1f GB/s algorithmic (%.1f%% of %.0f GB/s)" % (rank, spmm_kernel, kk, spmm_ms, achieved,
                                                                                           100 * achieved / HBM_PEAK_GBS, HBM_PEAK_GBS))
+    roofline = {"bound": "hbm", "kernel": spmm_kernel, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_stale": traffic_stale, "algorithmic_bytes": alg_bytes, "avg_ms": spmm_ms,
+                "traffic_source": "profiles/traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE of this kernel on this workload, corrected as profiles/README.md says)" if traffic else None,
+                "schedule": sweep_stats}
+    return {"spmm_columns": kk, "inloop_spmm": inloop, "roofline": roofline, "roofline_kernels": roofline_kernels}
 
-    # ---- timed solve ---------------------------------------------------------------------------------
-    W, K = args.warmup, args.steps
-    params = {"Maximum iterations": 100000, "Tolerance": 1e-30, "Expand size": args.expand, "Lanczos iterations": args.lanczos,
-              "Restart size": args.restart, "Reduced size": args.reduced, "Minimize solution space": 0}
-    solver = rails_amd.Solver(ctx, A, B, m_global=mg)
-    code = solver.set_parameters(params)
-    assert code == 0
-    solver.set_option("verbose", 1 if args.verbose else 0)
-    solver.set_option("max_trips", W + K)
-    solver.set_option("projected_lanczos", args.projected_lanczos)
-    solver.set_option("subspace", args.subspace)
-    marks = {}
 
-    allocs = []  # device / pinned allocations made by the library so far, per trip
-    stamps = []  # host time at the end of every trip (diagnostics: one slow trip shows up here)
+DUMP_ROWS = 2048  # rows of V in the sample that --dump-outputs writes
+DUMP_MAX_BYTES = 64 * 10**6
 
-    def on_trip(trip):
-        if trip == W or trip == W + K:
-            torch.cuda.synchronize()
-            if dist is not None:
-                dist.barrier()
-            torch.cuda.synchronize()
-            marks[trip] = time.perf_counter()
-        stamps.append(time.perf_counter())
-        allocs.append(ctx.stats().get("device_allocations", 0))
 
-    solver.set_trip_callback(on_trip)
-    import gc
+def dump_outputs(out_dir, solver, hist):
+    """What the timed solve holds after its last trip, as the caller of Solver.solve() would receive it (V, T) and its trip history,
+    float64: T, a fixed, seeded sample of the rows of V, the solution V T V' on those rows and columns, the Lanczos estimate of every trip."""
+    V, T = solver.V(), solver.T()
+    rows = np.sort(np.random.default_rng(20261016).choice(V.shape[0], size=min(V.shape[0], DUMP_ROWS), replace=False))
+    Vs = np.ascontiguousarray(V[rows])
+    del V
+    out = {"T": np.ascontiguousarray(T), "V_rows": Vs, "X_rows": Vs @ T @ Vs.T, "residual_estimates": np.asarray(hist, dtype=np.float64)}
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_MAX_BYTES, "outputs of %d bytes: more than %d" % (total, DUMP_MAX_BYTES)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64, copy=False))
+    log("outputs: %s in %s (%.1f MB)" % (", ".join("%s %s" % (n, "x".join(map(str, a.shape))) for n, a in out.items()), out_dir, total / 1e6))
 
-    gc.collect()
-    gc.disable()  # the trip callback is the only Python in the loop: no collector pause inside the timed region
-    try:
-        code, _, _ = solver.solve(fetch=False)
-    finally:
-        gc.enable()
-    assert solver.trips() == W + K, "solver stopped after %d trips (code %d)" % (solver.trips(), code)
-    elapsed = marks[W + K] - marks[W]
-    if dist is not None:
-        t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-    its = K / elapsed
-    import ctypes as _C
 
-    _sm, _bs = _C.c_long(0), _C.c_long(0)
-    rails_amd.load().rails_sb03md_counts(_C.byref(_sm), _C.byref(_bs))
-    sb_counts = (int(_sm.value), int(_bs.value))
-    _ext, _fresh = _C.c_long(0), _C.c_long(0)
-    rails_amd.load().rails_sb03md_adi_counts(_C.byref(_ext), _C.byref(_fresh))
-    hist = solver.history()
-    log("[rank %d] host sections (s, whole solve incl. warm-up): %s" % (rank, json.dumps(solver.profile())))
-    median_trip_ms = None
-    if len(stamps) > W + 2:
-        dts = np.diff(np.array(stamps))[W:]
-        median_trip_ms = 1e3 * float(np.median(dts))
-        log("[rank %d] timed trips: median %.2f ms, slowest %.2f ms (trip %d); library allocations inside the timed region: %d (at trips %s)" % (
-            rank, 1e3 * float(np.median(dts)), 1e3 * float(dts.max()), W + 1 + int(dts.argmax()), allocs[-1] - allocs[W - 1],
-            [i + 1 for i in range(W, len(allocs)) if allocs[i] != allocs[i - 1]]))
-    log("[rank %d] counters: %s %s" % (rank, json.dumps(ctx.stats()), json.dumps(solver.backend_stats())))
-    # steady-state rate: whole restart cycles, whatever --warmup / --steps cut out of them.  A restart trip stands out in the stamps
-    # (shrink + re-basing: 2-3x a regular trip); the rate is taken from the first to the last restart trip of the run (warm-up included,
-    # the first three trips -- library set-up -- excluded).
-    steady_it_s, restart_trips = None, []
-    if len(stamps) > 12:
-        dall = np.diff(np.array(stamps))
-        med = float(np.median(dall[3:]))
-        restart_trips = [i for i in range(3, dall.size) if dall[i] > 1.6 * med]
-        if len(restart_trips) >= 2:
-            a, b = restart_trips[0], restart_trips[-1]
-            steady_it_s = (b - a) / float(stamps[b + 1] - stamps[a + 1])
-            log("[rank %d] steady state: restart trips %s -> %d trips in %.4f s = %.1f it/s over %d whole restart cycles" % (
-                rank, [i + 1 for i in restart_trips], b - a, stamps[b + 1] - stamps[a + 1], steady_it_s, len(restart_trips) - 1))
-    # where a trip's wall time goes on the host's side: sections in which the host computes (projected solve, residual Lanczos on
-    # coordinates, restart algebra) against sections in which it mostly waits for the device (operator apply incl. the first projection)
-    prof = solver.profile()
-    ntr = max(1, solver.trips())
-    host_keys = [k for k in prof if k in ("dense_solve", "Residual Lanczos", "Restart", "Compute VAV", "Apply B", "Expand", "Orthogonalize")]
-    wait_keys = [k for k in prof if k in ("Apply A", "Apply M")]
-    host_ms = 1e3 * sum(prof[k] for k in host_keys) / ntr
-    device_critical_ms = 1e3 * sum(prof[k] for k in wait_keys) / ntr
-    sections_ms = {k: round(1e3 * v / ntr, 4) for k, v in prof.items()}
-    log("[rank %d] %d trips in %.3fs -> %.2f it/s; Lanczos estimates %.3e -> %.3e; V.N()=%d" % (rank, K, elapsed, its, hist[0], hist[-1], solver.k))
-
+def busy_run(args, ctx, solver, W, rank):
     # ---- GPU-busy fraction: a short run of its own on the same back end with the library's busy meter on (a pair of events around every
     # launch, a few microseconds each: not in the timed region above) -----------------------------------------------------------------
     gpu_busy_frac = None
@@ -512,9 +612,14 @@ def main():
         if Wb in marks_b and Wb + Kb in marks_b:
             gpu_busy_frac = (busy_b[Wb + Kb] - busy_b[Wb]) * 1e-3 / (marks_b[Wb + Kb] - marks_b[Wb])
             log("[rank %d] busy meter: %d trips in %.3fs, GPU at work %.1f ms -> %.3f" % (rank, Kb, marks_b[Wb + Kb] - marks_b[Wb], busy_b[Wb + Kb] - busy_b[Wb], gpu_busy_frac))
+    return gpu_busy_frac
 
+
+def direct_run(args, ctx, solver, W, dist, rank):
     # ---- the direct back end (device panels for V and AV: fused one-pass Lanczos kernel, block orthogonalisation on MFMA -- the north
     # star's literal path) on the same workload, a short timed run of its own: config.direct_backend_it_s ---------------------------
+    import torch
+
     direct_its = None
     if args.subspace and args.direct_steps > 0:
         Wd, Kd = min(W, 4), args.direct_steps
@@ -544,7 +649,10 @@ def main():
                 dt = float(t.item())
             direct_its = Kd / dt
             log("[rank %d] direct back end: %d trips in %.3fs -> %.2f it/s; counters %s" % (rank, Kd, dt, direct_its, json.dumps(ctx.stats())))
+    return direct_its
 
+
+def cpu_run(args, params, ml, W, rank, nranks):
     # ---- cpu_baseline: the oracle (CPU restatement of the Stl path, OpenMP) on the SAME full-size workload, rank 0, N = 1: a bounded
     # number of trips, each timed on its own (no extrapolation) -------------------------------------------------------------------
     cpu = None
@@ -593,49 +701,7 @@ def main():
                 finally:
                     orc.set_num_threads(nthreads)
         del out, As, Bs
-
-    if rank == 0:
-        line = {
-            "metric": "RAILS iterations/sec (+ A*V SpMM HBM GB/s in roofline), m=1M rows/GPU, k=128, fp64",
-            "value": its, "unit": "iterations/s", "n_gpus": nranks, "steps": K, "warmup": W, "ms_per_step": 1e3 * elapsed / K,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "BASELINE configs[2]: m=%d rows/GPU (global %d), 27 nnz/row %s CSR, B m x %d, Restart size %d, Reduced size %d, "
-                                   "Expand size %d, Lanczos iterations %d" % (ml, mg, desc, args.p, args.restart, args.reduced, args.expand, args.lanczos),
-                       "parallelism": "row-partition x%d, RCCL all-reduce of projected blocks" % nranks if nranks > 1 else "single GPU",
-                       "collectives": collectives,
-                       "spmm_columns": kk, "inloop_spmm": inloop, "residual_lanczos": ("the reference's recurrence on coordinate vectors (host)" if args.subspace else
-                                            ("coefficient-space, Gram differences" if args.projected_lanczos else "fused one-pass-per-step kernel")),
-                       "backend": "coordinates in a device-resident orthonormal basis" if args.subspace else "direct panels",
-                       # one JOINT solve over n_gpus x m rows: under weak scaling the ideal is a constant iteration rate; the rate at which
-                       # matrix rows are processed (rows x iterations / s) is the quantity that grows with the GPU count
-                       "global_rows": int(mg), "row_iterations_per_s": its * mg,
-                       # the same workload on the direct back end (fused Lanczos kernel + block orthogonalisation), a short run of its own
-                       "direct_backend_it_s": direct_its,
-                       # share of a trip during which the GPU is at work (the library's busy meter -- events around every launch -- over a short run
-                       # of its own); the rest is host work with the GPU idle
-                       "gpu_busy_frac": gpu_busy_frac,
-                       "median_trip_ms": median_trip_ms,
-                       # rate over whole restart cycles (first to last restart trip of the run, warm-up included): independent of --warmup / --steps
-                       "steady_it_s": steady_it_s, "restart_trips": [i + 1 for i in restart_trips],
-                       # per trip, averaged over the whole solve (warm-up included): host = sections in which the host computes (projected
-                       # solve, Lanczos on coordinates, restart algebra); device_critical = sections in which it waits for the device (A * W:
-                       # materialise, SpMM, first projection round); the rest of the device's work runs behind the host's
-                       "host_ms": host_ms, "device_critical_ms": device_critical_ms, "sections_ms_per_trip": sections_ms,
-                       "host_projected_solve_routes": {"smith_or_adi": sb_counts[0], "bartels_stewart": sb_counts[1],
-                                                       # ADI calls that built on the call before (bordered matrix: shifts kept, inverses extended) / from scratch
-                                                       "adi_extended": int(_ext.value), "adi_from_scratch": int(_fresh.value)}},
-            "roofline": {"bound": "hbm", "kernel": spmm_kernel, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_stale": traffic_stale, "algorithmic_bytes": alg_bytes, "avg_ms": spmm_ms,
-                         "traffic_source": "profiles/traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE of this kernel on this workload, corrected as profiles/README.md says)" if traffic else None,
-                         "schedule": sweep_stats},
-            "roofline_kernels": roofline_kernels,
-            "cpu_baseline": cpu,
-        }
-        emit(line)
-    solver.close()
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+    return cpu
 
 
 if __name__ == "__main__":

@@ -44,7 +44,7 @@ def main():
     if stats:
         shutil.copy(stats[0], os.path.join(dst, "%s_%s_kernel_stats.csv" % (tag, pattern)))
         rows = list(csv.DictReader(open(stats[0])))
-        lines += ["## `rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu` (whole run: SpMM leg + %s)" % "solve", "",
+        lines += ["## `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu` (whole run: SpMM leg + %s)" % "solve", "",
                   "| kernel | calls | total ms | avg us | % |", "|---|---|---|---|---|"]
         for r in rows[:16]:
             lines.append("| %s | %s | %.2f | %.1f | %s |" % (short(r["Name"]), r["Calls"], float(r["TotalDurationNs"]) / 1e6,

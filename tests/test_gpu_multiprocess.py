@@ -8,6 +8,7 @@ import re
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -46,8 +47,8 @@ def test_two_ranks_share_one_gpu():
 
 
 def test_bench_line_contract():
-    """the one JSON line of `python bench.py` (N = 1, small sizes): every field the bench contract names, with sane values"""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--rows-per-gpu", "60000", "--steps", "5", "--warmup", "3", "--spmm-reps", "2", "--cpu-trips", "2", "--cpu-warmup", "2", "--direct-steps", "3"]
+    """the one JSON line of `python bench.py --full` (N = 1, small sizes): every field the bench contract names, with sane values"""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--rows-per-gpu", "60000", "--steps", "5", "--warmup", "3", "--spmm-reps", "2", "--cpu-trips", "2", "--cpu-warmup", "2", "--direct-steps", "3"]
     p = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
@@ -75,3 +76,36 @@ def test_bench_line_contract():
     assert cfg["host_ms"] > 0 and cfg["device_critical_ms"] > 0
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] >= 1 and c["value"] > 0 and c["unit"] == "iterations/s" and "sample" in c
+
+
+def test_plain_bench_run_and_its_outputs(tmp_path):
+    """`python bench.py` without --full: the headline fields from exactly --steps timed trips, null where only --full measures, and
+    --dump-outputs writes what the timed solve computed -- float64, at most 64 MB, and the same again from a second run"""
+    runs = []
+    for i in range(2):
+        out = tmp_path / ("out%d" % i)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--rows-per-gpu", "60000", "--steps", "5", "--warmup", "3",
+               "--dump-outputs", str(out)]
+        p = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["metric"].startswith("RAILS iterations/sec") and d["unit"] == "iterations/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+        assert d["steps"] == 5 and d["warmup"] == 3 and d["ms_per_step"] > 0 and abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+        assert d["roofline"] is None and d["roofline_kernels"] is None and d["cpu_baseline"] is None
+        assert d["config"]["direct_backend_it_s"] is None and d["config"]["gpu_busy_frac"] is None
+        assert "prepare(" not in p.stderr and "busy meter" not in p.stderr and "[cpu]" not in p.stderr  # no leg of --full ran
+        names = sorted(os.listdir(out))
+        assert names == ["T.npy", "V_rows.npy", "X_rows.npy", "residual_estimates.npy"], names
+        arrays = {n[:-4]: np.load(out / n) for n in names}
+        assert sum(a.nbytes for a in arrays.values()) <= 64 * 10**6
+        for a in arrays.values():
+            assert a.dtype == np.float64 and np.all(np.isfinite(a))
+        k = arrays["T"].shape[0]
+        assert arrays["T"].shape == (k, k) and arrays["V_rows"].shape == (2048, k) and arrays["X_rows"].shape == (2048, 2048)
+        assert arrays["residual_estimates"].shape == (8,)  # one estimate per trip: warm-up + timed
+        runs.append(arrays)
+    a, b = runs
+    np.testing.assert_allclose(b["residual_estimates"], a["residual_estimates"], rtol=1e-6)
+    assert np.linalg.norm(b["X_rows"] - a["X_rows"]) <= 1e-6 * np.linalg.norm(a["X_rows"])
