@@ -190,6 +190,28 @@ int rails_panel_permute_rows(rails_ctx *ctx, const rails_panel *X, int xc0, int 
 int rails_index_upload(rails_ctx *ctx, const int32_t *host, int64_t n, int32_t **out_dev);
 void rails_index_free(rails_ctx *ctx, int32_t *dev);
 
+/* ---- sparse LU solve as a library object (rails_amd/csrc/splu.hip) --------------------------------------------------------------------
+ * The operator A^-1 of RAILS' inverse and extended Krylov projections (matlab/RAILSsolver.m:7-24, opts.projection_method and
+ * opts.Ainv) from the factors of a host LU, Pr A Pc = L U, as scipy's SuperLU gives them: Pr has ones at (perm_r[i], i), Pc at
+ * (i, perm_c[i]); L and U in CSR, L unit lower (its diagonal may be stored, as ones, or left out), U upper with its diagonal.
+ * rows (optional, m_sub distinct indices) restricts the operator to a subsystem, x -> (A^-1 E x)[rows] with E putting x on those rows
+ * and zeros elsewhere: the inverse of a Schur complement from an LU of the full matrix (Sinv, matlab/RAILSschur.m:60-64).  rows = NULL:
+ * the operator is A^-1 itself (m_sub is ignored).  The level analysis runs on the host, here.  Single GPU only. */
+typedef struct rails_lu rails_lu;
+int rails_lu_create(rails_ctx *ctx, int64_t n, const int64_t *L_rowptr, const int32_t *L_col, const double *L_val, const int64_t *U_rowptr,
+                    const int32_t *U_col, const double *U_val, const int32_t *perm_r, const int32_t *perm_c, const int32_t *rows, int64_t m_sub,
+                    rails_lu **out);
+void rails_lu_destroy(rails_lu *lu);
+/* Y[:, yc0:yc0+nc] = A^-1 X[:, xc0:xc0+nc] (trans != 0: A^-T), both panels of m_sub rows, out of place; X is left unchanged.  The
+ * object owns its workspace and grows it only when a wider nc arrives. */
+int rails_lu_solve(rails_ctx *ctx, rails_lu *lu, int trans, const rails_panel *X, int xc0, int nc, rails_panel *Y, int yc0);
+/* info[0..3] levels of L, U, U', L'; [4] nnz of L below its diagonal; [5] nnz of U; [6] kernel launches of the last solve; [7] n;
+ * [8] m_sub; [9] workspace columns.  Returns the number of entries written (at most cap), or a negative code. */
+int rails_lu_stats(const rails_lu *lu, int64_t *info, int cap);
+/* An operator handle whose rails_spmm is rails_lu_solve (both trans values): it takes the Matrix role wherever a CSR handle does
+ * (HipOperatorWrapper, rails_solver_create, rails_solver_set_inverse).  The caller keeps the rails_lu alive while the handle is used. */
+int rails_csr_create_lu(rails_ctx *ctx, rails_lu *lu, rails_csr **out);
+
 typedef struct rails_sweep_plan rails_sweep_plan;
 int rails_sweep_plan_create(int64_t m, int64_t ncols, const int64_t *rowptr, const int32_t *col, const double *val,
                             const int *params, rails_sweep_plan **out);

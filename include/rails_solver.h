@@ -39,6 +39,14 @@ int rails_solver_apply_parameters(rails_solver *s, int *code);
  * coordinate-space back end of rails/SubspaceWrappers.hpp -- all multivectors as coordinates in one orthonormal device basis;
  * 0: the direct back end of rails/HipWrappers.hpp) */
 int rails_solver_set_option(rails_solver *s, const char *name, double value);
+/* opts.Ainv of matlab/RAILSsolver.m:18-22: the operator the projection methods other than 1 apply as A^-1 ("Projection method" =
+ * 1.1, 1.2, 1.3: expand with A^-1 r instead of r; 2.1, 2.2, 2.3: with [r, A^-1 r]; the decimal picks the start space -- .1 A^-1 V0
+ * (2.x: [V0, A^-1 V0]), .2 A^-1 B ([B, A^-1 B]), .3 V0 -- matlab/RAILSsolver.m:7-16).  Any operator handle of A's row count: a
+ * sparse LU solve (rails_csr_create_lu), a callback, a CSR matrix.  The caller keeps ownership, as for A and M.  "Projection method"
+ * itself is a parameter (rails_solver_set_parameter); rails_solver_apply_parameters returns code 2 for a value that is no method, and
+ * rails_solver_solve refuses a method other than 1 without an inverse (RAILS_EINVAL). */
+int rails_solver_set_inverse(rails_solver *s, rails_csr *Ainv);
+
 /* called at the start of every loop trip with the index of that trip, and once after the last */
 typedef void (*rails_trip_fn)(void *user, int trip);
 int rails_solver_set_trip_callback(rails_solver *s, rails_trip_fn fn, void *user);

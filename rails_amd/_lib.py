@@ -83,6 +83,11 @@ SIGNATURES = {
     "rails_panel_permute_rows": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int]),
     "rails_index_upload": (C.c_int, [_vp, _i32p, C.c_int64, C.POINTER(_vp)]),
     "rails_index_free": (None, [_vp, _vp]),
+    "rails_lu_create": (C.c_int, [_vp, C.c_int64, _i64p, _i32p, _dp, _i64p, _i32p, _dp, _i32p, _i32p, _i32p, C.c_int64, C.POINTER(_vp)]),
+    "rails_lu_destroy": (None, [_vp]),
+    "rails_lu_solve": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int]),
+    "rails_lu_stats": (C.c_int, [_vp, _i64p, C.c_int]),
+    "rails_csr_create_lu": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     "rails_panel_random": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),
     "rails_gram": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _dp, C.c_int]),
     "rails_panel_gemm": (C.c_int, [_vp, C.c_double, _vp, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_double, _vp, C.c_int]),

@@ -187,6 +187,8 @@ struct rails_csr {
     // operator given by its action (rails_csr_create_callback): rails_spmm hands the panels over
     rails_apply_fn apply_cb = nullptr;
     void *apply_user = nullptr;
+    // operator that solves with a sparse LU (rails_csr_create_lu, splu.hip): rails_spmm is rails_lu_solve; the caller owns the object
+    rails_lu *lu = nullptr;
 };
 
 // Diagnostics: with RAILS_TRACE_SLOW_MS=x every guarded entry point synchronises before and after its work and reports on stderr

@@ -46,6 +46,8 @@ struct rails_solver {
     rails::HostDenseMatrix T;
     int64_t m_local = 0, m_global = 0;
     bool has_M = false;
+    rails::HipOperatorWrapper Ainv; // rails_solver_set_inverse (the caller owns the handle)
+    bool has_inv = false;
     bool mass = false;
     bool ortho_m = false; // V kept M-orthonormal (matlab/RAILSsolver.m opts.ortho = 'M'); needs mass
     rails_trip_fn trip_fn = nullptr;
@@ -159,6 +161,22 @@ extern "C" int rails_solver_set_option(rails_solver *s, const char *name, double
     return RAILS_OK;
 }
 
+extern "C" int rails_solver_set_inverse(rails_solver *s, rails_csr *Ainv)
+{
+    if (!s || !Ainv) {
+        rails_set_error("rails_solver_set_inverse: null argument");
+        return RAILS_EINVAL;
+    }
+    if (rails_csr_rows(Ainv) != s->m_local) {
+        rails_set_error("rails_solver_set_inverse: the inverse has %lld rows, A %lld", (long long)rails_csr_rows(Ainv), (long long)s->m_local);
+        return RAILS_EINVAL;
+    }
+    s->Ainv = rails::HipOperatorWrapper(s->ctx, Ainv, s->m_global);
+    s->has_inv = true;
+    s->solver->set_inverse(s->Ainv);
+    return RAILS_OK;
+}
+
 extern "C" int rails_solver_set_trip_callback(rails_solver *s, rails_trip_fn fn, void *user)
 {
     if (!s) return RAILS_EINVAL;
@@ -191,13 +209,16 @@ static int solve_in_coordinates(rails_solver *s)
     const int p = s->B.N();
     const int restart = s->params.get("Restart size", -1);
     const int expand = s->params.get("Expand size", 3);
-    const int kmax = std::max(restart > 0 ? restart : 100, 1) + expand + 100;
+    rails::HipSolver::Projection proj;
+    const bool pair = rails::HipSolver::parse_projection(s->params.get("Projection method", 1.0), proj) && proj.pair; // 2.x: twice per trip
+    const int kmax = std::max(restart > 0 ? restart : 100, 1) + (pair ? 2 : 1) * expand + 100;
     auto basis = std::make_shared<rails::SubspaceBasis>(s->ctx, s->m_local, s->m_global, 2 * kmax + p + 128);
     if (restart > 0 || s->params.get("Restart iterations", 20) > 0) basis->preallocate_compress_panel(); // restarts will re-base the basis
     rails::SubspaceMultiVector Bc = rails::SubspaceMultiVector::Absorb(basis, s->B);
     rails::SubspaceOperator Ac(s->A, basis);
     rails::SubspaceOperator Mc(s->mass ? s->M : s->A, basis);
     rails::SubspaceSolver solver(Ac, Bc, Mc);
+    if (s->has_inv) solver.set_inverse(rails::SubspaceOperator(s->Ainv, basis));
     int prc = solver.set_parameters(s->params);
     if (prc != 0) return prc + 100;
     solver.set_verbose(s->verbose);
@@ -237,6 +258,18 @@ extern "C" int rails_solver_solve(rails_solver *s, int *code, int *k)
     // a warm start needs the caller's V; "Restart from solution" without one is the direct back end's business (it starts from
     // the single column the solver object holds, like the reference)
     s->last_was_subspace = s->subspace && (s->have_V0 || !restart_from_solution);
+    { // the projection method: a valid value (rails_solver_apply_parameters reports it) with the inverse it needs
+        rails::HipSolver::Projection proj;
+        const double method = s->params.get("Projection method", 1.0);
+        if (!rails::HipSolver::parse_projection(method, proj)) {
+            rails_set_error("rails_solver_solve: 'Projection method' %g is none of 1, 1.1, 1.2, 1.3, 2.1, 2.2, 2.3", method);
+            return RAILS_EINVAL;
+        }
+        if (proj.uses_inverse() && !s->has_inv) {
+            rails_set_error("rails_solver_solve: 'Projection method' %g needs an inverse (rails_solver_set_inverse)", method);
+            return RAILS_EINVAL;
+        }
+    }
     rails::clear_sticky_error();
     int rc;
     try { // the solver templates allocate (std::vector, make_shared): nothing may unwind through the C boundary

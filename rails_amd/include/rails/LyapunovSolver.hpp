@@ -198,7 +198,37 @@ public:
         double keep_above = 1e-3 * 1e-3;  // "Restart tolerance": |eigenvalue of T| a kept direction must exceed (absolute, :471)
         bool shrink_on_convergence = true; // "Minimize solution space"
         bool warm_start = false;          // "Restart from solution": V holds an orthonormal basis to continue from
+        double projection_method = 1.0;   // "Projection method": opts.projection_method of matlab/RAILSsolver.m:7-16 (see projection())
     };
+
+    // The projection method, opts.projection_method of matlab/RAILSsolver.m:7-16,288-314,520-530: `pair` = the 2.x methods (every
+    // expansion adds [W, A^-1 W]; else 1.x adds A^-1 W), `start` = the decimal: 1 start from [V0, A^-1 V0] (2.1) or A^-1 V0 (1.1), 2 from
+    // [B, A^-1 B] or A^-1 B, 3 from V0 as method 1 does.  Method 1 (`start` 0) adds the Ritz vectors W themselves and never uses A^-1.
+    struct Projection {
+        bool pair = false;
+        int start = 0;
+        bool uses_inverse() const { return start != 0; }
+    };
+    // the method named by `value`, false if there is none (1, 1.1, 1.2, 1.3, 2.1, 2.2, 2.3)
+    static bool parse_projection(double value, Projection &out)
+    {
+        for (int family = 1; family <= 2; ++family)
+            for (int decimal = 0; decimal <= 3; ++decimal) {
+                if (family == 2 && decimal == 0) continue;
+                if (std::abs(value - (family + 0.1 * decimal)) < 1.5e-8) { // sqrt(eps), the reference's comparison (:293-304)
+                    out.pair = family == 2;
+                    out.start = decimal;
+                    return true;
+                }
+            }
+        return false;
+    }
+    Projection projection() const
+    {
+        Projection p;
+        parse_projection(settings_.projection_method, p);
+        return p;
+    }
 
     template <class RightHandSide>
     Solver(Matrix const &A, RightHandSide const &B, Matrix const &M) : op_A_(A), rhs_(BType(B)), op_M_(M) {}
@@ -219,6 +249,13 @@ public:
         s.keep_above = lookup_parameter(params, "Restart tolerance", s.tolerance * 1e-3); // default follows the tolerance (:84)
         s.shrink_on_convergence = lookup_parameter(params, "Minimize solution space", s.shrink_on_convergence);
         s.warm_start = lookup_parameter(params, "Restart from solution", s.warm_start);
+        const double method = lookup_parameter(params, "Projection method", s.projection_method);
+        Projection unused;
+        if (!parse_projection(method, unused)) {
+            std::cerr << "rails::Solver: 'Projection method' " << method << " is none of 1, 1.1, 1.2, 1.3, 2.1, 2.2, 2.3" << std::endl;
+            return 2;
+        }
+        s.projection_method = method;
         if (s.lanczos_steps <= s.expand_by) { // the estimate must offer more directions than a trip adds (:89-95)
             std::cerr << "rails::Solver: 'Lanczos iterations' (" << s.lanczos_steps << ") has to exceed 'Expand size' (" << s.expand_by << ")" << std::endl;
             return 1;
@@ -232,6 +269,14 @@ public:
     // standard one (`lyap(VAV, VBV)`, :384) instead of the generalized one; needs use_mass_matrix(true) and a symmetric definite M
     void use_mass_orthogonalisation(bool on) { ortho_m_ = on; }
     bool mass_orthogonalisation() const { return mass_ && ortho_m_; }
+    // opts.Ainv of matlab/RAILSsolver.m:18-22: the operator applied as A^-1 by the projection methods other than 1 (exact or not;
+    // any Matrix: a sparse LU solve, a Schur complement's inverse, a callback).  The solver keeps a copy of the handle.
+    void set_inverse(Matrix const &Ainv)
+    {
+        op_Ainv_ = Ainv;
+        has_inverse_ = true;
+    }
+    bool has_inverse() const { return has_inverse_; }
     void set_verbose(bool on) { verbose_ = on; }
     void set_max_trips(int n) { trip_budget_ = n; }
     // residual Lanczos carried in the (2k+p+1)-dimensional coefficient space where the backend supports it
@@ -250,8 +295,19 @@ public:
     int lanczos_iterations() const { return settings_.lanczos_steps; }
 
     // Low-rank solution X = V T V' of A X + X A' + B B' = 0 (A X M' + M X A' + B B' = 0 with a mass matrix)   (src/LyapunovSolver.hpp:100-346)
+    // A projection method other than 1 needs set_inverse(), and one that starts from B (x.2) needs B as a multivector: then the
+    // solve is refused (-2) and V, T are left as they are.
     int solve(MultiVector &V, DenseMatrix &T)
     {
+        const Projection proj = projection();
+        if (proj.uses_inverse() && !has_inverse_) {
+            std::cerr << "rails::Solver: 'Projection method' " << settings_.projection_method << " needs an inverse (set_inverse)" << std::endl;
+            return -2;
+        }
+        if (proj.start == 2 && rhs_.given_as_operator()) {
+            std::cerr << "rails::Solver: 'Projection method' " << settings_.projection_method << " starts from B, which is given as an operator" << std::endl;
+            return -2;
+        }
         Run run(*this, V, T);
         return run.go();
     }
@@ -471,6 +527,8 @@ private:
                     V_.orthogonalize();
             } else if (V_.N() != capacity_)
                 reserve_columns(V_, capacity_);
+            const Projection proj = s_.projection();
+            if (proj.uses_inverse() && proj.start != 3) open_with_inverse(proj);
             fresh_ = MultiVector(V_); // a deep copy: every column is still to be multiplied (:123)
             AV_ = MultiVector(V_, capacity_);
             AV_.resize(0);
@@ -483,6 +541,28 @@ private:
             }
             const double nb = s_.rhs_.norm2();
             scale_ = nb * nb;
+        }
+
+        // The start space of methods x.1 and x.2 (matlab/RAILSsolver.m:288-314): V0 (the columns open() made, x.1) or B (x.2), then
+        // V = A^-1 V0 (1.x) or [V0, A^-1 V0] (2.x), orthonormalised like any start space.
+        void open_with_inverse(Projection const &proj)
+        {
+            MultiVector V0 = proj.start == 2 ? MultiVector(s_.rhs_.panel()) : MultiVector(V_);
+            MultiVector inv;
+            {
+                ScopedTimer t(&s_.sections_, "Apply Ainv");
+                inv = s_.op_Ainv_ * V0;
+            }
+            const int width = (proj.pair ? V0.N() : 0) + inv.N();
+            capacity_ = std::max(capacity_, width);
+            reserve_columns(V_, capacity_);
+            V_.resize(0);
+            if (proj.pair) V_.push_back(V0);
+            V_.push_back(inv);
+            if (s_.mass_orthogonalisation())
+                m_orthogonalize(0);
+            else
+                V_.orthogonalize();
         }
 
         // capacity change that keeps the columns in use (resize up, then back: the contract's resize preserves data, src/StlWrapper.cpp:225-263)
@@ -629,12 +709,22 @@ private:
         // The Ritz vectors of the `add` largest |Ritz values| join V: add = min(expand_by, Ritz values available, room up to shrink_at
         // or n) (:306-307); capacity grows by 100 columns at a time (:311-332); only the new columns are orthogonalised (:340) and
         // they are the fresh ones of the next trip (:342).
+        // Methods other than 1 replace W by A^-1 W (1.x) or add [W, A^-1 W] (2.x: then at most half the room goes to Ritz vectors; with
+        // one column of room left only W joins) (matlab/RAILSsolver.m:520-530).
         void expand(typename Ops::Lanczos const &ritz, int width_before)
         {
+            const Projection proj = s_.projection();
             const int room = (opt_.shrink_at > 0 ? opt_.shrink_at : n_) - V_.N();
-            const int add = std::min(std::min(opt_.expand_by, ritz.eigenvalues.M()), room);
-            if (V_.N() + add > capacity_) {
-                capacity_ += 100;
+            int add = std::min(std::min(opt_.expand_by, ritz.eigenvalues.M()), room);
+            bool pair = proj.uses_inverse() && proj.pair;
+            const bool replace = proj.uses_inverse() && !proj.pair;
+            if (pair && room >= 2)
+                add = std::min(add, room / 2);
+            else
+                pair = false;
+            const int grow = pair ? 2 * add : add;
+            if (V_.N() + grow > capacity_) {
+                capacity_ += std::max(100, V_.N() + grow - capacity_);
                 reserve_columns(V_, capacity_);
                 reserve_columns(AV_, capacity_);
                 reserve_order(a_, capacity_);
@@ -651,7 +741,16 @@ private:
                 ScopedTimer t(&s_.sections_, "Expand");
                 ritz.append_to(V_, leading, add);
             }
-            int kept = add;
+            if ((pair || replace) && add > 0) {
+                MultiVector inv;
+                {
+                    ScopedTimer t(&s_.sections_, "Apply Ainv");
+                    inv = s_.op_Ainv_ * V_.view(width_before, width_before + add - 1);
+                }
+                if (replace) V_.resize(width_before);
+                V_.push_back(inv);
+            }
+            int kept = proj.uses_inverse() ? V_.N() - width_before : add;
             {
                 ScopedTimer t(&s_.sections_, "Orthogonalize");
                 if (s_.mass_orthogonalisation())
@@ -705,6 +804,8 @@ protected:
     Matrix op_A_;
     BType rhs_;
     Matrix op_M_;
+    Matrix op_Ainv_;
+    bool has_inverse_ = false;
     Settings settings_;
 
     bool mass_ = false;

@@ -146,6 +146,21 @@ def main(argv=None):
         solver.set_option("subspace", 0)
     if args.projected_lanczos and Mop is None:
         solver.set_option("projected_lanczos", 1)
+    # "Projection method" above 1 (opts.projection_method, matlab/RAILSsolver.m:7-24): the driver builds the inverse it needs
+    method = next((float(v) for k, v in params.items() if k.lower() == "projection method"), 1.0)
+    inverse = None
+    if method > 1:
+        if world > 1:
+            raise SystemExit("'Projection method' %g: the sparse LU inverse runs on one rank" % method)
+        t0 = time.time()
+        if schur is not None:
+            inverse = schur.inverse()
+            what = "Sinv, a sparse LU of the full matrix restricted to the %d Schur rows (matlab/RAILSschur.m:60-64)" % schur.m2
+        else:
+            inverse = rails_amd.SparseLU(ctx, (rowptr, col.astype(np.int32), val))
+            what = "a sparse LU of A"
+        solver.set_inverse(inverse)
+        _log(rank, "Projection method %g: A^-1 is %s; nnz(L+U) %d, factorised in %.2f s" % (method, what, inverse.nnz, time.time() - t0))
 
     _log(rank, "Performing solve")
     ctx.sync()
@@ -167,6 +182,8 @@ def main(argv=None):
         mmio.write_array(path(args.T), T, comment=note)
         print("wrote %s (%d x %d) and %s (%d x %d)" % (path(args.V), V.shape[0], V.shape[1], path(args.T), T.shape[0], T.shape[1]), flush=True)
     solver.close()
+    if inverse is not None:
+        inverse.close()
     ctx.close()
     if dist is not None:
         dist.barrier()

@@ -104,6 +104,7 @@ class SchurOperator:
         if self.m1 == 0:
             raise ValueError("the mass matrix is nonsingular: no Schur complement to take")
         As = sp.csr_matrix((val, col, rowptr), shape=(n, n))
+        self.A_full = As
         self.A11 = As[self.idx1][:, self.idx1].tocsc()
         self.A12 = As[self.idx1][:, self.idx2].tocsr()
         self.A21 = As[self.idx2][:, self.idx1].tocsr()
@@ -179,6 +180,13 @@ class SchurOperator:
         out[self.idx2] = V
         out[self.idx1] = -self.lu.solve(np.ascontiguousarray(self.A12 @ V))
         return out
+
+    def inverse(self):
+        """Sinv of matlab/RAILSschur.m:60-64: S^-1 x = (A^-1 E x)[idx2] with E putting x on the set-2 rows, from a sparse LU of the full
+        matrix A (its (1,1) block A11 is what S eliminates): a rails_amd.splu.SparseLU restricted to idx2 (the caller closes it)."""
+        from .splu import SparseLU
+
+        return SparseLU(self.ctx, self.A_full, rows=self.idx2)
 
     def dense(self):
         """the Schur complement as a dense matrix (tests, small problems)"""

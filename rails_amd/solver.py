@@ -39,6 +39,13 @@ class Solver:
     def set_option(self, name, value):
         check(self.lib.rails_solver_set_option(self.h, name.encode(), float(value)), "rails_solver_set_option")
 
+    def set_inverse(self, op):
+        """opts.Ainv of matlab/RAILSsolver.m:18-22 for the "Projection method" parameter (1.1 .. 2.3): any operator of A's row count --
+        a SparseLU's .op, a SchurOperator.inverse(), a HipOperatorWrapper (the object itself may be passed when it has an .op)."""
+        op = getattr(op, "op", op)
+        check(self.lib.rails_solver_set_inverse(self.h, op.h.h), "rails_solver_set_inverse")
+        self._inverse = op  # the handle must live as long as the solver uses it
+
     def set_trip_callback(self, fn):
         if fn is None:
             self._cb = None
