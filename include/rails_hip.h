@@ -297,6 +297,11 @@ int rails_panel_gemm_wide(rails_ctx *ctx, double alpha, const rails_panel *X, in
  * 1 = force column-wise, 2 = force block.  *used (may be NULL) receives the method used (1 column-wise, 2 block,
  * 3 block after one repair round: dependent columns replaced by their normalised residuals, see orth.hip). */
 int rails_orthogonalize(rails_ctx *ctx, rails_panel *V, int k_old, int w, int method, int *used);
+/* The same with a nullspace (opts.nullspace of matlab/RAILSsolver.m:538-616): columns [nc0, nc0+q) of the panel N (V's rows, not V
+ * itself; [N, V_old] orthonormal, as the solver keeps them) are projected out in every projection round of every path -- block, repair round, column-wise -- together with V's
+ * columns [0, k_old): one Gram pass [N V_old]'W, one all-reduce and one update W -= N D + V_old C per round (fused for q, w <= 32).
+ * q = 0 is rails_orthogonalize. */
+int rails_orthogonalize_deflated(rails_ctx *ctx, rails_panel *V, int k_old, int w, const rails_panel *N, int nc0, int q, int method, int *used);
 
 /* Fused residual Lanczos (src/LyapunovSolver.hpp:367-447): L steps of Lanczos on the implicit
  *   R = AV*T*MV^T + MV*T*AV^T + B*B^T      (MV == V for M = I)

@@ -46,6 +46,14 @@ int rails_solver_set_option(rails_solver *s, const char *name, double value);
  * itself is a parameter (rails_solver_set_parameter); rails_solver_apply_parameters returns code 2 for a value that is no method, and
  * rails_solver_solve refuses a method other than 1 without an inverse (RAILS_EINVAL). */
 int rails_solver_set_inverse(rails_solver *s, rails_csr *Ainv);
+/* opts.nullspace of matlab/RAILSsolver.m:33-34,221-222,538-616: N (host column-major, the LOCAL rows x q, leading dimension ldn, like B)
+ * spans a space that is projected out of every space that joins V -- the start space (cold, warm or A^-1 start) and every expansion --
+ * for a singular A with a known kernel.  The solve orthonormalises N (M-orthonormalises it with "mass_orthogonalisation", a deliberate
+ * deviation from the reference, whose Euclidean basis makes its M-projection no projector) and drops dependent columns; it is refused
+ * (*code = -2, V and T unchanged) when none is left or the rank reaches the problem size.  q = 0 clears it.  Both back ends. */
+int rails_solver_set_nullspace(rails_solver *s, const double *N_host, int64_t ldn, int q);
+/* columns of the nullspace the last solve kept after orthonormalisation (0 without one) */
+int rails_solver_nullspace_rank(rails_solver *s);
 
 /* called at the start of every loop trip with the index of that trip, and once after the last */
 typedef void (*rails_trip_fn)(void *user, int trip);

@@ -48,6 +48,8 @@ struct rails_solver {
     bool has_M = false;
     rails::HipOperatorWrapper Ainv; // rails_solver_set_inverse (the caller owns the handle)
     bool has_inv = false;
+    rails::HipMultiVectorWrapper N; // rails_solver_set_nullspace (null_q columns; 0: none)
+    int null_q = 0, null_rank = 0;
     bool mass = false;
     bool ortho_m = false; // V kept M-orthonormal (matlab/RAILSsolver.m opts.ortho = 'M'); needs mass
     rails_trip_fn trip_fn = nullptr;
@@ -177,6 +179,28 @@ extern "C" int rails_solver_set_inverse(rails_solver *s, rails_csr *Ainv)
     return RAILS_OK;
 }
 
+extern "C" int rails_solver_set_nullspace(rails_solver *s, const double *N_host, int64_t ldn, int q)
+{
+    if (!s || q < 0 || (q > 0 && (!N_host || ldn < s->m_local))) {
+        rails_set_error("rails_solver_set_nullspace: bad argument");
+        return RAILS_EINVAL;
+    }
+    s->null_q = q;
+    s->null_rank = 0;
+    if (q == 0) {
+        s->N = rails::HipMultiVectorWrapper();
+        s->solver->clear_nullspace();
+        return RAILS_OK;
+    }
+    s->N = rails::HipMultiVectorWrapper(s->m_local, q, s->ctx);
+    s->N.set_global_rows(s->m_global);
+    s->N.from_host(N_host, ldn);
+    s->solver->set_nullspace(s->N);
+    return RAILS_OK;
+}
+
+extern "C" int rails_solver_nullspace_rank(rails_solver *s) { return s ? s->null_rank : -1; }
+
 extern "C" int rails_solver_set_trip_callback(rails_solver *s, rails_trip_fn fn, void *user)
 {
     if (!s) return RAILS_EINVAL;
@@ -219,6 +243,7 @@ static int solve_in_coordinates(rails_solver *s)
     rails::SubspaceOperator Mc(s->mass ? s->M : s->A, basis);
     rails::SubspaceSolver solver(Ac, Bc, Mc);
     if (s->has_inv) solver.set_inverse(rails::SubspaceOperator(s->Ainv, basis));
+    if (s->null_q > 0) solver.set_nullspace(rails::SubspaceMultiVector::Absorb(basis, s->N)); // the one absorb of N: a live store from then on
     int prc = solver.set_parameters(s->params);
     if (prc != 0) return prc + 100;
     solver.set_verbose(s->verbose);
@@ -233,6 +258,8 @@ static int solve_in_coordinates(rails_solver *s)
         Vc.set_orthogonalized(Vc.N());
     }
     int rc = solver.solve(Vc, s->T);
+    s->null_rank = solver.nullspace_rank();
+    if (rc == -2) return rc; // refused before the first trip: V and T stay as they were
     s->V = Vc.materialise();
     s->V.set_orthogonalized(s->V.N());
     s->sub_trips = solver.trips();
@@ -276,8 +303,10 @@ extern "C" int rails_solver_solve(rails_solver *s, int *code, int *k)
         if (s->last_was_subspace) {
             rc = solve_in_coordinates(s);
             if (rc == -1000) return RAILS_EHIP;
-        } else
+        } else {
             rc = s->solver->solve(s->V, s->T);
+            s->null_rank = s->solver->nullspace_rank();
+        }
     } catch (std::bad_alloc const &) {
         rails_set_error("rails_solver_solve: out of host memory");
         return RAILS_ENOMEM;

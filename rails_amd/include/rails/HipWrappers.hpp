@@ -435,6 +435,18 @@ public:
         if (n_ > orthogonalized_) hip_ok(rails_orthogonalize(ctx_, panel_->p, orthogonalized_, n_ - orthogonalized_, 0, nullptr), "rails_orthogonalize");
         orthogonalized_ = n_;
     }
+    // the same against the orthonormal columns of N as well, N projected out in every round (the solver's nullspace, opts.nullspace)
+    void orthogonalize(HipMultiVectorWrapper const &N)
+    {
+        if (replicated_ || !panel_ || c0_ != 0 || N.replicated_ || !N.panel_) {
+            std::cerr << "rails_amd: orthogonalize(N) needs distributed multivectors, this one starting at column 0" << std::endl;
+            return;
+        }
+        if (n_ > orthogonalized_)
+            hip_ok(rails_orthogonalize_deflated(ctx_, panel_->p, orthogonalized_, n_ - orthogonalized_, N.panel_->p, N.c0_, std::max(N.n_, 0), 0, nullptr),
+                   "rails_orthogonalize_deflated");
+        orthogonalized_ = n_;
+    }
 
     // host round trips (tests, I/O)
     void from_host(const double *data, int64_t ld)

@@ -32,6 +32,7 @@
 #include <map>
 #include <numeric>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -39,6 +40,41 @@
 
 namespace rails
 {
+
+// Whether a MultiVector offers `orthogonalize(MultiVector const &N)`: the columns past its watermark orthonormalised against the orthonormal
+// columns of N and against all columns before them, with N projected out inside every round (a back end's own deflated orthogonalisation).
+template <class MultiVector, class = void>
+struct has_deflated_orthogonalize : std::false_type {
+};
+template <class MultiVector>
+struct has_deflated_orthogonalize<MultiVector, decltype(std::declval<MultiVector &>().orthogonalize(std::declval<MultiVector const &>()), void())>
+    : std::true_type {
+};
+
+// V's columns from `first` on, orthonormalised against N and against V's columns before `first`.  A back end with the deflated member does it
+// itself; any other goes through the contract: twice "project N out of the new columns, move the watermark back to `first`, orthogonalize()",
+// so that what orthogonalize() invents for a dependent column (normalised rounding noise) loses its part along N as well.
+template <class MultiVector>
+void orthogonalize_deflated(MultiVector &V, MultiVector const &N, int first, std::true_type)
+{
+    const int n = V.N();
+    V.resize(first); // (the contract's resize keeps the data: this only moves the watermark)
+    V.resize(n);
+    V.orthogonalize(N);
+}
+template <class MultiVector>
+void orthogonalize_deflated(MultiVector &V, MultiVector const &N, int first, std::false_type)
+{
+    const int n = V.N();
+    if (n <= first) return;
+    for (int round = 0; round < 2; ++round) {
+        MultiVector W = V.view(first, n - 1);
+        W -= N * N.dot(W);
+        V.resize(first);
+        V.resize(n);
+        V.orthogonalize();
+    }
+}
 
 // The right-hand side factor B, given either as an operator (Matrix) or as a tall panel (MultiVector) -- the two forms the
 // reference accepts through its B adaptor (src/MatrixOrMultiVectorWrapper.hpp:7-98).  Both members exist (the contract asks
@@ -277,6 +313,25 @@ public:
         has_inverse_ = true;
     }
     bool has_inverse() const { return has_inverse_; }
+    // opts.nullspace of matlab/RAILSsolver.m:33-34,221-222,311-313,527-529,538-616: a space projected out of every space that joins V
+    // (the known kernel of a singular A: a pure Neumann operator, disconnected parts, a pressure mode).  The solver keeps a copy of N (A's
+    // rows, any number of columns).  solve() orthonormalises it -- M-orthonormalises it under mass_orthogonalisation(), where the
+    // reference's Euclidean basis would not make its M-projection a projector -- and drops dependent columns.
+    void set_nullspace(MultiVector const &N)
+    {
+        nullspace_ = MultiVector(N);
+        has_nullspace_ = true;
+    }
+    void clear_nullspace()
+    {
+        nullspace_ = MultiVector();
+        null_basis_ = MultiVector();
+        has_nullspace_ = false;
+        null_rank_ = 0;
+    }
+    bool has_nullspace() const { return has_nullspace_; }
+    // columns of the nullspace the last solve kept (0 without one)
+    int nullspace_rank() const { return null_rank_; }
     void set_verbose(bool on) { verbose_ = on; }
     void set_max_trips(int n) { trip_budget_ = n; }
     // residual Lanczos carried in the (2k+p+1)-dimensional coefficient space where the backend supports it
@@ -296,9 +351,15 @@ public:
 
     // Low-rank solution X = V T V' of A X + X A' + B B' = 0 (A X M' + M X A' + B B' = 0 with a mass matrix)   (src/LyapunovSolver.hpp:100-346)
     // A projection method other than 1 needs set_inverse(), and one that starts from B (x.2) needs B as a multivector: then the
-    // solve is refused (-2) and V, T are left as they are.
+    // solve is refused (-2) and V, T are left as they are.  So is a nullspace (set_nullspace) with a row count other than A's, with no
+    // independent column, or with as many as the problem has dimensions.
     int solve(MultiVector &V, DenseMatrix &T)
     {
+        null_rank_ = 0;
+        if (has_nullspace_) {
+            const int rank = prepare_nullspace(V.M());
+            if (rank < 0) return rank;
+        }
         const Projection proj = projection();
         if (proj.uses_inverse() && !has_inverse_) {
             std::cerr << "rails::Solver: 'Projection method' " << settings_.projection_method << " needs an inverse (set_inverse)" << std::endl;
@@ -436,6 +497,53 @@ public:
     }
 
 private:
+    // `nullspace = Morth(opts.nullspace, [])` (matlab/RAILSsolver.m:221-222) into null_basis_: modified Gram-Schmidt, twice per column, in
+    // the inner product of V (M's under mass_orthogonalisation()); a column of which less than 1e-8 survives is dropped, as m_orthogonalize
+    // drops one.  Returns the rank kept, or -2 (with a message) when the solve has to be refused.
+    int prepare_nullspace(int n)
+    {
+        if (nullspace_.M() != n) {
+            std::cerr << "rails::Solver: the nullspace has " << nullspace_.M() << " rows, A has " << n << std::endl;
+            return -2;
+        }
+        const bool in_M = mass_orthogonalisation();
+        MultiVector Q(nullspace_);
+        int q = Q.N(), j = 0;
+        while (j < q) {
+            MultiVector v = Q.view(j);
+            const double n0 = v.norm();
+            double nrm = 0.0;
+            if (n0 > 0.0 && std::isfinite(n0)) {
+                v /= n0;
+                for (int pass = 0; pass < 2 && j > 0; ++pass) {
+                    MultiVector const before = Q.view(0, j - 1);
+                    MultiVector const Mv = in_M ? MultiVector(op_M_ * v) : MultiVector(v);
+                    v -= before * before.dot(Mv);
+                }
+                MultiVector const Mv = in_M ? MultiVector(op_M_ * v) : MultiVector(v);
+                nrm = std::sqrt(std::abs(v.dot(Mv)(0, 0)));
+            }
+            if (!(nrm >= 1e-8)) {
+                for (int l = j + 1; l < q; ++l) Q.view(l - 1) = Q.view(l);
+                Q.resize(--q);
+                continue;
+            }
+            v /= nrm;
+            ++j;
+        }
+        if (q == 0) {
+            std::cerr << "rails::Solver: the nullspace has no independent column" << std::endl;
+            return -2;
+        }
+        if (q >= n) {
+            std::cerr << "rails::Solver: the nullspace has rank " << q << ", the problem dimension is " << n << ": nothing is left to solve on" << std::endl;
+            return -2;
+        }
+        null_basis_ = Q;
+        null_rank_ = q;
+        return q;
+    }
+
     // One solve.  Everything the reference keeps in locals of solve() lives here, named for what it is.
     class Run
     {
@@ -524,9 +632,16 @@ private:
                 if (s_.mass_orthogonalisation())
                     m_orthogonalize(0);
                 else
-                    V_.orthogonalize();
-            } else if (V_.N() != capacity_)
-                reserve_columns(V_, capacity_);
+                    orthogonalize(0);
+            } else {
+                if (V_.N() != capacity_) reserve_columns(V_, capacity_);
+                if (deflating()) { // the caller's V loses its part along the nullspace like any start space (matlab/RAILSsolver.m:311-313)
+                    if (s_.mass_orthogonalisation())
+                        m_orthogonalize(0);
+                    else
+                        orthogonalize(0);
+                }
+            }
             const Projection proj = s_.projection();
             if (proj.uses_inverse() && proj.start != 3) open_with_inverse(proj);
             fresh_ = MultiVector(V_); // a deep copy: every column is still to be multiplied (:123)
@@ -561,6 +676,17 @@ private:
             V_.push_back(inv);
             if (s_.mass_orthogonalisation())
                 m_orthogonalize(0);
+            else
+                orthogonalize(0);
+        }
+
+        bool deflating() const { return s_.null_rank_ > 0; }
+
+        // V's columns from `first` on (the ones past the watermark), orthonormalised; with a nullspace, against it as well (:556-579)
+        void orthogonalize(int first)
+        {
+            if (deflating())
+                orthogonalize_deflated(V_, s_.null_basis_, first, has_deflated_orthogonalize<MultiVector>());
             else
                 V_.orthogonalize();
         }
@@ -756,7 +882,7 @@ private:
                 if (s_.mass_orthogonalisation())
                     kept = m_orthogonalize(width_before);
                 else
-                    V_.orthogonalize();
+                    orthogonalize(width_before);
             }
             fresh_ = V_.view(width_before, width_before + kept - 1);
         }
@@ -765,13 +891,24 @@ private:
         // new column is normalised, M-projected against all columns before it (twice: the reference's single sweep leaves a component
         // of relative size eps * cond, and V'MV = I is what makes the projected equation the standard one), M-normalised, and DROPPED
         // when less than 1e-8 of it is left (:592-594) -- V then grows by fewer columns than asked for.  Returns the columns kept.
+        // With a nullspace (M-orthonormal here) every pass projects it out first, with the same M v: `v -= n_i (n_i' M v)` (:600-616).
         int m_orthogonalize(int first)
         {
             int n = V_.N(), j = first;
             while (j < n) {
                 MultiVector v = V_.view(j);
                 v /= v.norm();
-                if (j > 0) {
+                if (deflating()) {
+                    MultiVector const &N = s_.null_basis_;
+                    for (int pass = 0; pass < 2; ++pass) {
+                        MultiVector const Mv = s_.op_M_ * v;
+                        v -= N * N.dot(Mv);
+                        if (j > 0) {
+                            MultiVector const before = V_.view(0, j - 1);
+                            v -= before * before.dot(Mv);
+                        }
+                    }
+                } else if (j > 0) {
                     MultiVector const before = V_.view(0, j - 1);
                     for (int pass = 0; pass < 2; ++pass) {
                         MultiVector const Mv = s_.op_M_ * v;
@@ -806,6 +943,10 @@ protected:
     Matrix op_M_;
     Matrix op_Ainv_;
     bool has_inverse_ = false;
+    MultiVector nullspace_;  // the caller's N (set_nullspace)
+    MultiVector null_basis_; // its orthonormal basis for the current solve (prepare_nullspace)
+    bool has_nullspace_ = false;
+    int null_rank_ = 0;
     Settings settings_;
 
     bool mass_ = false;

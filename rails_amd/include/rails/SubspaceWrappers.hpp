@@ -1089,10 +1089,17 @@ public:
     // which less than 1e-13 of its unit length survives -- nothing but rounding: a remainder of 1e-10 still is a direction good to 1e-6,
     // and slowly converging solves (the MOC problem) live on those -- is replaced by what the reference's noise is in effect: a fresh
     // random direction (drawn on the device, absorbed into the basis like every random vector), orthogonalised like any other column.
-    void orthogonalize()
+    void orthogonalize() { orthogonalize_against(nullptr); }
+    // The same with the nullspace N (orthonormal columns in this basis, the solver's opts.nullspace) projected out first in both passes --
+    // the random replacement column included.  Host arithmetic on coefficients, exact to the orthonormality of P: no device work.
+    void orthogonalize(SubspaceMultiVector const &N) { orthogonalize_against(&N); }
+
+private:
+    void orthogonalize_against(SubspaceMultiVector const *N)
     {
         std::vector<double> h;
         int replaced = 0;
+        const int q = N ? std::max(N->n_, 0) : 0;
         for (int i = orthogonalized_; i < n_; ++i) {
             const int r = rows();
             double *v = cptr(i);
@@ -1104,7 +1111,13 @@ public:
             double nr = nrm2();
             if (nr > 0.0)
                 for (int l = 0; l < r; ++l) v[l] /= nr;
-            for (int pass = 0; pass < 2 && i > 0; ++pass) {
+            for (int pass = 0; pass < 2 && (i > 0 || q > 0); ++pass) {
+                if (q > 0) {
+                    h.assign(q, 0.0);
+                    rails_dgemm('T', 'N', q, 1, r, 1.0, N->cptr(), N->ld(), v, ld(), 0.0, h.data(), q);
+                    rails_dgemm('N', 'N', r, 1, q, -1.0, N->cptr(), N->ld(), h.data(), q, 1.0, v, ld());
+                }
+                if (i == 0) continue;
                 h.assign(i, 0.0);
                 rails_dgemm('T', 'N', i, 1, r, 1.0, cptr(), ld(), v, ld(), 0.0, h.data(), i);
                 rails_dgemm('N', 'N', r, 1, i, -1.0, cptr(), ld(), h.data(), i, 1.0, v, ld());
@@ -1126,6 +1139,7 @@ public:
         orthogonalized_ = n_;
     }
 
+public:
     // device image P * C (m_local x n): used by the operator, the final read-out and the tests
     HipMultiVectorWrapper materialise() const { return basis_->materialise(cptr(), ld(), n_); }
     void to_host(double *data, int64_t ldd) const

@@ -35,6 +35,8 @@ def main(argv=None):
     ap.add_argument("--T", default="T.mtx")
     ap.add_argument("--warm-start", default=None, help="V.mtx of a previous solve (orthonormal columns): sets 'Restart from solution'")
     ap.add_argument("--set", action="append", default=[], metavar="NAME=VALUE", help="override one solver parameter, e.g. --set 'Tolerance=1e-6'")
+    ap.add_argument("--nullspace", default=None, help="N.mtx (dense array): a space projected out of the solution space (opts.nullspace), "
+                                                      "with the rows of the equation solved (the Schur rows after a Schur reduction)")
     ap.add_argument("--direct", action="store_true", help="direct back end (device panels for V, AV) instead of the default coordinate-space back end")
     ap.add_argument("--projected-lanczos", action="store_true", help="direct back end with the coefficient-space residual Lanczos (M = I only)")
     ap.add_argument("--seed", type=int, default=1)
@@ -80,6 +82,7 @@ def main(argv=None):
             raise SystemExit("M must be %d x %d" % (m, m))
         Mcsr = (mrp, mcol, mval)
     V0 = mmio.read_dense(path(args.warm_start)) if args.warm_start else None
+    Nsp = mmio.read_dense(path(args.nullspace)) if args.nullspace else None
     if V0 is not None:
         params["Restart from solution"] = 1
     _log(rank, "  A %d x %d, %d nonzeros; B %d x %d; %s; read in %.2f s" % (m, m, val.size, B.shape[0], B.shape[1],
@@ -130,6 +133,8 @@ def main(argv=None):
         elif not diagonal and np.any(mdiag == 0.0):
             raise SystemExit("M has zero diagonal entries but is not diagonal: not supported")
 
+    if Nsp is not None and Nsp.shape[0] != m:
+        raise SystemExit("--nullspace: N has %d rows, the equation solved has %d%s" % (Nsp.shape[0], m, " (the rows of the Schur complement)" if schur is not None else ""))
     _log(rank, "Creating solver")
     A = schur.op if schur is not None else operator((rowptr, col, val))
     Mop = operator(Mcsr) if Mcsr else None
@@ -146,6 +151,8 @@ def main(argv=None):
         solver.set_option("subspace", 0)
     if args.projected_lanczos and Mop is None:
         solver.set_option("projected_lanczos", 1)
+    if Nsp is not None:
+        solver.set_nullspace(Nsp[r0:r1])  # each rank its own rows, like B
     # "Projection method" above 1 (opts.projection_method, matlab/RAILSsolver.m:7-24): the driver builds the inverse it needs
     method = next((float(v) for k, v in params.items() if k.lower() == "projection method"), 1.0)
     inverse = None
@@ -172,6 +179,8 @@ def main(argv=None):
     if schur is not None:
         _log(rank, "Amount of matrix-vector products after the solve: %d" % schur.applies)
     _log(rank, "solve returned %d after %d iterations in %.3f s: V is %d x %d, relative residual %.3e" % (code, solver.trips(), dt, m, solver.k, rel))
+    if Nsp is not None:
+        _log(rank, "nullspace: %d of %d columns kept" % (solver.nullspace_rank, Nsp.shape[1]))
     if world > 1:
         parts = [None] * world
         dist.all_gather_object(parts, V)

@@ -46,6 +46,22 @@ class Solver:
         check(self.lib.rails_solver_set_inverse(self.h, op.h.h), "rails_solver_set_inverse")
         self._inverse = op  # the handle must live as long as the solver uses it
 
+    def set_nullspace(self, N):
+        """opts.nullspace of matlab/RAILSsolver.m:33-34,221-222,538-616: N (numpy, the local rows x q) spans a space projected out of
+        every space that joins V (the known kernel of a singular A).  None clears it.  See include/rails_solver.h."""
+        if N is None:
+            check(self.lib.rails_solver_set_nullspace(self.h, None, max(1, self.m_local), 0), "rails_solver_set_nullspace")
+            return
+        N = _f(N)
+        if N.shape[0] != self.m_local:
+            raise ValueError("the nullspace has %d rows, the solver %d local rows" % (N.shape[0], self.m_local))
+        check(self.lib.rails_solver_set_nullspace(self.h, _p(N), max(1, N.shape[0]), N.shape[1]), "rails_solver_set_nullspace")
+
+    @property
+    def nullspace_rank(self):
+        """columns of the nullspace the last solve kept after orthonormalisation (0 without one)"""
+        return self.lib.rails_solver_nullspace_rank(self.h)
+
     def set_trip_callback(self, fn):
         if fn is None:
             self._cb = None

@@ -320,6 +320,18 @@ class HipMultiVectorWrapper:
         self.orthogonalized = self.n
         return used.value
 
+    def orthogonalize_deflated(self, N, method=0):
+        """orthogonalize() with the orthonormal columns of N (another multivector; None: none) projected out as well"""
+        used = C.c_int(0)
+        k0 = self.orthogonalized
+        if self.c0 != 0:
+            raise _lib.RailsError("orthogonalize on a view that does not start at column 0 is not supported")
+        q = N.n if N is not None else 0
+        check(self.ctx.lib.rails_orthogonalize_deflated(self.ctx.h, self.panel.h, k0, self.n - k0, N.panel.h if q else None, N.c0 if q else 0, q,
+                                                        method, C.byref(used)), "rails_orthogonalize_deflated")
+        self.orthogonalized = self.n
+        return used.value
+
 
 class HipOperatorWrapper:
     """Device CSR operator: the Matrix role (`A * X`, `A.transpose() * X`)."""
