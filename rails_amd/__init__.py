@@ -6,6 +6,7 @@ templated Solver<Matrix, MultiVector, DenseMatrix>.  This Python package is the 
 mirror used by the tests and bench.py.  There is no CPU fallback anywhere in this package.
 """
 from ._lib import LIB_PATH, RailsError, load  # noqa: F401
+from .solution import Solution  # noqa: F401
 from .solver import Solver  # noqa: F401
 from .splu import SparseLU  # noqa: F401
 from .wrappers import (Context, HipMultiVectorWrapper, HipOperatorWrapper, lanczos_vectors,  # noqa: F401

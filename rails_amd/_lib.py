@@ -143,6 +143,9 @@ def load():
         _bind_solver(lib)
     except ImportError:
         pass
+    from ._solution_sigs import bind as _bind_solution
+
+    _bind_solution(lib)
     _lib = lib
     return lib
 

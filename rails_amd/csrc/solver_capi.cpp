@@ -11,6 +11,7 @@
 
 #include "rails/HipSolverOps.hpp"
 #include "rails/SubspaceSolverOps.hpp"
+#include "rails_solution.h"
 #include "rails_solver.h"
 
 void rails_set_error(const char *fmt, ...);
@@ -423,4 +424,19 @@ extern "C" int rails_solver_relative_residual(rails_solver *s, double *rel)
         }
     *rel = std::sqrt(std::fabs(tr)) / std::sqrt(bb);
     return RAILS_OK;
+}
+
+// the solution object (include/rails_solution.h) of the last solve: a device copy of V and the host T
+extern "C" int rails_solution_from_solver(rails_solver *s, rails_solution **out)
+{
+    if (!s || !out) {
+        rails_set_error("rails_solution_from_solver: null argument");
+        return RAILS_EINVAL;
+    }
+    const int k = s->V.N();
+    if (k < 1 || !s->V.panel() || s->T.M() != k || s->T.N() != k) {
+        rails_set_error("rails_solution_from_solver: no solution yet (V has %d columns, T is %d x %d)", k, s->T.M(), s->T.N());
+        return RAILS_EINVAL;
+    }
+    return rails_solution_create(s->ctx, s->V.panel(), s->V.offset(), k, (double *)s->T, s->T.LDA(), 1, out);
 }

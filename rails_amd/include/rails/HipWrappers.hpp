@@ -30,6 +30,7 @@
 
 #include "rails/HostDenseMatrix.hpp"
 #include "rails_hip.h"
+#include "rails_solution.h"
 
 namespace rails
 {
@@ -446,6 +447,18 @@ public:
             hip_ok(rails_orthogonalize_deflated(ctx_, panel_->p, orthogonalized_, n_ - orthogonalized_, N.panel_->p, N.c0_, std::max(N.n_, 0), 0, nullptr),
                    "rails_orthogonalize_deflated");
         orthogonalized_ = n_;
+    }
+
+    // diag(this * S * this') as an m x 1 multivector: the one-pass kernel of solution.hip (rails::Solution::variance picks it up)
+    HipMultiVectorWrapper rowquad(HostDenseMatrix const &S) const
+    {
+        HipMultiVectorWrapper out(*this, 1);
+        if (replicated_ || !panel_ || S.M() != n_ || S.N() != n_ || S.transposed()) {
+            std::cerr << "rails_amd: rowquad() needs a distributed multivector and an untransposed " << n_ << " x " << n_ << " matrix" << std::endl;
+            return out;
+        }
+        hip_ok(rails_panel_rowquad(ctx_, panel_->p, c0_, n_, (double *)S, S.raw_ld(), out.panel_->p, 0), "rails_panel_rowquad");
+        return out;
     }
 
     // host round trips (tests, I/O)

@@ -1,0 +1,127 @@
+// rails::Solution<MultiVector, DenseMatrix> -- the low-rank solution X = U S U' as an object: trace, products, leading eigenpairs and the
+// pointwise variance diag(X), written against the same MultiVector / DenseMatrix contract as the solver template (dot, operator*, view,
+// orthogonalize; DenseMatrix: (m, n) constructor, operator(), M(), N(), eigs).  It is the second half of the reference's driver
+// (src/main.cpp:140-170: the leading eigenpairs of the covariance, its trace, the share of each mode) in factored form: the reference
+// iterates with Anasazi on an operator that applies X; with U and S in hand the eigenproblem is a small dense one and exact.
+//
+// U need not be orthonormal (a lifted Schur solution is not) and may be rank deficient.  The object holds a VIEW of U (no copy of the
+// m x k data) and a deep copy of S.
+#ifndef RAILS_SOLUTION_HPP
+#define RAILS_SOLUTION_HPP
+
+#include <algorithm>
+#include <cmath>
+#include <numeric>
+#include <type_traits>
+#include <utility>
+#include <vector>
+
+namespace rails
+{
+
+// Whether a MultiVector offers `rowquad(DenseMatrix const &S)`: the m x 1 multivector of sum_{j,l} U(i,j) S(j,l) U(i,l), a back end's own
+// one-pass kernel (HipMultiVectorWrapper: rails_panel_rowquad).
+template <class MultiVector, class DenseMatrix, class = void>
+struct has_rowquad : std::false_type {
+};
+template <class MultiVector, class DenseMatrix>
+struct has_rowquad<MultiVector, DenseMatrix, decltype(std::declval<MultiVector const &>().rowquad(std::declval<DenseMatrix const &>()), void())> : std::true_type {
+};
+
+template <class MultiVector, class DenseMatrix>
+class Solution
+{
+    MultiVector U_;
+    DenseMatrix S_;
+
+    MultiVector variance_(std::true_type) const { return U_.rowquad(S_); }
+    // through the contract: column l of P = U S is one product with a k x 1 matrix; it is multiplied into U's column l entry by entry, which
+    // needs the element access of host back ends (operator()(i, j), as the reference's StlWrapper has it)
+    MultiVector variance_(std::false_type) const
+    {
+        const int k = U_.N(), m = U_.M();
+        MultiVector out(U_, 1);
+        out = 0.0;
+        for (int l = 0; l < k; ++l) {
+            DenseMatrix s(k, 1);
+            for (int j = 0; j < k; ++j) s(j, 0) = S_(j, l);
+            MultiVector p = U_ * s;
+            for (int i = 0; i < m; ++i) out(i, 0) += p(i, 0) * U_(i, l);
+        }
+        return out;
+    }
+
+public:
+    struct Eigs {
+        DenseMatrix values;  // found x 1, decreasing modulus
+        MultiVector vectors; // m x found, orthonormal
+        int found;
+    };
+
+    Solution(MultiVector const &U, DenseMatrix const &S) : U_(U.view()), S_(S)
+    {
+        const int k = S_.M();
+        for (int j = 0; j < k; ++j) // S is symmetric by definition of the object
+            for (int i = 0; i < j; ++i) S_(i, j) = S_(j, i) = 0.5 * (S_(i, j) + S_(j, i));
+    }
+
+    int rank() const { return U_.N(); }
+    MultiVector const &U() const { return U_; }
+    DenseMatrix const &S() const { return S_; }
+
+    // tr(X) = tr(S U'U): one dot
+    double trace() const
+    {
+        const int k = U_.N();
+        DenseMatrix G = U_.dot(U_);
+        double t = 0.0;
+        for (int j = 0; j < k; ++j)
+            for (int i = 0; i < k; ++i) t += S_(i, j) * G(j, i);
+        return t;
+    }
+
+    // X W = U (S (U'W))
+    MultiVector apply(MultiVector const &W) const
+    {
+        DenseMatrix C = U_.dot(W);
+        return U_ * (S_ * C);
+    }
+
+    // diag(X) as an m x 1 multivector
+    MultiVector variance() const { return variance_(has_rowquad<MultiVector, DenseMatrix>()); }
+
+    // The `want` eigenpairs of largest modulus (want <= 0: all), those with |lambda| <= tol max|lambda| dropped: Q = orthonormal basis of U,
+    // R = Q'U, the small symmetric eigenproblem of R S R', vectors = Q Z.  A dependent column of U leaves a column in Q that U has no part
+    // along (a zero row of R), so a rank-deficient U costs nothing but zero eigenvalues.
+    Eigs eigs(int want = 0, double tol = 0.0) const
+    {
+        const int k = U_.N();
+        MultiVector Q(U_); // deep copy
+        Q.orthogonalize();
+        DenseMatrix R = Q.dot(U_);
+        DenseMatrix M = (R * S_) * R.transpose();
+        for (int j = 0; j < k; ++j)
+            for (int i = 0; i < j; ++i) M(i, j) = M(j, i) = 0.5 * (M(i, j) + M(j, i));
+        DenseMatrix Zall, d;
+        M.eigs(Zall, d);
+        std::vector<int> order(k);
+        std::iota(order.begin(), order.end(), 0);
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return std::abs(d(a, 0)) > std::abs(d(b, 0)); });
+        const int cap = (want <= 0 || want > k) ? k : want;
+        const double dmax = k > 0 ? std::abs(d(order[0], 0)) : 0.0;
+        int found = 0;
+        while (found < cap && std::abs(d(order[found], 0)) > tol * dmax) ++found;
+        Eigs out{DenseMatrix(found, 1), MultiVector(), found};
+        DenseMatrix Z(k, found);
+        for (int q = 0; q < found; ++q) {
+            out.values(q, 0) = d(order[q], 0);
+            for (int i = 0; i < k; ++i) Z(i, q) = Zall(i, order[q]);
+        }
+        out.vectors = Q * Z;
+        return out;
+    }
+};
+
+} // namespace rails
+
+#endif

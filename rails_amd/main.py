@@ -1,6 +1,7 @@
 """Command-line driver: solve A X M' + M X A' + B B' = 0 for X = V T V' with matrices from MatrixMarket files.
 
     python -m rails_amd.main [params.xml] [--dir DIR] [--A A.mtx] [--B B.mtx] [--M M.mtx] [--V V.mtx] [--T T.mtx]
+                               [--eigs K] [--variance FILE]
     python -m torch.distributed.run --nproc-per-node N -m rails_amd.main ...      (one rank per GPU, rows partitioned)
 
 File names, formats and the parameter file follow the reference's driver (src/main.cpp:57-68,111,123-126): `A.mtx`, `B.mtx`
@@ -9,6 +10,11 @@ mass matrix with zeros on its diagonal (a descriptor system) is handled as the r
 Lyapunov equation is solved on the Schur complement A22 - A21 A11^-1 A12 of the rows where M is nonzero (rails_amd/schur.py; one
 rank), B is restricted to those rows and V has that many rows.  Otherwise M must be absent (identity) or symmetric positive
 definite.
+
+`--eigs K` and `--variance FILE` are the second half of the reference's driver (src/main.cpp:140-170) on the solution object
+(rails_amd.Solution): the K eigenvalues of largest modulus of the covariance X, each next to its share of the trace, written to
+`eigenvalues.mtx` / `eigenvectors.mtx`, and the pointwise variance diag(X).  After a Schur reduction both refer to the solution lifted to
+all unknowns (SchurOperator.lift), in the original row order.
 """
 import argparse
 import os
@@ -37,6 +43,9 @@ def main(argv=None):
     ap.add_argument("--set", action="append", default=[], metavar="NAME=VALUE", help="override one solver parameter, e.g. --set 'Tolerance=1e-6'")
     ap.add_argument("--nullspace", default=None, help="N.mtx (dense array): a space projected out of the solution space (opts.nullspace), "
                                                       "with the rows of the equation solved (the Schur rows after a Schur reduction)")
+    ap.add_argument("--eigs", type=int, default=0, metavar="K", help="print the K leading eigenvalues of X and their share of the trace "
+                                                                   "(src/main.cpp:162-168); writes eigenvalues.mtx and eigenvectors.mtx")
+    ap.add_argument("--variance", default=None, metavar="FILE", help="write diag(X), the pointwise variance, to FILE (MatrixMarket array)")
     ap.add_argument("--direct", action="store_true", help="direct back end (device panels for V, AV) instead of the default coordinate-space back end")
     ap.add_argument("--projected-lanczos", action="store_true", help="direct back end with the coefficient-space residual Lanczos (M = I only)")
     ap.add_argument("--seed", type=int, default=1)
@@ -190,6 +199,35 @@ def main(argv=None):
         mmio.write_array(path(args.V), V, comment=note)
         mmio.write_array(path(args.T), T, comment=note)
         print("wrote %s (%d x %d) and %s (%d x %d)" % (path(args.V), V.shape[0], V.shape[1], path(args.T), T.shape[0], T.shape[1]), flush=True)
+    if args.eigs > 0 or args.variance:
+        sol = solver.solution()
+        if schur is not None:
+            sol, small = schur.lift(sol), sol
+            small.close()
+        if args.variance:
+            var = sol.variance()
+            if world > 1:
+                parts = [None] * world
+                dist.all_gather_object(parts, var)
+                var = np.concatenate(parts)
+            if rank == 0:
+                mmio.write_array(path(args.variance), var.reshape(-1, 1), comment="rails_amd: diag(X), the pointwise variance of X = V T V'")
+                print("wrote %s (%d x 1)" % (path(args.variance), var.size), flush=True)
+        if args.eigs > 0:
+            trace = sol.trace()
+            lam, Z = sol.eigs(args.eigs)
+            if world > 1:
+                parts = [None] * world
+                dist.all_gather_object(parts, Z)
+                Z = np.vstack(parts)
+            if rank == 0:
+                for x in lam:
+                    print("%20.6g%20.6g" % (x, x / trace), flush=True)
+                note = "rails_amd: the %d eigenpairs of largest modulus of X = V T V'; trace %.17g" % (lam.size, trace)
+                mmio.write_array(path("eigenvalues.mtx"), lam.reshape(-1, 1), comment=note)
+                mmio.write_array(path("eigenvectors.mtx"), Z, comment=note)
+                print("wrote %s (%d x 1) and %s (%d x %d)" % (path("eigenvalues.mtx"), lam.size, path("eigenvectors.mtx"), Z.shape[0], Z.shape[1]), flush=True)
+        sol.close()
     solver.close()
     if inverse is not None:
         inverse.close()

@@ -181,6 +181,33 @@ class SchurOperator:
         out[self.idx1] = -self.lu.solve(np.ascontiguousarray(self.A12 @ V))
         return out
 
+    def lift(self, solution):
+        """The solution on ALL m1 + m2 unknowns, in the original row order, from a rails_amd.Solution on set 2: the same S and
+        U_full[idx2] = U, U_full[idx1] = -A11^-1 A12 U -- prolongate() on the device: the A12 SpMM, the A11 solve (DeviceLU when the
+        operator has it, the host LU otherwise) and two row scatters.  Trace, variance, eigs and apply of the result are those of the full
+        covariance [X11 X12; X21 X22] the reference's operator multiplies by once a solution is set (src/SchurOperator.cpp:191-342:
+        X22 = V T V', X12 = -A11^-1 A12 X22, X11 = A11^-1 A12 X22 A12' A11^-T), its trace that of SchurOperator::Trace.  One rank."""
+        from .solution import Solution
+
+        if solution.m != self.m2:
+            raise ValueError("lift: the solution has %d rows, the Schur complement %d (one rank only, like the operator)" % (solution.m, self.m2))
+        ctx, lib, k = self.ctx, self.ctx.lib, solution.k
+        U = solution.U()
+        W = HipMultiVectorWrapper(ctx, self.m1, k)
+        Z = HipMultiVectorWrapper(ctx, self.m1, k)
+        check(lib.rails_spmm(ctx.h, self.dA12.h.h, 0, U.panel.h, U.c0, k, W.panel.h, 0), "rails_spmm")
+        if self.dlu is not None:
+            self.dlu.solve(W, HipMultiVectorWrapper(ctx, self.m1, k), Z)
+        else:
+            Z.from_host(np.asfortranarray(self.lu.solve(np.ascontiguousarray(W.to_host())).reshape(self.m1, k)))
+        Z *= -1.0
+        full = HipMultiVectorWrapper(ctx, self.m1 + self.m2, k)
+        for part, idx in ((U, self.idx2), (Z, self.idx1)):
+            idx32 = np.ascontiguousarray(idx, dtype=np.int32)
+            check(lib.rails_panel_move_rows(ctx.h, part.panel.h, part.c0, k, idx32.ctypes.data_as(C.POINTER(C.c_int32)), idx32.size, 1, full.panel.h, 0),
+                  "rails_panel_move_rows")
+        return Solution(ctx, full, solution.S())
+
     def inverse(self):
         """Sinv of matlab/RAILSschur.m:60-64: S^-1 x = (A^-1 E x)[idx2] with E putting x on the set-2 rows, from a sparse LU of the full
         matrix A (its (1,1) block A11 is what S eliminates): a rails_amd.splu.SparseLU restricted to idx2 (the caller closes it)."""

@@ -98,6 +98,14 @@ class Solver:
         check(self.lib.rails_solver_get_T(self.h, _p(T), max(1, self.k)), "rails_solver_get_T")
         return T
 
+    def solution(self):
+        """the solution object X = V T V' of the last solve (rails_amd.Solution): a device copy of V, no host round trip"""
+        from .solution import Solution
+
+        h = C.c_void_p()
+        check(self.lib.rails_solution_from_solver(self.h, C.byref(h)), "rails_solution_from_solver")
+        return Solution(self.ctx, _handle=h)
+
     def trips(self):
         return self.lib.rails_solver_trips(self.h)
 
