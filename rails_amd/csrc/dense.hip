@@ -13,6 +13,13 @@
 // Reductions over rows are two-stage and deterministic: per-block partial tiles are written to a
 // workspace and summed in a fixed order by a second kernel (no float atomics), then all-reduced
 // over the ranks through the context hook.
+//
+// The row-split Gram, the wide-X Gram and the panel GEMM each have ONE body (dense_gram.inc, dense_gram_cols.inc, dense_panel_gemm.inc),
+// written against the left operand Xo: a OneSeg, columns of one panel, or a TwoSeg, [X1 | X2] in two panels (the deflated projection of
+// orth.hip: the nullspace and the old basis columns).  Every __global__ kernel declares its own parameters and attributes, builds Xo and
+// includes the body, so a one-segment kernel has the arguments, the attributes and -- compared per kernel on the assembly when the bodies
+// were merged -- the instructions and registers it had with a body of its own.  (The bodies are text, not __forceinline__ functions:
+// a function is optimised once on its own and again after inlining, which alone reordered operands in k_gram.)
 #include "rails_internal.h"
 
 #include <dlfcn.h>
@@ -31,6 +38,40 @@ __device__ __forceinline__ v4f64 mfma_f64(double a, double b, v4f64 c)
     return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
 }
 
+// The left operand X of a kernel body: col() turns a column index into the handle a lane keeps per tile, row() a row index into the base
+// pointer(s) of that row, at() both into an address.
+struct OneSeg {
+    const double *X;
+    int ld;
+    struct Row {
+        const double *x;
+    };
+    __device__ int col(int c) const { return c; }
+    __device__ Row row(int64_t r) const { return {X + r * ld}; }
+    __device__ static const double *at(Row r, int c) { return r.x + c; }
+};
+// [X1 | X2]: columns [0, a1) are columns of X1, [a1, a) columns of X2; a lane picks the segment by address
+struct TwoSeg {
+    const double *X1;
+    int ld1, a1;
+    const double *X2;
+    int ld2;
+    struct Col {
+        int off;
+        bool second;
+    };
+    struct Row {
+        const double *x1, *x2;
+    };
+    __device__ Col col(int c) const
+    {
+        const bool second = c >= a1;
+        return {second ? c - a1 : c, second};
+    }
+    __device__ Row row(int64_t r) const { return {X1 + r * ld1, X2 + r * ld2}; }
+    __device__ static const double *at(Row r, Col c) { return (c.second ? r.x2 : r.x1) + c.off; }
+};
+
 // ------------------------------------------------------------------------------- Gram ---
 // grid.x = row slabs, grid.y = tile groups (gi over X column tiles, gj over Y column tiles).
 // Each of the 4 waves accumulates TI x TJ output tiles over its share of the slab's rows.
@@ -38,99 +79,18 @@ template <int TI, int TJ>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) void k_gram(const double *__restrict__ X, int ldx, int a, const double *__restrict__ Y, int ldy,
                                               int b, int64_t m, int64_t rows_per_slab, int ngj, double *__restrict__ partial)
 {
-    __shared__ double red[TI * TJ * 256];
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int li = lane & 15, kk = lane >> 4;
-    const int gi = blockIdx.y / ngj, gj = blockIdx.y % ngj;
-    const int xcol0 = gi * TI * 16, ycol0 = gj * TJ * 16;
-    const int64_t r_begin = (int64_t)blockIdx.x * rows_per_slab;
-    int64_t r_end = r_begin + rows_per_slab;
-    if (r_end > m) r_end = m;
+    const OneSeg Xo{X, ldx};
+#include "dense_gram.inc"
+}
 
-    v4f64 acc[TI][TJ];
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int j = 0; j < TJ; ++j) acc[i][j] = (v4f64){0.0, 0.0, 0.0, 0.0};
-
-    // Loads without branches (a load inside a conditional gets its own exec-masked block, and the compiler then waits for ALL loads in
-    // flight -- the next step's too -- before the first MFMA: see k_gram_cols): columns outside the operands are clamped to the tile's
-    // first column (their results are never written), rows past the slab to its last row with the Y operand zeroed.
-    int xoff[TI], yoff[TJ];
-#pragma unroll
-    for (int i = 0; i < TI; ++i) xoff[i] = (xcol0 + 16 * i + li) < a ? xcol0 + 16 * i + li : 0;
-#pragma unroll
-    for (int j = 0; j < TJ; ++j) yoff[j] = (ycol0 + 16 * j + li) < b ? ycol0 + 16 * j + li : 0;
-
-    // software pipeline: the operands of the next 4-row step are in flight while the MFMAs of this one run (one step's loads per
-    // wave do not cover the HBM latency at 3 waves per SIMD: the Gram at 17 columns ran at 37 % of the HBM rate without it)
-    auto fetch = [&](int64_t r, double *xa, double *yb) {
-        const int64_t row = r + kk;
-        const bool rok = row < r_end;
-        const int64_t rc = rok ? row : (r_end > 0 ? r_end - 1 : 0);
-        const double *xr = X + rc * ldx;
-        const double *yr = Y + rc * ldy;
-#pragma unroll
-        for (int i = 0; i < TI; ++i) xa[i] = xr[xoff[i]];
-#pragma unroll
-        for (int j = 0; j < TJ; ++j) {
-            const double t = yr[yoff[j]];
-            yb[j] = rok ? t : 0.0;
-        }
-    };
-    double xa[TI], yb[TJ], xn[TI], yn[TJ];
-    int64_t r = r_begin + 4 * wave;
-    if (r < r_end) fetch(r, xa, yb);
-    for (; r < r_end; r += 16) {
-        const bool more = r + 16 < r_end;
-        if (more) fetch(r + 16, xn, yn);
-#pragma unroll
-        for (int i = 0; i < TI; ++i)
-#pragma unroll
-            for (int j = 0; j < TJ; ++j) acc[i][j] = mfma_f64(xa[i], yb[j], acc[i][j]);
-        if (more) {
-#pragma unroll
-            for (int i = 0; i < TI; ++i) xa[i] = xn[i];
-#pragma unroll
-            for (int j = 0; j < TJ; ++j) yb[j] = yn[j];
-        }
-    }
-
-    // cross-wave reduction in a fixed order (wave 0 += wave 1, 2, 3)
-    for (int w = 1; w < 4; ++w) {
-        if (wave == w) {
-#pragma unroll
-            for (int i = 0; i < TI; ++i)
-#pragma unroll
-                for (int j = 0; j < TJ; ++j)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) red[((i * TJ + j) * 4 + v) * 64 + lane] = acc[i][j][v];
-        }
-        __syncthreads();
-        if (wave == 0) {
-#pragma unroll
-            for (int i = 0; i < TI; ++i)
-#pragma unroll
-                for (int j = 0; j < TJ; ++j)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) acc[i][j][v] += red[((i * TJ + j) * 4 + v) * 64 + lane];
-        }
-        __syncthreads();
-    }
-    if (wave == 0) {
-        double *P = partial + (int64_t)blockIdx.x * a * b;
-#pragma unroll
-        for (int i = 0; i < TI; ++i)
-#pragma unroll
-            for (int j = 0; j < TJ; ++j)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    int ci = xcol0 + 16 * i + kk + 4 * v; // D row  -> X column
-                    int cj = ycol0 + 16 * j + li;         // D col  -> Y column
-                    if (ci < a && cj < b) P[ci + (int64_t)cj * a] = acc[i][j][v];
-                }
-    }
+// the same with X = [X1 | X2], a columns in all (no amdgpu_waves_per_eu: these kernels never had one)
+template <int TI, int TJ>
+__global__ __launch_bounds__(256) void k_gram2(const double *__restrict__ X1, int ldx1, int a1, const double *__restrict__ X2, int ldx2, int a,
+                                               const double *__restrict__ Y, int ldy, int b, int64_t m, int64_t rows_per_slab, int ngj,
+                                               double *__restrict__ partial)
+{
+    const TwoSeg Xo{X1, ldx1, a1, X2, ldx2};
+#include "dense_gram.inc"
 }
 
 // Wide-X / narrow-Y form (the projections [P | X]' X of the coordinate-space back end: a = dim + w >> b = w <= 32): the four waves
@@ -146,94 +106,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
                                                                                              const double *__restrict__ Y, int ldy, int b, int64_t m,
                                                                                              int64_t rows_per_slab, double *__restrict__ partial)
 {
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int li = lane & 15, kk = lane >> 4;
-    const int xcol0 = ((int)blockIdx.y * 4 + wave) * TI * 16;
-    if (xcol0 >= a) return; // wave-uniform; no barrier below
-    const int64_t r_begin = (int64_t)blockIdx.x * rows_per_slab;
-    int64_t r_end = r_begin + rows_per_slab;
-    if (r_end > m) r_end = m;
+    const OneSeg Xo{X, ldx};
+#include "dense_gram_cols.inc"
+}
 
-    v4f64 acc[TI][TJ];
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int j = 0; j < TJ; ++j) acc[i][j] = (v4f64){0.0, 0.0, 0.0, 0.0};
-    double acce[TI][NE > 0 ? NE : 1];
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int q = 0; q < (NE > 0 ? NE : 1); ++q) acce[i][q] = 0.0;
-    // Loads without branches and without selects on X: with `cond ? load : 0` every load sat in an exec-masked block of its own and the
-    // compiler waited for everything in flight (`s_waitcnt vmcnt(0)`: the next step's operands too) before the first MFMA of a step.
-    // Columns outside the operands are clamped to column 0 (their results are never written), rows past the slab to its last row
-    // with the Y operand zeroed: what comes back from there is multiplied by zero.
-    int xoff[TI], yoff[TJ], eoff[NE > 0 ? NE : 1];
-#pragma unroll
-    for (int i = 0; i < TI; ++i) xoff[i] = (xcol0 + 16 * i + li) < a ? xcol0 + 16 * i + li : 0;
-#pragma unroll
-    for (int j = 0; j < TJ; ++j) yoff[j] = (16 * j + li) < b ? 16 * j + li : 0;
-#pragma unroll
-    for (int q = 0; q < NE; ++q) eoff[q] = 16 * TJ + q < b ? 16 * TJ + q : 0;
-
-    auto fetch = [&](int64_t r, double *xa, double *yb, double *ye) {
-        const int64_t row = r + kk;
-        const bool rok = row < r_end;
-        const int64_t rc = rok ? row : (r_end > 0 ? r_end - 1 : 0);
-        const double *xr = X + rc * ldx;
-        const double *yr = Y + rc * ldy;
-#pragma unroll
-        for (int i = 0; i < TI; ++i) xa[i] = xr[xoff[i]];
-#pragma unroll
-        for (int j = 0; j < TJ; ++j) {
-            const double t = yr[yoff[j]];
-            yb[j] = rok ? t : 0.0;
-        }
-#pragma unroll
-        for (int q = 0; q < NE; ++q) {
-            const double t = yr[eoff[q]]; // (one address per row: a broadcast; a column past b is clamped and its result dropped)
-            ye[q] = rok ? t : 0.0;
-        }
-    };
-    auto work = [&](const double *xa, const double *yb, const double *ye) {
-#pragma unroll
-        for (int i = 0; i < TI; ++i) {
-#pragma unroll
-            for (int j = 0; j < TJ; ++j) acc[i][j] = mfma_f64(xa[i], yb[j], acc[i][j]);
-#pragma unroll
-            for (int q = 0; q < NE; ++q) acce[i][q] += xa[i] * ye[q];
-        }
-    };
-    double xa[TI], ya[TJ], xb[TI], yb[TJ], ea[NE > 0 ? NE : 1], eb[NE > 0 ? NE : 1];
-    fetch(r_begin, xa, ya, ea);
-    fetch(r_begin + 4, xb, yb, eb);
-    for (int64_t r = r_begin; r < r_end; r += 8) {
-        work(xa, ya, ea);
-        fetch(r + 8, xa, ya, ea); // rows past the slab come back as zeros
-        work(xb, yb, eb);
-        fetch(r + 12, xb, yb, eb);
-    }
-    double *P = partial + (int64_t)blockIdx.x * a * b;
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int j = 0; j < TJ; ++j)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                int ci = xcol0 + 16 * i + kk + 4 * v; // D row  -> X column
-                int cj = 16 * j + li;                 // D col  -> Y column
-                if (ci < a && cj < b) P[ci + (int64_t)cj * a] = acc[i][j][v];
-            }
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int q = 0; q < NE; ++q) {
-            const double t0 = acce[i][q];
-            const double t1 = __shfl(t0, li + 16, 64), t2 = __shfl(t0, li + 32, 64), t3 = __shfl(t0, li + 48, 64);
-            const int ci = xcol0 + 16 * i + li;
-            if (kk == 0 && ci < a && 16 * TJ + q < b) P[ci + (int64_t)(16 * TJ + q) * a] = ((t0 + t1) + t2) + t3;
-        }
+// the same with X = [X1 | X2], a columns in all (no amdgpu_waves_per_eu: these kernels never had one)
+template <int TI, int TJ, int NE>
+__global__ __launch_bounds__(256) void k_gram_cols2(const double *__restrict__ X1, int ldx1, int a1, const double *__restrict__ X2, int ldx2, int a,
+                                                    const double *__restrict__ Y, int ldy, int b, int64_t m, int64_t rows_per_slab,
+                                                    double *__restrict__ partial)
+{
+    const TwoSeg Xo{X1, ldx1, a1, X2, ldx2};
+#include "dense_gram_cols.inc"
 }
 
 // out[e] = sum_t partial[t][e] in a fixed order: 16 interleaved strands per element, then the strands 0..15
@@ -264,6 +148,15 @@ void launch_gram(rails_ctx *c, const double *X, int ldx, int a, const double *Y,
                        m, rps, ngj, partial);
 }
 
+template <int TI, int TJ>
+void launch_gram2(rails_ctx *c, const double *X1, int ldx1, int a1, const double *X2, int ldx2, int a, const double *Y, int ldy, int b, int64_t m,
+                  int64_t rps, int64_t nslab, double *partial)
+{
+    int ngi = (a + 16 * TI - 1) / (16 * TI), ngj = (b + 16 * TJ - 1) / (16 * TJ);
+    RAILS_LAUNCH((k_gram2<TI, TJ>), dim3((unsigned)nslab, (unsigned)(ngi * ngj)), dim3(256), 0, c->stream, X1, ldx1, a1, X2, ldx2, a, Y, ldy, b,
+                 m, rps, ngj, partial);
+}
+
 // ------------------------------------------------------------------------- panel GEMM ---
 // Each wave owns 16 rows and all r (<= 16*TR) output columns; the block streams C through LDS in
 // chunks of KC rows.  X is read with the k index permuted inside every 16-column block so that a
@@ -274,68 +167,21 @@ __global__ __launch_bounds__(256) void k_panel_gemm(double alpha, const double *
                                                     const double *__restrict__ C, int r, double beta, double *Yp,
                                                     int ldy, int64_t m, int vec_ok)
 {
-    constexpr int RL = 16 * TR + 4; // LDS row length (doubles): +4 keeps the 4 k-groups on disjoint banks
-    __shared__ double Cs[KC * RL];
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int li = lane & 15, kk = lane >> 4;
-    const int64_t r0 = ((int64_t)blockIdx.x * 4 + wave) * 16;
-    const int64_t myrow = r0 + li;
-    const bool rowok = myrow < m;
+    const OneSeg Xo{X, ldx};
+#define RAILS_PG_VEC4(c) (vec_ok && (c) + 4 <= k)
+#include "dense_panel_gemm.inc"
+}
 
-    v4f64 acc[TR];
-#pragma unroll
-    for (int t = 0; t < TR; ++t) acc[t] = (v4f64){0.0, 0.0, 0.0, 0.0};
-
-    const double *xrow = X + myrow * ldx;
-    for (int kc = 0; kc < k; kc += KC) {
-        __syncthreads();
-        // stage C[kc:kc+KC, 0:r) (col-major, ld = k) into LDS row-major, zero padded
-        for (int idx = threadIdx.x; idx < KC * 16 * TR; idx += 256) {
-            int kl = idx % KC, j = idx / KC;
-            double v = 0.0;
-            if (kc + kl < k && j < r) v = C[(kc + kl) + (int64_t)j * k];
-            Cs[kl * RL + j] = v;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int kb = 0; kb < KC; kb += 16) {
-            const int kcol = kc + kb + 4 * kk;
-            double xs[4];
-            if (rowok && vec_ok && kcol + 4 <= k) {
-                v2f64 t0 = *reinterpret_cast<const v2f64 *>(xrow + kcol);
-                v2f64 t1 = *reinterpret_cast<const v2f64 *>(xrow + kcol + 2);
-                xs[0] = t0.x;
-                xs[1] = t0.y;
-                xs[2] = t1.x;
-                xs[3] = t1.y;
-            } else {
-#pragma unroll
-                for (int s = 0; s < 4; ++s) xs[s] = (rowok && kcol + s < k) ? xrow[kcol + s] : 0.0;
-            }
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const double *crow = &Cs[(kb + 4 * kk + s) * RL + li];
-#pragma unroll
-                for (int t = 0; t < TR; ++t) acc[t] = mfma_f64(xs[s], crow[16 * t], acc[t]);
-            }
-        }
-    }
-    // D[row = kk + 4v][col = li]
-#pragma unroll
-    for (int t = 0; t < TR; ++t) {
-        const int j = 16 * t + li;
-        if (j >= r) continue;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int64_t row = r0 + kk + 4 * v;
-            if (row >= m) continue;
-            double *dst = Yp + row * ldy + j;
-            double val = alpha * acc[t][v];
-            if (beta != 0.0) val += beta * (*dst);
-            *dst = val;
-        }
-    }
+// the same with X = [X1 | X2], a columns in all; vec1 / vec2: the rows of that segment may be read 16 bytes at a time
+template <int TR, int KC>
+__global__ __launch_bounds__(256) void k_panel_gemm2(double alpha, const double *X1, int ldx1, int a1, const double *X2, int ldx2, int a,
+                                                     const double *__restrict__ C, int r, double beta, double *Yp, int ldy, int64_t m, int vec1,
+                                                     int vec2)
+{
+    const TwoSeg Xo{X1, ldx1, a1, X2, ldx2};
+    const int k = a;
+#define RAILS_PG_VEC4(c) (((c) + 4 <= a1 && vec1) || ((c) >= a1 && (c) + 4 <= a && vec2))
+#include "dense_panel_gemm.inc"
 }
 
 template <int TR, int KC>
@@ -468,12 +314,9 @@ int launch_pg_wide(rails_ctx *c, double alpha, const double *X, int ldx, int k, 
     return RAILS_OK;
 }
 
-} // namespace
-
-int rails_gram_dev(rails_ctx *c, const double *X, int ldx, const double *Y, int ldy, int64_t m, int a, int b, double *C_dev)
+// row slabs of a Gram product (a x b): enough blocks to fill the chip, partial-tile traffic bounded to ~4% of the input
+void gram_slabs(int64_t m, int a, int b, int64_t *nslab_out, int64_t *rps_out)
 {
-    if (a <= 0 || b <= 0) return RAILS_OK;
-    // slab count: enough blocks to fill the chip, partial-tile traffic bounded to ~4% of the input
     double bound = 0.02 * (double)m * (double)(a + b) / ((double)a * (double)b);
     int64_t nslab = (int64_t)std::min<double>(1024.0, std::max<double>(1.0, bound));
     int64_t maxslab = (m + 15) / 16;
@@ -481,7 +324,59 @@ int rails_gram_dev(rails_ctx *c, const double *X, int ldx, const double *Y, int 
     int64_t rps = (m + nslab - 1) / nslab;
     rps = (rps + 15) / 16 * 16;
     if (rps < 16) rps = 16;
-    nslab = std::max<int64_t>(1, (m + rps - 1) / rps);
+    *nslab_out = std::max<int64_t>(1, (m + rps - 1) / rps);
+    *rps_out = rps;
+}
+
+// wide-X form: tiles of 16 X-columns per wave, the choice that leaves the fewest idle tile slots in blocks of four waves
+// (one_tile: Y is one MFMA column tile, b <= 16 or the 17th column on the vector unit)
+int gram_cols_tiles(int ntiles, bool one_tile)
+{
+    const int cand2[3] = {3, 4, 5}, cand1[3] = {4, 6, 8};
+    const int *cand = one_tile ? cand1 : cand2;
+    int best = cand[1], best_cost = 1 << 30;
+    for (int q = 0; q < 3; ++q) {
+        int ti = cand[q], strips = (ntiles + ti - 1) / ti, cost = (strips + 3) / 4 * 4 * ti;
+        if (cost < best_cost) best = ti, best_cost = cost;
+    }
+    return best;
+}
+
+// the nine instantiations of the wide-X form; K is k_gram_cols or k_gram_cols2, the variadic part its operand arguments
+#define RAILS_GRAM_COLS_CASE(K, TI, TJ, NE, ...) RAILS_LAUNCH((K<TI, TJ, NE>), grid, dim3(256), 0, c->stream, __VA_ARGS__, Y, ldy, b, m, rps, c->ws)
+#define RAILS_GRAM_COLS(K, ...)                                                                                                            \
+    do {                                                                                                                                   \
+        const int ntiles = (a + 15) / 16, best = gram_cols_tiles(ntiles, b <= 16 || extra);                                                \
+        const dim3 grid((unsigned)nslab, (unsigned)(((ntiles + best - 1) / best + 3) / 4));                                                \
+        if (extra) {                                                                                                                       \
+            if (best == 4)                                                                                                                 \
+                RAILS_GRAM_COLS_CASE(K, 4, 1, 1, __VA_ARGS__);                                                                             \
+            else if (best == 6)                                                                                                            \
+                RAILS_GRAM_COLS_CASE(K, 6, 1, 1, __VA_ARGS__);                                                                             \
+            else                                                                                                                           \
+                RAILS_GRAM_COLS_CASE(K, 8, 1, 1, __VA_ARGS__);                                                                             \
+        } else if (b <= 16) {                                                                                                              \
+            if (best == 4)                                                                                                                 \
+                RAILS_GRAM_COLS_CASE(K, 4, 1, 0, __VA_ARGS__);                                                                             \
+            else if (best == 6)                                                                                                            \
+                RAILS_GRAM_COLS_CASE(K, 6, 1, 0, __VA_ARGS__);                                                                             \
+            else                                                                                                                           \
+                RAILS_GRAM_COLS_CASE(K, 8, 1, 0, __VA_ARGS__);                                                                             \
+        } else if (best == 3)                                                                                                              \
+            RAILS_GRAM_COLS_CASE(K, 3, 2, 0, __VA_ARGS__);                                                                                 \
+        else if (best == 4)                                                                                                                \
+            RAILS_GRAM_COLS_CASE(K, 4, 2, 0, __VA_ARGS__);                                                                                 \
+        else                                                                                                                               \
+            RAILS_GRAM_COLS_CASE(K, 5, 2, 0, __VA_ARGS__);                                                                                 \
+    } while (0)
+
+} // namespace
+
+int rails_gram_dev(rails_ctx *c, const double *X, int ldx, const double *Y, int ldy, int64_t m, int a, int b, double *C_dev)
+{
+    if (a <= 0 || b <= 0) return RAILS_OK;
+    int64_t nslab, rps;
+    gram_slabs(m, a, b, &nslab, &rps);
     size_t n = (size_t)a * b;
     RAILS_TRY(rails_ws_reserve(c, (size_t)nslab * n * sizeof(double)));
     if (b <= 16 && a <= 16)
@@ -489,44 +384,10 @@ int rails_gram_dev(rails_ctx *c, const double *X, int ldx, const double *Y, int 
     else if (b <= 32 && a >= 128) {
         static const int cols_form = getenv("RAILS_GRAM_COLS") ? atoi(getenv("RAILS_GRAM_COLS")) : 1;
         if (cols_form) {
-            // tiles of 16 X-columns per wave: the choice that leaves the fewest idle tile slots in blocks of four waves
-            const int ntiles = (a + 15) / 16;
-            // b = 17: one MFMA column tile and the 17th column on the vector unit (see k_gram_cols)
+            // b = 17: one MFMA column tile and the 17th column on the vector unit (see gram_cols_body)
             static const int extra_env = getenv("RAILS_GRAM_EXTRA_COLUMN") ? atoi(getenv("RAILS_GRAM_EXTRA_COLUMN")) : 1;
             const bool extra = extra_env && b == 17;
-            const int cand2[3] = {3, 4, 5}, cand1[3] = {4, 6, 8};
-            const int *cand = (b <= 16 || extra) ? cand1 : cand2;
-            int best = cand[1], best_cost = 1 << 30;
-            for (int q = 0; q < 3; ++q) {
-                int ti = cand[q], strips = (ntiles + ti - 1) / ti, cost = (strips + 3) / 4 * 4 * ti;
-                if (cost < best_cost) best = ti, best_cost = cost;
-            }
-            const dim3 grid((unsigned)nslab, (unsigned)(((ntiles + best - 1) / best + 3) / 4));
-#define RAILS_GRAM_COLS_CASE(TI, TJ, NE)                                                                                                 \
-    RAILS_LAUNCH((k_gram_cols<TI, TJ, NE>), grid, dim3(256), 0, c->stream, X, ldx, a, Y, ldy, b, m, rps, c->ws)
-            if (extra) {
-                if (best == 4)
-                    RAILS_GRAM_COLS_CASE(4, 1, 1);
-                else if (best == 6)
-                    RAILS_GRAM_COLS_CASE(6, 1, 1);
-                else
-                    RAILS_GRAM_COLS_CASE(8, 1, 1);
-            } else if (b <= 16) {
-                if (best == 4)
-                    RAILS_GRAM_COLS_CASE(4, 1, 0);
-                else if (best == 6)
-                    RAILS_GRAM_COLS_CASE(6, 1, 0);
-                else
-                    RAILS_GRAM_COLS_CASE(8, 1, 0);
-            } else {
-                if (best == 3)
-                    RAILS_GRAM_COLS_CASE(3, 2, 0);
-                else if (best == 4)
-                    RAILS_GRAM_COLS_CASE(4, 2, 0);
-                else
-                    RAILS_GRAM_COLS_CASE(5, 2, 0);
-            }
-#undef RAILS_GRAM_COLS_CASE
+            RAILS_GRAM_COLS(k_gram_cols, X, ldx, a);
         } else if (b <= 16)
             launch_gram<8, 1>(c, X, ldx, a, Y, ldy, b, m, rps, nslab, c->ws);
         else
@@ -543,6 +404,30 @@ int rails_gram_dev(rails_ctx *c, const double *X, int ldx, const double *Y, int 
         launch_gram<2, 4>(c, X, ldx, a, Y, ldy, b, m, rps, nslab, c->ws);
     else
         launch_gram<2, 4>(c, X, ldx, a, Y, ldy, b, m, rps, nslab, c->ws);
+    RAILS_LAUNCH(k_reduce_partials, dim3((unsigned)((n + 63) / 64)), dim3(1024), 0, c->stream, c->ws, nslab, (int64_t)n, C_dev);
+    RAILS_HIP_CHECK(hipGetLastError());
+    return RAILS_OK;
+}
+
+// the same for a left operand in two panels, [X1 X2]' Y with a = a1 + a2 columns (the deflated projection of orth.hip); b <= 32
+int rails_gram2_dev(rails_ctx *c, const double *X1, int ldx1, int a1, const double *X2, int ldx2, int a2, const double *Y, int ldy, int64_t m, int b,
+                    double *C_dev)
+{
+    const int a = a1 + a2;
+    if (a <= 0 || b <= 0) return RAILS_OK;
+    int64_t nslab, rps;
+    gram_slabs(m, a, b, &nslab, &rps);
+    const size_t n = (size_t)a * b;
+    RAILS_TRY(rails_ws_reserve(c, (size_t)nslab * n * sizeof(double)));
+    if (a >= 128 && b <= 32) {
+        const bool extra = b == 17;
+        RAILS_GRAM_COLS(k_gram_cols2, X1, ldx1, a1, X2, ldx2, a);
+    } else if (a <= 16 && b <= 16)
+        launch_gram2<1, 1>(c, X1, ldx1, a1, X2, ldx2, a, Y, ldy, b, m, rps, nslab, c->ws);
+    else if (b <= 16)
+        launch_gram2<8, 1>(c, X1, ldx1, a1, X2, ldx2, a, Y, ldy, b, m, rps, nslab, c->ws);
+    else
+        launch_gram2<4, 2>(c, X1, ldx1, a1, X2, ldx2, a, Y, ldy, b, m, rps, nslab, c->ws);
     RAILS_LAUNCH(k_reduce_partials, dim3((unsigned)((n + 63) / 64)), dim3(1024), 0, c->stream, c->ws, nslab, (int64_t)n, C_dev);
     RAILS_HIP_CHECK(hipGetLastError());
     return RAILS_OK;
@@ -946,6 +831,23 @@ int rails_panel_gemm_dev(rails_ctx *c, double alpha, const double *X, int ldx, i
         launch_pg<8, 32>(c, alpha, X, ldx, k, C_dev, r, beta, Y, ldy, m, vec_ok);
     else
         launch_pg<16, 16>(c, alpha, X, ldx, k, C_dev, r, beta, Y, ldy, m, vec_ok);
+    RAILS_HIP_CHECK(hipGetLastError());
+    return RAILS_OK;
+}
+
+// Y += alpha [X1 X2] C, C (a x r, ld a, a = a1 + a2) on the device; r <= 32
+int rails_panel_gemm2_dev(rails_ctx *c, double alpha, const double *X1, int ldx1, int a1, const double *X2, int ldx2, int a2, const double *C_dev,
+                          int r, double *Y, int ldy, int64_t m)
+{
+    if (r <= 0 || m <= 0) return RAILS_OK;
+    const int a = a1 + a2;
+    const int vec1 = ((((uintptr_t)X1) & 15) == 0 && (ldx1 % 2) == 0) ? 1 : 0;
+    const int vec2 = ((((uintptr_t)X2) & 15) == 0 && (ldx2 % 2) == 0 && (a1 % 2) == 0) ? 1 : 0;
+    const unsigned grid = (unsigned)((m + 63) / 64);
+    if (r <= 16)
+        RAILS_LAUNCH((k_panel_gemm2<1, 32>), dim3(grid), dim3(256), 0, c->stream, alpha, X1, ldx1, a1, X2, ldx2, a, C_dev, r, 1.0, Y, ldy, m, vec1, vec2);
+    else
+        RAILS_LAUNCH((k_panel_gemm2<2, 32>), dim3(grid), dim3(256), 0, c->stream, alpha, X1, ldx1, a1, X2, ldx2, a, C_dev, r, 1.0, Y, ldy, m, vec1, vec2);
     RAILS_HIP_CHECK(hipGetLastError());
     return RAILS_OK;
 }

@@ -264,5 +264,10 @@ int rails_gram_dev(rails_ctx *ctx, const double *X, int ldx, const double *Y, in
                    double *C_dev);
 int rails_panel_gemm_dev(rails_ctx *ctx, double alpha, const double *X, int ldx, int k, const double *C_dev,
                          int r, double beta, double *Y, int ldy, int64_t m);
+// the same with the left operand in two panels, [X1 X2] with a1 + a2 columns (b, r <= 32; Y += alpha [X1 X2] C)
+int rails_gram2_dev(rails_ctx *ctx, const double *X1, int ldx1, int a1, const double *X2, int ldx2, int a2, const double *Y, int ldy, int64_t m,
+                    int b, double *C_dev);
+int rails_panel_gemm2_dev(rails_ctx *ctx, double alpha, const double *X1, int ldx1, int a1, const double *X2, int ldx2, int a2,
+                          const double *C_dev, int r, double *Y, int ldy, int64_t m);
 
 #endif

@@ -130,3 +130,22 @@ def test_without_a_nullspace_is_bitwise_rails_orthogonalize(ctx, k_old, w):
     u2 = X2.orthogonalize_deflated(None, 0)
     assert u1 == u2
     assert np.array_equal(X1.to_host(), X2.to_host())
+
+
+@pytest.mark.parametrize("q,k_old,w", [(3, 0, 5), (1, 127, 16), (5, 37, 17), (4, 300, 17), (32, 128, 32)])
+def test_deflating_is_bitwise_orthogonalize_on_one_panel(ctx, q, k_old, w):
+    """[N | V_old] in two panels (the two-segment kernels) against the same columns in one panel (the one-segment kernels): one kernel
+    body for both operand forms and the same summation order, so the new columns agree bit for bit"""
+    m = 5003
+    g = np.random.default_rng(100 * q + k_old + w)
+    NV = basis(g, m, q + k_old)
+    N, Vold = NV[:, :q], NV[:, q:]
+    W = g.uniform(-1, 1, (m, w))
+    X1 = MV(ctx, np.hstack([Vold, W]), capacity=k_old + w)
+    X1.orthogonalized = k_old
+    u1 = X1.orthogonalize_deflated(MV(ctx, N), 0)
+    X2 = MV(ctx, np.hstack([N, Vold, W]), capacity=q + k_old + w)
+    X2.orthogonalized = q + k_old
+    u2 = X2.orthogonalize(0)
+    assert u1 == u2
+    assert np.array_equal(X1.to_host()[:, k_old:], X2.to_host()[:, q + k_old:])
