@@ -226,8 +226,9 @@ void transpose_csr(int64_t n, const std::vector<int64_t> &rp, const std::vector<
         }
 }
 
-int sweep(rails_ctx *c, rails_lu *lu, const LuTri &T, bool first, bool last, const int32_t *in_map, const int32_t *out_pos, const double *X, int ldx,
-          double *Y, int ldy, int nc)
+// a solve is a first sweep (gathers from X) and a last one (scatters to Y): the only two forms of the kernels that are built
+int sweep(rails_ctx *c, rails_lu *lu, const LuTri &T, bool first, const int32_t *in_map, const int32_t *out_pos, const double *X, int ldx, double *Y, int ldy,
+          int nc)
 {
     double *W = lu->work;
     const int ldw = lu->work_ld;
@@ -242,14 +243,10 @@ int sweep(rails_ctx *c, rails_lu *lu, const LuTri &T, bool first, bool last, con
             RAILS_LAUNCH((k_lu_run<F, L>), dim3((unsigned)nc), dim3(s.threads), 0, c->stream, T.rowptr, T.col, T.val, T.diag, T.order,          \
                          T.level_ptr_dev, s.l0, s.l1, in_map, out_pos, X, ldx, W, ldw, Y, ldy);                                                 \
     } while (0)
-        if (first && last)
-            RAILS_LU_LAUNCH(true, true);
-        else if (first)
+        if (first)
             RAILS_LU_LAUNCH(true, false);
-        else if (last)
-            RAILS_LU_LAUNCH(false, true);
         else
-            RAILS_LU_LAUNCH(false, false);
+            RAILS_LU_LAUNCH(false, true);
 #undef RAILS_LU_LAUNCH
         lu->last_launches++;
     }
@@ -366,8 +363,8 @@ extern "C" int rails_lu_solve(rails_ctx *c, rails_lu *lu, int trans, const rails
     const LuTri &first = lu->tri[trans ? 2 : 0], &second = lu->tri[trans ? 3 : 1];
     const double *Xp = X->d + xc0;
     double *Yp = Y->d + yc0;
-    RAILS_TRY(sweep(c, lu, first, true, false, lu->in_map[t], lu->out_pos[t], Xp, X->ld, Yp, Y->ld, nc));
-    RAILS_TRY(sweep(c, lu, second, false, true, lu->in_map[t], lu->out_pos[t], Xp, X->ld, Yp, Y->ld, nc));
+    RAILS_TRY(sweep(c, lu, first, true, lu->in_map[t], lu->out_pos[t], Xp, X->ld, Yp, Y->ld, nc));
+    RAILS_TRY(sweep(c, lu, second, false, lu->in_map[t], lu->out_pos[t], Xp, X->ld, Yp, Y->ld, nc));
     RAILS_HIP_CHECK(hipGetLastError());
     return RAILS_OK;
 }
