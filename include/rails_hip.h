@@ -327,6 +327,9 @@ int rails_lanczos_start(rails_ctx *ctx, const rails_panel *AV, int avc0, const r
  * host column-major, lds).  Replaces `eigenvectors = Q * v` (src/LyapunovSolver.hpp:443); passing only the
  * selected columns of v writes the expansion vectors straight into V's tail (:338-339). */
 int rails_lanczos_vectors(rails_ctx *ctx, const double *S_host, int lds, int w, rails_panel *Out, int oc0);
+/* Which pass kernel the context's last rails_resid_lanczos / rails_lanczos_start launched: k_lanczos_pass<nch, unroll> (nch = 128-column
+ * pair chunks per lane, unroll = rows in flight per wave) on nblocks blocks.  Read-only; an error before the first run. */
+int rails_lanczos_last_launch(rails_ctx *ctx, int *nch, int *unroll, int *nblocks);
 int rails_lanczos_release(rails_ctx *ctx); /* frees the Lanczos vectors kept by the context (also done by rails_ctx_destroy) */
 
 /* ---------------------------------------------------------- timing helpers --- */

@@ -98,6 +98,7 @@ SIGNATURES = {
                                       _dp, C.c_int, _ip]),
     "rails_lanczos_start": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _dp]),
     "rails_lanczos_vectors": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _vp, C.c_int]),
+    "rails_lanczos_last_launch": (C.c_int, [_vp, _ip, _ip, _ip]),
     "rails_lanczos_release": (C.c_int, [_vp]),
     "rails_timer_start": (C.c_int, [_vp]),
     "rails_timer_stop": (C.c_int, [_vp, _dp]),

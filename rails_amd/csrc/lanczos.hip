@@ -27,6 +27,7 @@ struct rails_lanczos_state {
     int L = 0;
     double *small = nullptr; // T, coefficients, reduced sums, state, alphas, betas
     size_t small_bytes = 0;
+    int last_nch = 0, last_unroll = 0, last_nblocks = 0; // what the last lz_run launched (rails_lanczos_last_launch)
 };
 
 // one state per context: the Lanczos vectors of the context's last run (several contexts may live in one process,
@@ -444,10 +445,15 @@ int lz_unroll()
     return u;
 }
 
-void launch_pass(rails_ctx *c, const LzArgs &a, int nch, int *nblocks_io, bool size_only)
+int pass_unroll(int nch)
 {
     int u = lz_unroll();
-    if (nch >= 3 && u > 2) u = 2;
+    return (nch >= 3 && u > 2) ? 2 : u;
+}
+
+void launch_pass(rails_ctx *c, const LzArgs &a, int nch, int *nblocks_io, bool size_only)
+{
+    const int u = pass_unroll(nch);
 #define RAILS_LZ_CASE(N, UU) \
     if (nch == N && u == UU) return launch_pass_u<N, UU>(c, a, nblocks_io, size_only);
     RAILS_LZ_CASE(1, 1) RAILS_LZ_CASE(1, 2) RAILS_LZ_CASE(1, 4) RAILS_LZ_CASE(2, 1) RAILS_LZ_CASE(2, 2) RAILS_LZ_CASE(2, 4)
@@ -500,6 +506,9 @@ static int lz_run(rails_ctx *c, const rails_panel *AV, int avc0, const rails_pan
     }
     nblocks = (int)std::min<int64_t>((ngroups + 3) / 4, (int64_t)nblocks);
     if (nblocks < 1) nblocks = 1;
+    S.last_nch = nch;
+    S.last_unroll = pass_unroll(nch);
+    S.last_nblocks = nblocks;
     // small device block: T | coef | sums | state(8) | alphas(L+2) | betas(L+2)
     size_t nsmall = (size_t)k * k + ncoef + ncoef + 8 + 2 * (size_t)(L + 2);
     if (nsmall * sizeof(double) > S.small_bytes) {
@@ -628,6 +637,17 @@ extern "C" int rails_lanczos_vectors(rails_ctx *c, const double *S_host, int lds
     }
     RAILS_HIP_CHECK(hipGetLastError());
     RAILS_HIP_CHECK(rails_stream_sync(c));
+    return RAILS_OK;
+}
+
+extern "C" int rails_lanczos_last_launch(rails_ctx *c, int *nch, int *unroll, int *nblocks)
+{
+    RAILS_REQUIRE(c && nch && unroll && nblocks, "rails_lanczos_last_launch: null argument");
+    const rails_lanczos_state &S = lz_state(c);
+    RAILS_REQUIRE(S.last_nblocks > 0, "rails_lanczos_last_launch: no Lanczos run on this context");
+    *nch = S.last_nch;
+    *unroll = S.last_unroll;
+    *nblocks = S.last_nblocks;
     return RAILS_OK;
 }
 
