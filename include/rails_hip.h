@@ -157,6 +157,13 @@ int rails_csr_prepare(rails_ctx *ctx, rails_csr *A, int trans, int nc, int *kern
 /* Statistics of the sweep kernel's schedule for nc columns, once it has been built:
  * out[0] slot efficiency, [1] X rows staged per matrix row and chunk, [2] lock-step trips, [3] 1 if the schedule exists. */
 int rails_csr_sweep_stats(rails_csr *A, int nc, double *out);
+/* The LDS-staged footprint kernel's tile plan and its most recent launch (out has room for 16):
+ * out[0] 1 once the plan has been looked at, [1] 1 if it was accepted, [2] 1 for boxes of a structured grid (0: runs of consecutive rows),
+ * [3] tiles, [4] rows of the largest tile, [5] largest column footprint, [6] most LDS rows a footprint is spread over, [7] most nonzeros
+ * of a row, [8] nonzeros per staged X row; the launch: [9] 0 none yet, 1 k_spmm_tiled, 2 k_spmm_tiled_pipe, 3 k_spmm_tiled_reg,
+ * [10] columns per chunk KC, [11] register slots per row NNZ, [12] staging slots per thread NL, [13] 16-byte vectors per lane V2,
+ * [14] chunks in flight NS (zeros where a kernel has no such parameter); [15] 0. */
+int rails_csr_tile_stats(rails_csr *A, double *out);
 /* A rectangular operator, n_rows x n_cols, all columns local: in rails_spmm X has n_cols rows and Y n_rows; no transposed apply, no
  * ghost rows.  Role: the off-diagonal blocks A12, A21 of the reference's Schur complement operator (src/SchurOperator.cpp:181-214). */
 int rails_csr_create_rect(rails_ctx *ctx, int64_t n_rows, int64_t n_cols, const int64_t *rowptr, const int32_t *col, const double *val,

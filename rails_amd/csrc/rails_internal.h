@@ -183,6 +183,7 @@ struct rails_csr {
     int max_fp = 0, max_nz = 0, max_pos = 0;
     double tile_reuse = 0.0;
     bool tile_grid = false;
+    int tl_kernel = 0, tl_kc = 0, tl_nnz = 0, tl_nl = 0, tl_v2 = 0, tl_ns = 0; // the most recent LDS-staged launch (rails_csr_tile_stats)
     const char *last_kernel = "";
     // operator given by its action (rails_csr_create_callback): rails_spmm hands the panels over
     rails_apply_fn apply_cb = nullptr;

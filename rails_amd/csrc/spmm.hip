@@ -1441,6 +1441,12 @@ bool make_plan(const rails_csr *A, const std::vector<int32_t> &tile_of_row, int6
         P.max_rows = std::max(P.max_rows, r1 - r0);
     }
     P.reuse = P.fp.empty() ? 0.0 : (double)A->nnz / (double)P.fp.size();
+    // one element of padding: the register-resident kernel loads entry 0 of a row and footprint row 0 of a tile unconditionally, and
+    // for an empty last row (a last tile of empty rows) those are one past the end
+    P.t_val.push_back(0.0);
+    P.t_lcol.push_back(0);
+    P.fp.push_back(0);
+    P.fp_pos.push_back(0);
     return true;
 }
 
@@ -1456,6 +1462,41 @@ int upload(T **dst, const std::vector<T> &src)
 } // namespace
 
 bool rails_detect_grid(const rails_csr *A, int64_t *nx, int64_t *ny, int64_t *nz) { return detect_grid(A, nx, ny, nz); }
+
+// what the most recent LDS-staged launch was (rails_csr_tile_stats): kernel 1 = k_spmm_tiled, 2 = k_spmm_tiled_pipe, 3 = k_spmm_tiled_reg
+static void tile_launched(rails_csr *A, int kernel, int kc, int nnz, int nl, int v2, int ns)
+{
+    A->tl_kernel = kernel;
+    A->tl_kc = kc;
+    A->tl_nnz = nnz;
+    A->tl_nl = nl;
+    A->tl_v2 = v2;
+    A->tl_ns = ns;
+}
+
+extern "C" int rails_csr_tile_stats(rails_csr *A, double *out)
+{
+    RAILS_REQUIRE(A && out, "rails_csr_tile_stats: null argument");
+    for (int i = 0; i < 16; ++i) out[i] = 0.0;
+    out[0] = A->tiled_ready ? 1.0 : 0.0;
+    out[7] = (double)A->max_row_nnz;
+    if (A->tiled_ok) {
+        out[1] = 1.0;
+        out[2] = A->tile_grid ? 1.0 : 0.0;
+        out[3] = (double)A->n_tiles;
+        out[4] = (double)A->tile_rows;
+        out[5] = (double)A->max_fp;
+        out[6] = (double)A->max_pos;
+        out[8] = A->tile_reuse;
+    }
+    out[9] = (double)A->tl_kernel;
+    out[10] = (double)A->tl_kc;
+    out[11] = (double)A->tl_nnz;
+    out[12] = (double)A->tl_nl;
+    out[13] = (double)A->tl_v2;
+    out[14] = (double)A->tl_ns;
+    return RAILS_OK;
+}
 
 static bool rails_csr_is_grid(rails_csr *A)
 {
@@ -1615,6 +1656,7 @@ int rails_spmm_tiled(rails_ctx *c, rails_csr *A, const double *X, int ldx, const
     do {                                                                                                                               \
         RAILS_HIP_CHECK(hipFuncSetAttribute((const void *)k_spmm_tiled_reg<KCV, NNZV, NLV, V2V, NSV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_reg)); \
         RAILS_LAUNCH((k_spmm_tiled_reg<KCV, NNZV, NLV, V2V, NSV>), dim3((unsigned)grid), dim3(256), lds_reg, c->stream, RAILS_REG_ARGS); \
+        tile_launched(A, 3, KCV, NNZV, NLV, V2V, NSV);                                                                                 \
     } while (0)
 #define RAILS_LAUNCH_REG(KCV, NNZV, NLV, V2V)                                                                                         \
     do {                                                                                                                               \
@@ -1664,6 +1706,7 @@ int rails_spmm_tiled(rails_ctx *c, rails_csr *A, const double *X, int ldx, const
     do {                                                                                                                               \
         RAILS_HIP_CHECK(hipFuncSetAttribute((const void *)k_spmm_tiled_pipe<KCV, NLV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pipe)); \
         RAILS_LAUNCH((k_spmm_tiled_pipe<KCV, NLV>), dim3((unsigned)grid), dim3(256), lds_pipe, c->stream, RAILS_TILED_ARGS);  \
+        tile_launched(A, 2, KCV, 0, NLV, 0, 0);                                                                                        \
     } while (0)
     if (pipe) {
         if (KC == 8) {
@@ -1676,9 +1719,11 @@ int rails_spmm_tiled(rails_ctx *c, rails_csr *A, const double *X, int ldx, const
     } else if (KC == 8) {
         RAILS_HIP_CHECK(hipFuncSetAttribute((const void *)k_spmm_tiled<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         RAILS_LAUNCH((k_spmm_tiled<8>), dim3((unsigned)grid), dim3(256), lds, c->stream, RAILS_TILED_ARGS);
+        tile_launched(A, 1, 8, 0, 0, 0, 0);
     } else {
         RAILS_HIP_CHECK(hipFuncSetAttribute((const void *)k_spmm_tiled<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         RAILS_LAUNCH((k_spmm_tiled<16>), dim3((unsigned)grid), dim3(256), lds, c->stream, RAILS_TILED_ARGS);
+        tile_launched(A, 1, 16, 0, 0, 0, 0);
     }
 #undef RAILS_LAUNCH_PIPE
 #undef RAILS_TILED_ARGS

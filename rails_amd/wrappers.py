@@ -417,6 +417,16 @@ class HipOperatorWrapper:
         check(self.ctx.lib.rails_csr_sweep_stats(self.h.h, nc, out), "rails_csr_sweep_stats")
         return {"efficiency": out[0], "staged_rows_per_row": out[1], "trips": int(out[2]), "built": bool(out[3])}
 
+    def tile_stats(self):
+        """The LDS-staged kernel's tile plan and its most recent launch (rails_csr_tile_stats): which of the three kernels ran and the
+        template parameters of that instantiation, zeros where a kernel has none."""
+        out = (C.c_double * 16)()
+        check(self.ctx.lib.rails_csr_tile_stats(self.h.h, out), "rails_csr_tile_stats")
+        kernels = ("", "k_spmm_tiled", "k_spmm_tiled_pipe", "k_spmm_tiled_reg")
+        return {"built": bool(out[0]), "accepted": bool(out[1]), "grid": bool(out[2]), "n_tiles": int(out[3]), "tile_rows": int(out[4]),
+                "max_fp": int(out[5]), "max_pos": int(out[6]), "max_row_nnz": int(out[7]), "reuse": out[8], "kernel": kernels[int(out[9])],
+                "KC": int(out[10]), "NNZ": int(out[11]), "NL": int(out[12]), "V2": int(out[13]), "NS": int(out[14])}
+
     def set_halo(self, plan, pyfunc):
         """Install the ghost-row plan (rails_amd.partition.HaloPlan) and hook pyfunc(send_ptr, recv_ptr, ncols, stream)."""
         def tramp(user, send, recv, nc, stream):

@@ -95,10 +95,15 @@ def test_spmm_matches_oracle(ctx, oracle, name):
         ref = oracle.csr_spmm(*A, Xh)
         scale = np.abs(ref).max() + 1e-300
         assert np.abs(Y.to_host() - ref).max() <= 1e-14 * np.sqrt(nnz_row) * scale * 4
-        # transposed apply (GenericOperatorWrapper_test.cpp:91-109)
+        # transposed apply (GenericOperatorWrapper_test.cpp:91-109): against the oracle's product with the transposed CSR, built here
         opT = op.transpose()
         YT = opT.apply(X)
         rowptr, col, val = A
+        order = np.argsort(col, kind="stable")
+        AT = (np.concatenate([[0], np.cumsum(np.bincount(col, minlength=m))]).astype(np.int64),
+              np.repeat(np.arange(m), np.diff(rowptr))[order].astype(np.int32), np.asarray(val)[order])
+        refT = oracle.csr_spmm(*AT, Xh)
+        assert np.abs(YT.to_host() - refT).max() <= 1e-14 * np.sqrt(nnz_row) * (np.abs(refT).max() + 1e-300) * 4
         dense = np.zeros((m, m)) if m <= 400 else None
         if dense is not None:
             for i in range(m):
