@@ -135,11 +135,13 @@ struct rails_panel {
 
 struct rails_planes_plan; // spmm_planes.hip: coefficient records of a structured-grid stencil
 struct rails_sweep_cache; // spmm_sweep.hip: device copies of the sweep kernel's schedules, one per column-chunk count
+struct rails_tile_cache;  // spmm_tiled.hip: device copy of the LDS-staged kernels' tile plan (tile_plan.h) and what they last launched
 
 struct rails_csr {
     rails_ctx *ctx = nullptr;
     rails_sweep_cache *sweep = nullptr;
     rails_planes_plan *planes = nullptr;
+    rails_tile_cache *tiled = nullptr;
     int64_t m = 0, ncols_ext = 0, nnz = 0;
     bool rect = false; // rails_csr_create_rect: n_rows x n_cols with n_cols != n_rows, all columns local (X has ncols_ext rows, Y has m)
     int64_t *rowptr = nullptr;
@@ -164,26 +166,8 @@ struct rails_csr {
     rails_halo_fn halo = nullptr;
     void *halo_user = nullptr;
     std::vector<int64_t> send_counts, recv_counts; // rows per neighbour rank (rails_csr_set_halo_counts): the RCCL form of the exchange
-    // LDS-staged footprint kernel (spmm.hip): per row-block column footprints
-    int variant = 0;
-    bool tiled_ready = false;
+    int variant = 0;  // rails_csr_set_variant: the kernel rails_spmm is to take (0: its own choice)
     int is_grid = -1; // structured-grid stencil? (-1: not looked at yet; rails_csr_is_grid, spmm.hip)
-    bool tiled_ok = false;
-    int tile_rows = 0;
-    int64_t n_tiles = 0;
-    int32_t *t_fp_ptr = nullptr; // [n_tiles+1] offsets into t_fp
-    int32_t *t_fp = nullptr;     // footprint column lists
-    uint16_t *t_lcol = nullptr;  // [nnz] footprint-relative column of every nonzero, tile-major
-    int32_t *t_rowptr = nullptr; // [n_tiles+1] offsets into t_rows
-    int32_t *t_rows = nullptr;   // [m] rows of every tile
-    int64_t *t_nzptr = nullptr;  // [n_tiles+1] offsets into t_val / t_lcol
-    int32_t *t_rp = nullptr;     // [m + n_tiles] per-tile local row offsets (rows+1 per tile)
-    double *t_val = nullptr;     // [nnz] values, tile-major
-    uint16_t *t_fpos = nullptr;  // LDS row of every footprint entry
-    int max_fp = 0, max_nz = 0, max_pos = 0;
-    double tile_reuse = 0.0;
-    bool tile_grid = false;
-    int tl_kernel = 0, tl_kc = 0, tl_nnz = 0, tl_nl = 0, tl_v2 = 0, tl_ns = 0; // the most recent LDS-staged launch (rails_csr_tile_stats)
     const char *last_kernel = "";
     // operator given by its action (rails_csr_create_callback): rails_spmm hands the panels over
     rails_apply_fn apply_cb = nullptr;
@@ -227,6 +211,13 @@ struct rails_slow_guard {
     }
 };
 
+// integer environment switch (the RAILS_SPMM_* of the SpMM sources)
+inline int spmm_env(const char *name, int def)
+{
+    const char *e = getenv(name);
+    return e ? atoi(e) : def;
+}
+
 // ---- helpers implemented in ctx.hip ----
 int rails_ws_reserve(rails_ctx *ctx, size_t bytes);
 void rails_library_gemm_release(rails_ctx *ctx);
@@ -259,7 +250,11 @@ void rails_planes_release(rails_csr *A);
 // the interior planes of a z-slab of a grid stencil (rows without ghost columns) on stream st; *done = false: not that kind of operator
 int rails_spmm_planes_interior(rails_ctx *c, rails_csr *A, const double *X, int ldx, double *Y, int ldy, int nc, bool aligned, hipStream_t st, bool *done);
 bool planes_last_interior(const rails_csr *A);
-bool rails_detect_grid(const rails_csr *A, int64_t *nx, int64_t *ny, int64_t *nz); // spmm.hip
+// spmm_tiled.hip: the LDS-staged footprint kernels over the tile plan of tile_plan.h (which also has the grid detection); *done
+// tells whether they computed the product.  x_room: columns of the padded X row from the window's first one on
+int rails_spmm_tiled(rails_ctx *c, rails_csr *A, const double *X, int ldx, const double *Xg, int ldg, double *Y, int ldy, int nc, bool vec2,
+                     int x_room, bool *done);
+void rails_tiled_release(rails_csr *A);
 // dense.hip: partial Gram into device memory (no host copy / all-reduce): C_dev (a x b col-major, ldc = a)
 int rails_gram_dev(rails_ctx *ctx, const double *X, int ldx, const double *Y, int ldy, int64_t m, int a, int b,
                    double *C_dev);

@@ -3,7 +3,7 @@
 // Replaces `A_ * W` of the reference (src/LyapunovSolver.hpp:146; Epetra_CrsMatrix::Apply behind src/Epetra_OperatorWrapper.cpp:87) for
 // the operators of BASELINE configs[1] and configs[3].  HBM-bound fp64 streaming work: no MFMA here.
 //
-// The box kernel (spmm.hip, k_spmm_tiled_reg) stages the halo box of a 4 x 4 x 4 tile per column chunk: every X row crosses the CUs'
+// The box kernel (spmm_tiled.hip, k_spmm_tiled_reg) stages the halo box of a 4 x 4 x 4 tile per column chunk: every X row crosses the CUs'
 // load path 3.4 times.  This kernel turns the sweep kernel's idea (spmm_sweep.hip: X streams once, the partial sums stay put) onto
 // the grid: a workgroup owns a PX x PY patch of grid columns and walks along z.  Per step ONE plane of X (patch + halo, whole panel
 // rows of up to 128 columns = 1 KiB) arrives in LDS by LDS-DMA, two planes ahead of its use, and contributes to the three output planes
@@ -16,6 +16,7 @@
 // z+1, inside a plane y-1, y, y+1, inside a line x-1, x, x+1), so the product is bitwise the row-gather kernel's except for the sign
 // of an exact zero (products with halo rows outside the grid are +0 terms).
 #include "rails_internal.h"
+#include "tile_plan.h"
 
 #include <algorithm>
 
@@ -268,7 +269,7 @@ static int planes_build(rails_ctx *c, rails_csr *A)
     rails_planes_plan *P = A->planes;
     if (A->rect || A->nnz == 0 || (A->n_ghost == 0 && A->m != A->ncols_ext)) return RAILS_OK;
     int64_t gx = 0, gy = 0, gz = 0;
-    if (!rails_detect_grid(A, &gx, &gy, &gz)) return RAILS_OK;
+    if (!rails_detect_grid(A->m, A->h_rowptr.data(), A->h_col.data(), &gx, &gy, &gz)) return RAILS_OK;
     if (gx * gy * gz != A->m || gx > 0x7fff || gy > 0x7fff || gz > 0x3fffffff) return RAILS_OK;
     // a row block with ghost columns: a z-slab whose interior rows (rails_csr_set_halo) are whole planes
     int64_t v_lo = 0, v_hi = A->m;

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel register / occupancy report of one HIP source (compile only: works without a GPU).
-usage: python scripts/kernel_resources.py rails_amd/csrc/spmm.hip [name filter] [extra hipcc flags...]"""
+usage: python scripts/kernel_resources.py rails_amd/csrc/spmm.hip [name filter] [extra hipcc flags...]
+(one source per call: spmm.hip has the row kernels, spmm_tiled.hip the LDS-staged ones)"""
 import os
 import re
 import subprocess

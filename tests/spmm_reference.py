@@ -1,4 +1,5 @@
-"""Host references, derived bounds and input generators for the CSR x panel product Y = A X (rails_amd/csrc/spmm.hip).  numpy only,
+"""Host references, derived bounds and input generators for the CSR x panel product Y = A X (rails_amd/csrc/spmm.hip, spmm_tiled.hip;
+the tile plan: tile_plan.cpp).  numpy only,
 no project imports: a host test and a device test can share everything in here.
 
 Two references, for two kinds of input.

@@ -610,3 +610,77 @@ def test_narrow_product_is_bitwise_the_rowgather_result(ctx, oracle, nc, xoff, y
     assert np.array_equal(Y3.to_host(), Yn)
     ref = oracle.csr_spmm(rowptr, col, val, Xh)
     assert np.abs(Yn - ref).max() <= 1e-14 * np.sqrt(60) * 4 * np.abs(ref).max()
+
+
+# ---------------------------------------------------------------------------------------------------- which row kernel runs
+# (variant, columns, X offset, Y offset) -> kernel, on a flat operator with 12 entries per row and fewer than 2^24 columns: the selection
+# rule of DESIGN.md "Which row kernel runs" (row_choice.h).  Variant 1 keeps the LDS-staged, sweep and plane kernels out of the way.
+ROW_KERNEL_CASES = (
+    [(1, nc, 0, 0, "k_spmm_rowgather") for nc in (1, 2, 8)]          # up to 8 columns: the plain kernel
+    + [(1, nc, 0, 0, "k_spmm_narrow") for nc in (9, 16, 17, 32)]     # 9..32 columns, one chunk, flat and small: the lean kernel
+    + [(1, 16, 0, 1, "k_spmm_narrow"),                               # a Y window on an odd column only changes the stores
+       (1, 16, 1, 0, "k_spmm_narrow"),                               # X rows that are only 8-byte aligned: the lean kernel up to 16 columns ...
+       (1, 17, 1, 0, "k_spmm_rowgather"),                            # ... and the plain one beyond
+       (1, 33, 0, 0, "k_spmm_rowgather"),
+       (3, 16, 0, 0, "k_spmm_rowgather"),                            # variant 3 is always the plain kernel
+       (4, 32, 0, 0, "k_spmm_narrow"),                               # variants 4 / 5 chunk only above 32 / 64 columns ...
+       (4, 48, 0, 0, "k_spmm_rowgather_cc"),
+       (4, 48, 0, 1, "k_spmm_rowgather"),                            # ... and only between 16-byte aligned windows
+       (5, 64, 0, 0, "k_spmm_rowgather"),
+       (5, 80, 0, 0, "k_spmm_rowgather_cc")]
+)
+
+
+def _row_kernel_operands(long_row):
+    """banded_random(3000, 12, 40) -- with row 1500 replaced by one of 70 entries if long_row -- integer values, an integer panel of 80
+    columns and the exact product (spmm_reference.py), computed once"""
+    import spmm_reference as R
+    from rails_amd import problems as P
+
+    key = "_cache_%d" % long_row
+    if not hasattr(_row_kernel_operands, key):
+        rowptr, col, _ = P.banded_random(3000, 12, 40, seed=1)
+        if long_row:
+            rows = [col[rowptr[i]:rowptr[i + 1]] for i in range(3000)]
+            rows[1500] = np.arange(1500 - 35, 1500 + 35, dtype=np.int32)
+            rowptr = np.zeros(3001, dtype=np.int64)
+            rowptr[1:] = np.cumsum([r.size for r in rows])
+            col = np.concatenate(rows).astype(np.int32)
+        val = R.int_values(col.size, seed=7)
+        X = R.int_panel(3000, 80)
+        ref = R.spmm_exact_int(rowptr, col, val, X)
+        for a in (X, ref):
+            a.setflags(write=False)
+        setattr(_row_kernel_operands, key, (rowptr, col, val, X, ref))
+    return getattr(_row_kernel_operands, key)
+
+
+def _row_kernel_product(ctx, variant, nc, xoff, yoff, long_row=False):
+    import rails_amd
+
+    rowptr, col, val, Xh, ref = _row_kernel_operands(long_row)
+    op = rails_amd.HipOperatorWrapper(ctx, rowptr, col, val)
+    op.set_variant(variant)
+    big = MV(ctx, m=3000, n=nc + xoff, capacity=nc + xoff)
+    X = big.view(xoff, xoff + nc - 1)
+    X.from_host(Xh[:, :nc])
+    outp = MV(ctx, m=3000, n=nc + yoff, capacity=nc + yoff)
+    Y = outp.view(yoff, yoff + nc - 1)
+    op.apply(X, Y)
+    return op.last_kernel(), Y.to_host(), ref[:, :nc]
+
+
+@pytest.mark.parametrize("variant,nc,xoff,yoff,kernel", ROW_KERNEL_CASES)
+def test_row_kernel_choice(ctx, variant, nc, xoff, yoff, kernel):
+    got, Y, ref = _row_kernel_product(ctx, variant, nc, xoff, yoff)
+    assert got == kernel, (got, kernel)
+    assert np.array_equal(Y, ref)
+
+
+def test_row_kernel_choice_long_row(ctx):
+    """one row of 70 entries (more than 64): the plain kernel at the lean kernel's width"""
+    rowptr = _row_kernel_operands(True)[0]
+    assert np.diff(rowptr).max() == 70
+    got, Y, ref = _row_kernel_product(ctx, 1, 16, 0, 0, long_row=True)
+    assert got == "k_spmm_rowgather", got
+    assert np.array_equal(Y, ref)

@@ -1,8 +1,9 @@
-"""Every form of the LDS-staged SpMM (rails_amd/csrc/spmm.hip: k_spmm_tiled, k_spmm_tiled_pipe, k_spmm_tiled_reg<KC, NNZ, NL, V2, NS>)
+"""Every form of the LDS-staged SpMM (rails_amd/csrc/spmm_tiled.hip: k_spmm_tiled, k_spmm_tiled_pipe, k_spmm_tiled_reg<KC, NNZ, NL, V2, NS>)
 against the host references of tests/spmm_reference.py.
 
 Each case runs a product through operator variant 2 (8-column chunks) or 6 (16-column chunks where they apply), asserts through
-tile_stats() WHICH kernel and instantiation ran -- derived below from the dispatcher, so a moved threshold fails here instead of
+tile_stats() WHICH kernel and instantiation ran -- derived below from the dispatcher (rails_spmm_tiled; the plan itself is host code,
+rails_amd/csrc/tile_plan.cpp, checked without a GPU by test_tile_plan_host.py), so a moved threshold fails here instead of
 silently taking the coverage away -- and checks the result
 
   exactly   integer val in [-8, 8] \\ {0} and X in [-16, 16]: every partial sum is an exact double, Y must equal the int64 product;
