@@ -219,6 +219,40 @@ int rails_lu_stats(const rails_lu *lu, int64_t *info, int cap);
  * (HipOperatorWrapper, rails_solver_create, rails_solver_set_inverse).  The caller keeps the rails_lu alive while the handle is used. */
 int rails_csr_create_lu(rails_ctx *ctx, rails_lu *lu, rails_csr **out);
 
+/* ---- sparse right-hand side (rails_amd/csrc/sprhs_host.cpp, sprhs.hip, lanczos.hip) ------------------------------------------------------
+ * B of A X M' + M X A' + B B' = 0 as a sparse m x p matrix instead of a panel: the operator form of the reference's
+ * MatrixOrMultiVectorWrapper (src/MatrixOrMultiVectorWrapper.hpp; src/main.cpp:67 reads B.mtx as a CrsMatrix and :98 hands it to the
+ * solver).  p is not limited by the fused Lanczos' 128 panel columns and B costs its nonzeros, not 8 m p bytes. */
+
+/* Host only (no device is touched).  Transpose of an n_rows x n_cols CSR matrix into t_rowptr (n_cols + 1), t_col, t_val (rowptr[n_rows]
+ * each).  Stable: the entries of a transposed row come in increasing original row and duplicates keep their order.  RAILS_EINVAL for a
+ * rowptr that does not start at 0 or decreases and for a column outside [0, n_cols); nothing is read out of range. */
+int rails_csr_transpose_host(int64_t n_rows, int64_t n_cols, const int64_t *rowptr, const int32_t *col, const double *val, int64_t *t_rowptr,
+                             int32_t *t_col, double *t_val);
+/* Host only.  *out = ||B'B||_F^2 from B (n_rows x n_cols) and its transpose, with a sparse accumulator over the columns of B: no
+ * n_cols x n_cols array.  Both forms are validated as above. */
+int rails_csr_gram_norm2_host(int64_t n_rows, int64_t n_cols, const int64_t *rowptr, const int32_t *col, const double *val,
+                              const int64_t *t_rowptr, const int32_t *t_col, const double *t_val, double *out);
+
+/* Uploads B (m_local x p, CSR, p >= 0, any number of entries per row) and its transpose.  Single GPU only: B'W of a row-partitioned B
+ * would need an all-reduce of p x w, so a context with more than one rank gets RAILS_EINVAL. */
+typedef struct rails_sprhs rails_sprhs;
+int rails_sprhs_create(rails_ctx *ctx, int64_t m_local, int p, const int64_t *rowptr, const int32_t *col, const double *val, rails_sprhs **out);
+void rails_sprhs_destroy(rails_sprhs *S);
+int64_t rails_sprhs_rows(const rails_sprhs *S);
+int64_t rails_sprhs_cols(const rails_sprhs *S);
+int64_t rails_sprhs_nnz(const rails_sprhs *S);
+double rails_sprhs_gram_norm2(const rails_sprhs *S); /* ||B'B||_F^2, computed on the host at creation */
+/* trans == 0: Y[:, yc0:yc0+nc] = B X[:, xc0:xc0+nc], X of p rows and Y of m; trans != 0: Y = B' X, X of m rows and Y of p. */
+int rails_sprhs_apply(rails_ctx *ctx, rails_sprhs *S, int trans, const rails_panel *X, int xc0, int nc, rails_panel *Y, int yc0);
+/* An operator handle whose rails_spmm is rails_sprhs_apply (both trans values), as rails_csr_create_lu makes one for an LU solve.  The
+ * caller keeps the rails_sprhs alive while the handle is used. */
+int rails_csr_create_sprhs(rails_ctx *ctx, rails_sprhs *S, rails_csr **out);
+/* rows of X in a product with A (trans == 0): the columns of a rectangular operator or of a sparse right-hand side, the rows of any other */
+int64_t rails_csr_cols(const rails_csr *A);
+/* the sparse right-hand side behind a handle made by rails_csr_create_sprhs, NULL for any other operator */
+rails_sprhs *rails_csr_sprhs(const rails_csr *A);
+
 typedef struct rails_sweep_plan rails_sweep_plan;
 int rails_sweep_plan_create(int64_t m, int64_t ncols, const int64_t *rowptr, const int32_t *col, const double *val,
                             const int *params, rails_sweep_plan **out);
@@ -322,6 +356,13 @@ int rails_orthogonalize_deflated(rails_ctx *ctx, rails_panel *V, int k_old, int 
 int rails_resid_lanczos(rails_ctx *ctx, const rails_panel *AV, int avc0, const rails_panel *MV, int mvc0, int k,
                         const double *T_host, int ldt, const rails_panel *B, int bc0, int p, int L,
                         double *H_host, int ldh, int *steps);
+
+/* The same run with B a sparse right-hand side S (m x p, any p >= 0): per step one pass over [AV MV] that takes B's part of each row
+ * from the CSR form, r = [AV MV]_row . g + sum_q B_val[q] g_B[B_col[q]] - alpha q_i - beta q_{i-1}, then c_B = B'r over the transposed
+ * form, balanced by nonzeros and summed in a fixed order (two runs from one seed give the same bits).  Everything else -- the RNG
+ * stream, H, the breakdown test, the stored vectors, rails_lanczos_last_launch, k <= 512, even window starts -- as above.  Single GPU. */
+int rails_resid_lanczos_sparse(rails_ctx *ctx, const rails_panel *AV, int avc0, const rails_panel *MV, int mvc0, int k, const double *T_host,
+                               int ldt, const rails_sprhs *S, int L, double *H_host, int ldh, int *steps);
 
 /* Start of a residual Lanczos run only: draws the random start vector q0 (one RNG stream, as Q.random() at :374), and
  * returns sums_host = [AV^T q0 (k) | MV^T q0 (k) | B^T q0 (p) | q0^T q0] (summed over the ranks) in ONE pass over the

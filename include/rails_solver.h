@@ -22,6 +22,12 @@ typedef struct rails_solver rails_solver;
  * m_local x p with leading dimension ldb.  m_global: global row count (= m_local on one GPU). */
 int rails_solver_create(rails_ctx *ctx, rails_csr *A, rails_csr *M, const double *B_host, int64_t ldb, int p,
                         int64_t m_global, rails_solver **out);
+/* The same with B a sparse right-hand side (rails_sprhs_create; the caller keeps S alive): B takes the operator form of the reference's
+ * B adaptor (src/MatrixOrMultiVectorWrapper.hpp; src/main.cpp:67,98).  Single GPU.  Such a solver always runs the direct back end -- the
+ * coordinate-space back end needs B inside its basis -- so rails_solver_backend_stats is "{}" and the options "subspace" and
+ * "projected_lanczos" are accepted and ignored.  The projection methods that start from B (1.2, 2.2) are refused (*code = -2), as for
+ * any operator B. */
+int rails_solver_create_sparse(rails_ctx *ctx, rails_csr *A, rails_csr *M, rails_sprhs *S, int64_t m_global, rails_solver **out);
 int rails_solver_destroy(rails_solver *s);
 
 /* set_parameters -- src/LyapunovSolver.hpp:72-98.  Names are the reference's ("Maximum iterations",
@@ -69,6 +75,8 @@ int rails_solver_solve(rails_solver *s, int *code, int *k);
 int rails_solver_get_V(rails_solver *s, double *V_host, int64_t ldv); /* local rows x k */
 int rails_solver_get_T(rails_solver *s, double *T_host, int ldt);     /* k x k */
 int rails_solver_trips(rails_solver *s);
+/* ||B||_2^2 as the last solve computed it, the scale of its stopping test (src/LyapunovSolver.hpp:134); 0 before the first solve */
+int rails_solver_scale(rails_solver *s, double *scale);
 int rails_solver_history(rails_solver *s, double *res, int cap);      /* Lanczos estimates per trip; returns count */
 
 /* host wall-clock seconds per solver section of the last solve (JSON object; names follow the reference's profile
@@ -81,6 +89,8 @@ const char *rails_solver_backend_stats(rails_solver *s);
  * (uses R = [AV V B] G [AV V B]'; test / reporting helper).  The norm comes out of a trace of Gram products, i.e. as the
  * square root of a difference of O(||X||^2 ||A||^2) terms: it bottoms out near 1e-8 relative.  Below that use products with R
  * itself (tests/test_gpu_fullsize.py does a power iteration on R). */
+/* With a sparse B (rails_solver_create_sparse): P = [AV MV], K = [[0 T],[T 0]], Z = B'P (a p-row panel), and
+ * ||R||_F^2 = tr((P'P K)^2) + 2 tr(K Z'Z) + ||B'B||_F^2 with the last term from rails_sprhs_gram_norm2: no m x p or p x p array. */
 int rails_solver_relative_residual(rails_solver *s, double *rel);
 
 #ifdef __cplusplus

@@ -8,6 +8,7 @@ mirror used by the tests and bench.py.  There is no CPU fallback anywhere in thi
 from ._lib import LIB_PATH, RailsError, load  # noqa: F401
 from .solution import Solution  # noqa: F401
 from .solver import Solver  # noqa: F401
+from .sparse_rhs import SparseRHS, resid_lanczos_sparse  # noqa: F401
 from .splu import SparseLU  # noqa: F401
 from .wrappers import (Context, HipMultiVectorWrapper, HipOperatorWrapper, lanczos_vectors,  # noqa: F401
                        resid_lanczos)

@@ -89,6 +89,19 @@ SIGNATURES = {
     "rails_lu_solve": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int]),
     "rails_lu_stats": (C.c_int, [_vp, _i64p, C.c_int]),
     "rails_csr_create_lu": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
+    "rails_csr_transpose_host": (C.c_int, [C.c_int64, C.c_int64, _i64p, _i32p, _dp, _i64p, _i32p, _dp]),
+    "rails_csr_gram_norm2_host": (C.c_int, [C.c_int64, C.c_int64, _i64p, _i32p, _dp, _i64p, _i32p, _dp, _dp]),
+    "rails_sprhs_create": (C.c_int, [_vp, C.c_int64, C.c_int, _i64p, _i32p, _dp, C.POINTER(_vp)]),
+    "rails_sprhs_destroy": (None, [_vp]),
+    "rails_sprhs_rows": (C.c_int64, [_vp]),
+    "rails_sprhs_cols": (C.c_int64, [_vp]),
+    "rails_sprhs_nnz": (C.c_int64, [_vp]),
+    "rails_sprhs_gram_norm2": (C.c_double, [_vp]),
+    "rails_sprhs_apply": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int]),
+    "rails_csr_create_sprhs": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
+    "rails_csr_cols": (C.c_int64, [_vp]),
+    "rails_csr_sprhs": (_vp, [_vp]),
+    "rails_resid_lanczos_sparse": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _dp, C.c_int, _vp, C.c_int, _dp, C.c_int, _ip]),
     "rails_panel_random": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),
     "rails_gram": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _dp, C.c_int]),
     "rails_panel_gemm": (C.c_int, [_vp, C.c_double, _vp, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_double, _vp, C.c_int]),

@@ -9,7 +9,9 @@ TRIP_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int)
 
 SOLVER_SIGNATURES = {
     "rails_solver_create": (C.c_int, [_vp, _vp, _vp, _dp, C.c_int64, C.c_int, C.c_int64, C.POINTER(_vp)]),
+    "rails_solver_create_sparse": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.POINTER(_vp)]),
     "rails_solver_destroy": (C.c_int, [_vp]),
+    "rails_solver_scale": (C.c_int, [_vp, _dp]),
     "rails_solver_set_parameter": (C.c_int, [_vp, C.c_char_p, C.c_double]),
     "rails_solver_apply_parameters": (C.c_int, [_vp, _ip]),
     "rails_solver_set_option": (C.c_int, [_vp, C.c_char_p, C.c_double]),

@@ -86,198 +86,83 @@ struct LzArgs {
     double *partial;      // [nblocks][2k+p+1]
 };
 
-// lane l owns column pairs (2(l+64c), 2(l+64c)+1), c < NCH, of AV and of MV, and pair l of B.
+// B as a sparse right-hand side (rails_sprhs): the CSR form of B for the pass, g_B = coef + 2k (p doubles, read-only for the pass)
+struct LzSparse {
+    const int64_t *rowptr;
+    const int32_t *col;
+    const double *val;
+    const double *gB;
+};
+struct LzNoSparse {
+};
+
+// B's part of the rows of one 64-row group, sum_q B_val[q] g_B[B_col[q]], row row0 + l in lane l.  Rows of at most RAILS_SPRHS_SHORT
+// entries are summed by their own lane, entry by entry; a longer row by the whole wave, 64 strands and wave_sum.  The loads are
+// unconditional (masked lanes read entry 0, which exists whenever a loop runs), the loop bounds wave-uniform.
+__device__ __forceinline__ double sparse_rows(const LzSparse &sp, int64_t row0, int nrows, int lane)
+{
+    const int64_t rl = row0 + (lane < nrows ? lane : 0);
+    const int64_t s0 = sp.rowptr[rl];
+    const int len = lane < nrows ? (int)(sp.rowptr[rl + 1] - s0) : 0;
+    const int lshort = len <= RAILS_SPRHS_SHORT ? len : 0;
+    double sB = 0.0;
+    for (int t = 0; __builtin_amdgcn_ballot_w64(t < lshort) != 0; t += 4) { // four entries in flight, added in their order
+        double v[4], gv[4];
+        int32_t ci[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int64_t idx = t + u < lshort ? s0 + t + u : 0;
+            v[u] = sp.val[idx];
+            ci[u] = sp.col[idx];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) gv[u] = sp.gB[ci[u]];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) sB = t + u < lshort ? __builtin_fma(v[u], gv[u], sB) : sB;
+    }
+    uint64_t longs = __builtin_amdgcn_ballot_w64(len > RAILS_SPRHS_SHORT);
+    while (longs != 0) {
+        const int l = __builtin_ctzll(longs);
+        longs &= longs - 1;
+        const int n = __builtin_amdgcn_readlane(len, l);
+        const int64_t b = ((int64_t)__builtin_amdgcn_readlane((int)(s0 >> 32), l) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)s0, l);
+        double acc = 0.0;
+        for (int e0 = 0; e0 < n; e0 += 64) {
+            const bool on = e0 + lane < n;
+            const int64_t idx = on ? b + e0 + lane : 0;
+            const double v = sp.val[idx];
+            const double gv = sp.gB[sp.col[idx]];
+            acc = on ? __builtin_fma(v, gv, acc) : acc;
+        }
+        const double tot = wave_sum(acc);
+        sB = lane == l ? tot : sB;
+    }
+    return sB;
+}
+__device__ __forceinline__ double sparse_rows(const LzNoSparse &, int64_t, int, int) { return 0.0; }
+
+// lane l owns column pairs (2(l+64c), 2(l+64c)+1), c < NCH, of AV and of MV, and pair l of B.  The body is lanczos_pass.inc, shared with
+// the sparse form below.
 template <int NCH, int U>
 __global__ __launch_bounds__(256) void k_lanczos_pass(LzArgs a)
 {
-    __shared__ double red[4][(4 * NCH + 2) * 64 + 1];
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const bool init = a.step < 0;
-    const double done = a.state[3];
-    const int ncoef = 2 * a.k + a.p + 1;
-    double *myp = a.partial + (int64_t)blockIdx.x * ncoef;
-    if (done != 0.0) {
-        for (int i = threadIdx.x; i < ncoef; i += 256) myp[i] = 0.0;
-        return;
-    }
-    const double alpha = init ? 0.0 : a.state[0];
-    const double betap = init ? 0.0 : a.state[1];
-    const double invb = init ? 1.0 : a.state[2];
-
-    v2f64 gav[NCH], gmv[NCH], gb;
-    bool ok0[NCH], ok1[NCH];
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        int col = 2 * (lane + 64 * c);
-        ok0[c] = col < a.k;
-        ok1[c] = col + 1 < a.k;
-        gav[c].x = (!init && ok0[c]) ? a.coef[col] : 0.0;
-        gav[c].y = (!init && ok1[c]) ? a.coef[col + 1] : 0.0;
-        gmv[c].x = (!init && ok0[c]) ? a.coef[a.k + col] : 0.0;
-        gmv[c].y = (!init && ok1[c]) ? a.coef[a.k + col + 1] : 0.0;
-    }
-    const bool bok0 = 2 * lane < a.p, bok1 = 2 * lane + 1 < a.p;
-    // clamped (always valid, 16-B aligned) column offsets for the unconditional loads: lanes past the last column pair
-    // re-read that pair (same cache line as their neighbour: no extra HBM traffic), never the padding beyond it
-    int cav_off[NCH], cmv_off[NCH];
-    {
-        const int klast = a.k > 1 ? ((a.k - 1) & ~1) : 0;
-        const int lim_av = klast < a.av_room - 2 ? klast : a.av_room - 2;
-        const int lim_mv = klast < a.mv_room - 2 ? klast : a.mv_room - 2;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const int col = 2 * (lane + 64 * c);
-            cav_off[c] = col < lim_av ? col : lim_av;
-            cmv_off[c] = col < lim_mv ? col : lim_mv;
-        }
-    }
-    const int plast = a.p > 1 ? ((a.p - 1) & ~1) : 0;
-    const int lim_b = plast < a.b_room - 2 ? plast : a.b_room - 2;
-    const int cb_off = 2 * lane < lim_b ? 2 * lane : lim_b;
-    gb.x = (!init && bok0) ? a.coef[2 * a.k + 2 * lane] : 0.0;
-    gb.y = (!init && bok1) ? a.coef[2 * a.k + 2 * lane + 1] : 0.0;
-    v2f64 cav[NCH], cmv[NCH], cb;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        cav[c] = (v2f64){0.0, 0.0};
-        cmv[c] = (v2f64){0.0, 0.0};
-    }
-    cb = (v2f64){0.0, 0.0};
-    double rr = 0.0;
-
-    double *q_cur = a.Qc + (int64_t)(init ? 0 : a.step) * a.mpad;
-    const double *q_prev = a.Qc + (int64_t)((init || a.step == 0) ? 0 : a.step - 1) * a.mpad;
-    double *q_next = a.Qc + (int64_t)(a.step + 1) * a.mpad;
-    const bool have_prev = (!init && a.step > 0);
-
-    const int64_t ngroups = a.mpad / 64;
-    for (int64_t grp = (int64_t)blockIdx.x * 4 + wave; grp < ngroups; grp += (int64_t)gridDim.x * 4) {
-        const int64_t row0 = grp * 64;
-        double qn = q_cur[row0 + lane] * invb; // rows >= m hold zeros
-        double qm = have_prev ? q_prev[row0 + lane] : 0.0;
-        if (!init) q_cur[row0 + lane] = qn; // store the normalised q_i
-        double rvec = 0.0;
-        const int nrows = (int)((a.m - row0) < 64 ? (a.m - row0) : 64);
-        // U rows per trip of the loop: their 2*NCH+1 row loads are all issued before the first reduction, the
-        // U wave reductions are independent chains (rows are independent of each other)
-        for (int j0 = 0; j0 < nrows; j0 += U) {
-            // all row loads are UNCONDITIONAL (clamped row / column, values masked afterwards with selects): a load
-            // under a lane-dependent branch makes hipcc wait vmcnt(0) at the join and serialises the loads
-            v2f64 xav[U][NCH], xmv[U][NCH], xb[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int jr = (j0 + u) < nrows ? (j0 + u) : (nrows - 1);
-                const int64_t row = row0 + jr;
-                const double *pav = a.AV + row * a.ldav;
-                const double *pmv = a.MV + row * a.ldmv;
-#pragma unroll
-                for (int c = 0; c < NCH; ++c) {
-                    xav[u][c] = *reinterpret_cast<const v2f64 *>(pav + cav_off[c]);
-                    xmv[u][c] = *reinterpret_cast<const v2f64 *>(pmv + cmv_off[c]);
-                }
-                xb[u] = *reinterpret_cast<const v2f64 *>(a.B + row * a.ldb + cb_off);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-#pragma unroll
-                for (int c = 0; c < NCH; ++c) {
-                    xav[u][c].x = ok0[c] ? xav[u][c].x : 0.0;
-                    xav[u][c].y = ok1[c] ? xav[u][c].y : 0.0;
-                    xmv[u][c].x = ok0[c] ? xmv[u][c].x : 0.0;
-                    xmv[u][c].y = ok1[c] ? xmv[u][c].y : 0.0;
-                }
-                xb[u].x = bok0 ? xb[u].x : 0.0;
-                xb[u].y = bok1 ? xb[u].y : 0.0;
-            }
-            double r[U];
-            if (init) {
-#pragma unroll
-                for (int u = 0; u < U; ++u) r[u] = ((j0 + u) < nrows) ? readlane_f64(qn, (j0 + u) & 63) : 0.0;
-            } else {
-                double t[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    double tt = 0.0;
-#pragma unroll
-                    for (int c = 0; c < NCH; ++c) {
-                        tt = __builtin_fma(xav[u][c].x, gav[c].x, tt);
-                        tt = __builtin_fma(xav[u][c].y, gav[c].y, tt);
-                        tt = __builtin_fma(xmv[u][c].x, gmv[c].x, tt);
-                        tt = __builtin_fma(xmv[u][c].y, gmv[c].y, tt);
-                    }
-                    tt = __builtin_fma(xb[u].x, gb.x, tt);
-                    tt = __builtin_fma(xb[u].y, gb.y, tt);
-                    t[u] = tt;
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u) t[u] = wave_sum(t[u]);
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int jj = (j0 + u) & 63;
-                    const double qi = readlane_f64(qn, jj);
-                    const double qmi = readlane_f64(qm, jj);
-                    r[u] = ((j0 + u) < nrows) ? (t[u] - alpha * qi - betap * qmi) : 0.0;
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-#pragma unroll
-                for (int c = 0; c < NCH; ++c) {
-                    cav[c].x = __builtin_fma(xav[u][c].x, r[u], cav[c].x);
-                    cav[c].y = __builtin_fma(xav[u][c].y, r[u], cav[c].y);
-                    cmv[c].x = __builtin_fma(xmv[u][c].x, r[u], cmv[c].x);
-                    cmv[c].y = __builtin_fma(xmv[u][c].y, r[u], cmv[c].y);
-                }
-                cb.x = __builtin_fma(xb[u].x, r[u], cb.x);
-                cb.y = __builtin_fma(xb[u].y, r[u], cb.y);
-                rr = __builtin_fma(r[u], r[u], rr);
-                rvec = (lane == j0 + u) ? r[u] : rvec;
-            }
-        }
-        if (!init) q_next[row0 + lane] = rvec;
-    }
-
-    // block reduction in a fixed order: wave 0 += wave 1, 2, 3
-    double *mine = red[wave];
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        mine[(4 * c + 0) * 64 + lane] = cav[c].x;
-        mine[(4 * c + 1) * 64 + lane] = cav[c].y;
-        mine[(4 * c + 2) * 64 + lane] = cmv[c].x;
-        mine[(4 * c + 3) * 64 + lane] = cmv[c].y;
-    }
-    mine[(4 * NCH + 0) * 64 + lane] = cb.x;
-    mine[(4 * NCH + 1) * 64 + lane] = cb.y;
-    if (lane == 0) mine[(4 * NCH + 2) * 64] = rr;
-    __syncthreads();
-    if (wave == 0) {
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                int slot = (4 * c + e) * 64 + lane;
-                double s = ((red[0][slot] + red[1][slot]) + red[2][slot]) + red[3][slot];
-                int col = 2 * (lane + 64 * c) + (e & 1);
-                if (col < a.k) myp[(e < 2 ? 0 : a.k) + col] = s;
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            int slot = (4 * NCH + e) * 64 + lane;
-            double s = ((red[0][slot] + red[1][slot]) + red[2][slot]) + red[3][slot];
-            int col = 2 * lane + e;
-            if (col < a.p) myp[2 * a.k + col] = s;
-        }
-        if (lane == 0) {
-            int slot = (4 * NCH + 2) * 64;
-            myp[2 * a.k + a.p] = ((red[0][slot] + red[1][slot]) + red[2][slot]) + red[3][slot];
-        }
-    }
+    constexpr bool SP = false;
+    const LzNoSparse sp{};
+#include "lanczos_pass.inc"
 }
 
-// out[e] = sum over the blocks' partials, fixed order (16 interleaved strands, then strands 0..15)
-__global__ __launch_bounds__(1024) void k_lz_reduce(const double *__restrict__ partial, int nblocks, int n, double *__restrict__ out)
+// the pass of rails_resid_lanczos_sparse: partials of 2k + 1 entries [c'_AV | c'_MV | rr]
+template <int NCH, int U>
+__global__ __launch_bounds__(256) void k_lanczos_pass_sparse(LzArgs a, LzSparse sp)
+{
+    constexpr bool SP = true;
+#include "lanczos_pass.inc"
+}
+
+// out[e] = sum over the blocks' partials, fixed order (16 interleaved strands, then strands 0..15); LAST_AT: the last entry (rr) goes to
+// out[last_at] instead, behind the p entries of c'_B that the partials of the sparse form do not hold
+template <bool LAST_AT>
+__device__ __forceinline__ void lz_reduce_body(const double *__restrict__ partial, int nblocks, int n, double *__restrict__ out, int last_at)
 {
     __shared__ double sh[16][64];
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
@@ -291,8 +176,82 @@ __global__ __launch_bounds__(1024) void k_lz_reduce(const double *__restrict__ p
         double r = 0.0;
 #pragma unroll
         for (int g = 0; g < 16; ++g) r += sh[g][tx];
-        out[e] = r;
+        out[(LAST_AT && e == n - 1) ? last_at : e] = r;
     }
+}
+
+__global__ __launch_bounds__(1024) void k_lz_reduce(const double *__restrict__ partial, int nblocks, int n, double *__restrict__ out)
+{
+    lz_reduce_body<false>(partial, nblocks, n, out, 0);
+}
+
+__global__ __launch_bounds__(1024) void k_lz_reduce_last_at(const double *__restrict__ partial, int nblocks, int n, double *__restrict__ out,
+                                                            int last_at)
+{
+    lz_reduce_body<true>(partial, nblocks, n, out, last_at);
+}
+
+// c'_B = B'r over the transposed CSR form, balanced by nonzeros, no atomics (rails_internal.h: rails_sprhs).  Blocks [0, nshort): one
+// thread per transposed row of at most RAILS_SPRHS_SHORT entries, summed in order into out[row]; the blocks behind them: one wave per item
+// of a long row, 64 strands and wave_sum into item_partial.  k_sprhs_bt_long then adds a long row's items, again 64 strands and wave_sum.
+struct LzBt {
+    const int64_t *t_rowptr;
+    const int32_t *t_col;
+    const double *t_val;
+    int p, nshort;
+    const int64_t *item_beg;
+    const int32_t *item_len;
+    int64_t n_items;
+    const int32_t *long_row;
+    const int64_t *long_item0;
+    int64_t n_long;
+    double *item_partial;
+    const double *r;     // the vector of this pass (m entries at least)
+    double *out;         // sums + 2k
+    const double *state; // [3]: the run has stopped
+};
+
+__global__ __launch_bounds__(256) void k_sprhs_bt(LzBt b)
+{
+    if (b.state[3] != 0.0) return;
+    if ((int)blockIdx.x < b.nshort) {
+        const int j = blockIdx.x * 256 + threadIdx.x;
+        if (j >= b.p) return;
+        const int64_t q0 = b.t_rowptr[j], q1 = b.t_rowptr[j + 1];
+        if (q1 - q0 > RAILS_SPRHS_SHORT) return;
+        double s = 0.0;
+        for (int64_t q = q0; q < q1; ++q) s = __builtin_fma(b.t_val[q], b.r[b.t_col[q]], s);
+        b.out[j] = s;
+        return;
+    }
+    const int lane = threadIdx.x & 63;
+    const int64_t item = ((int64_t)blockIdx.x - b.nshort) * 4 + (threadIdx.x >> 6);
+    if (item >= b.n_items) return; // wave-uniform
+    const int64_t beg = b.item_beg[item];
+    const int n = b.item_len[item];
+    double acc = 0.0;
+    for (int e0 = 0; e0 < n; e0 += 64) {
+        const bool on = e0 + lane < n;
+        const int64_t q = on ? beg + e0 + lane : beg;
+        const double v = b.t_val[q];
+        const double x = b.r[b.t_col[q]];
+        acc = on ? __builtin_fma(v, x, acc) : acc;
+    }
+    const double tot = wave_sum(acc);
+    if (lane == 0) b.item_partial[item] = tot;
+}
+
+__global__ __launch_bounds__(256) void k_sprhs_bt_long(LzBt b)
+{
+    if (b.state[3] != 0.0) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t l = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (l >= b.n_long) return; // wave-uniform
+    const int64_t i0 = b.long_item0[l], i1 = b.long_item0[l + 1];
+    double acc = 0.0;
+    for (int64_t i = i0 + lane; i < i1; i += 64) acc += b.item_partial[i];
+    const double tot = wave_sum(acc);
+    if (lane == 0) b.out[b.long_row[l]] = tot;
 }
 
 // One block.  sums = [c'_AV (k) | c'_MV (k) | c'_B (p) | rr] (already all-reduced).
@@ -421,17 +380,23 @@ __global__ void k_lz_random(double *__restrict__ q, int64_t m, int64_t mpad, uin
     }
 }
 
+// sp != nullptr: the pass of the sparse form
 template <int NCH, int U>
-void launch_pass_u(rails_ctx *c, const LzArgs &a, int *nblocks_io, bool size_only)
+void launch_pass_u(rails_ctx *c, const LzArgs &a, const LzSparse *sp, int *nblocks_io, bool size_only)
 {
     if (size_only) { // grid = resident blocks only (every block walks the row groups with a grid stride)
         int occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_lanczos_pass<NCH, U>, 256, 0) != hipSuccess || occ < 1) occ = 2;
+        const hipError_t e = sp ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_lanczos_pass_sparse<NCH, U>, 256, 0)
+                                : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_lanczos_pass<NCH, U>, 256, 0);
+        if (e != hipSuccess || occ < 1) occ = 2;
         if (occ > 4) occ = 4;
         *nblocks_io = c->num_cu * occ;
         return;
     }
-    RAILS_LAUNCH((k_lanczos_pass<NCH, U>), dim3(*nblocks_io), dim3(256), 0, c->stream, a);
+    if (sp)
+        RAILS_LAUNCH((k_lanczos_pass_sparse<NCH, U>), dim3(*nblocks_io), dim3(256), 0, c->stream, a, *sp);
+    else
+        RAILS_LAUNCH((k_lanczos_pass<NCH, U>), dim3(*nblocks_io), dim3(256), 0, c->stream, a);
 }
 
 int lz_unroll()
@@ -451,11 +416,11 @@ int pass_unroll(int nch)
     return (nch >= 3 && u > 2) ? 2 : u;
 }
 
-void launch_pass(rails_ctx *c, const LzArgs &a, int nch, int *nblocks_io, bool size_only)
+void launch_pass(rails_ctx *c, const LzArgs &a, const LzSparse *sp, int nch, int *nblocks_io, bool size_only)
 {
     const int u = pass_unroll(nch);
 #define RAILS_LZ_CASE(N, UU) \
-    if (nch == N && u == UU) return launch_pass_u<N, UU>(c, a, nblocks_io, size_only);
+    if (nch == N && u == UU) return launch_pass_u<N, UU>(c, a, sp, nblocks_io, size_only);
     RAILS_LZ_CASE(1, 1) RAILS_LZ_CASE(1, 2) RAILS_LZ_CASE(1, 4) RAILS_LZ_CASE(2, 1) RAILS_LZ_CASE(2, 2) RAILS_LZ_CASE(2, 4)
     RAILS_LZ_CASE(3, 1) RAILS_LZ_CASE(3, 2) RAILS_LZ_CASE(4, 1) RAILS_LZ_CASE(4, 2)
 #undef RAILS_LZ_CASE
@@ -464,16 +429,18 @@ void launch_pass(rails_ctx *c, const LzArgs &a, int nch, int *nblocks_io, bool s
 } // namespace
 
 static int lz_run(rails_ctx *c, const rails_panel *AV, int avc0, const rails_panel *MV, int mvc0, int k, const double *T_host, int ldt,
-                  const rails_panel *B, int bc0, int p, int L, double *H_host, int ldh, int *steps_out, double *start_sums_host)
+                  const rails_panel *B, int bc0, int p, int L, double *H_host, int ldh, int *steps_out, double *start_sums_host,
+                  const rails_sprhs *SR = nullptr)
 {
+    // SR: B is a sparse right-hand side (rails_resid_lanczos_sparse; B == nullptr, bc0 == 0, p == SR->p)
     const bool only_start = (start_sums_host != nullptr);
-    RAILS_REQUIRE(c && AV && MV && B && (only_start || (H_host && steps_out)), "rails_resid_lanczos: null argument");
+    RAILS_REQUIRE(c && AV && MV && (B || SR) && (only_start || (H_host && steps_out)), "rails_resid_lanczos: null argument");
     RAILS_REQUIRE(k >= 0 && p >= 0 && L >= 1 && (only_start || ldh >= L + 1), "rails_resid_lanczos: bad sizes k=%d p=%d L=%d ldh=%d", k, p, L, ldh);
-    RAILS_REQUIRE(avc0 >= 0 && avc0 + k <= AV->cap && mvc0 >= 0 && mvc0 + k <= MV->cap && bc0 >= 0 && bc0 + p <= B->cap,
+    RAILS_REQUIRE(avc0 >= 0 && avc0 + k <= AV->cap && mvc0 >= 0 && mvc0 + k <= MV->cap && bc0 >= 0 && (SR || bc0 + p <= B->cap),
                   "rails_resid_lanczos: column windows outside capacity");
-    RAILS_REQUIRE(AV->m == MV->m && AV->m == B->m, "rails_resid_lanczos: row mismatch");
+    RAILS_REQUIRE(AV->m == MV->m && AV->m == (SR ? SR->m : B->m), "rails_resid_lanczos: row mismatch");
     RAILS_REQUIRE(((avc0 | mvc0 | bc0) & 1) == 0, "rails_resid_lanczos: column windows must start at even columns");
-    RAILS_REQUIRE(k <= 512 && p <= 128, "rails_resid_lanczos: fused kernel supports k <= 512, p <= 128 (got %d, %d)", k, p);
+    RAILS_REQUIRE(k <= 512 && (SR || p <= 128), "rails_resid_lanczos: fused kernel supports k <= 512, p <= 128 (got %d, %d)", k, p);
     RAILS_REQUIRE(k == 0 || only_start || (T_host && ldt >= k), "rails_resid_lanczos: bad T");
     const int64_t m = AV->m;
     const int64_t mpad = (m + 63) / 64 * 64;
@@ -497,12 +464,14 @@ static int lz_run(rails_ctx *c, const rails_panel *AV, int avc0, const rails_pan
     S.L = L;
     S.steps = 0;
     const int ncoef = 2 * k + p + 1;
+    const int npart = SR ? 2 * k + 1 : ncoef; // entries of a block's partial sums: c'_B of a sparse B is not made by the pass
     int64_t ngroups = S.mpad / 64;
     const int nch = std::min(4, std::max(1, (k + 127) / 128));
     int nblocks = 0;
     {
         LzArgs dummy;
-        launch_pass(c, dummy, nch, &nblocks, true);
+        LzSparse sdummy;
+        launch_pass(c, dummy, SR ? &sdummy : nullptr, nch, &nblocks, true);
     }
     nblocks = (int)std::min<int64_t>((ngroups + 3) / 4, (int64_t)nblocks);
     if (nblocks < 1) nblocks = 1;
@@ -524,7 +493,7 @@ static int lz_run(rails_ctx *c, const rails_panel *AV, int avc0, const rails_pan
     double *dstate = dsums + ncoef;
     double *dalpha = dstate + 8;
     double *dbeta = dalpha + (L + 2);
-    RAILS_TRY(rails_ws_reserve(c, (size_t)nblocks * ncoef * sizeof(double)));
+    RAILS_TRY(rails_ws_reserve(c, (size_t)nblocks * npart * sizeof(double)));
     RAILS_TRY(rails_pinned_begin_write(c, std::max<size_t>((size_t)k * k, (size_t)(2 * (L + 2) + 8)) * sizeof(double)));
     // T -> device (contiguous k x k)
     if (!only_start) {
@@ -543,23 +512,52 @@ static int lz_run(rails_ctx *c, const rails_panel *AV, int avc0, const rails_pan
     a.ldav = AV->ld;
     a.MV = MV->d + mvc0;
     a.ldmv = MV->ld;
-    a.B = B->d + bc0;
-    a.ldb = B->ld;
+    a.B = SR ? nullptr : B->d + bc0;
+    a.ldb = SR ? 0 : B->ld;
     a.k = k;
-    a.p = p;
+    a.p = SR ? 0 : p;
     a.av_room = AV->ld - avc0;
     a.mv_room = MV->ld - mvc0;
-    a.b_room = B->ld - bc0;
+    a.b_room = SR ? 0 : B->ld - bc0;
     a.m = m;
     a.mpad = S.mpad;
     a.Qc = S.Qc;
     a.coef = dcoef;
     a.state = dstate;
     a.partial = c->ws;
+    LzSparse sp;
+    LzBt bt;
+    if (SR) {
+        sp.rowptr = SR->B->rowptr;
+        sp.col = SR->B->col;
+        sp.val = SR->B->val;
+        sp.gB = dcoef + 2 * k;
+        bt.t_rowptr = SR->Bt->rowptr;
+        bt.t_col = SR->Bt->col;
+        bt.t_val = SR->Bt->val;
+        bt.p = p;
+        bt.nshort = (p + 255) / 256;
+        bt.item_beg = SR->item_beg;
+        bt.item_len = SR->item_len;
+        bt.n_items = SR->n_items;
+        bt.long_row = SR->long_row;
+        bt.long_item0 = SR->long_item0;
+        bt.n_long = SR->n_long;
+        bt.item_partial = SR->item_partial;
+        bt.out = dsums + 2 * k;
+        bt.state = dstate;
+    }
     for (int step = -1; step < (only_start ? 0 : L); ++step) {
         a.step = step;
-        launch_pass(c, a, nch, &nblocks, false);
-        RAILS_LAUNCH(k_lz_reduce, dim3((ncoef + 63) / 64), dim3(1024), 0, c->stream, c->ws, nblocks, ncoef, dsums);
+        launch_pass(c, a, SR ? &sp : nullptr, nch, &nblocks, false);
+        if (SR) { // [c'_AV | c'_MV] and rr from the partials, c'_B = B'r from the vector the pass has just written (the raw q_0 at the start)
+            RAILS_LAUNCH(k_lz_reduce_last_at, dim3((npart + 63) / 64), dim3(1024), 0, c->stream, c->ws, nblocks, npart, dsums, ncoef - 1);
+            bt.r = S.Qc + (size_t)(step + 1) * S.mpad;
+            const int64_t grid = bt.nshort + (bt.n_items + 3) / 4;
+            if (grid > 0) RAILS_LAUNCH(k_sprhs_bt, dim3((unsigned)grid), dim3(256), 0, c->stream, bt);
+            if (bt.n_long > 0) RAILS_LAUNCH(k_sprhs_bt_long, dim3((unsigned)((bt.n_long + 3) / 4)), dim3(256), 0, c->stream, bt);
+        } else
+            RAILS_LAUNCH(k_lz_reduce, dim3((ncoef + 63) / 64), dim3(1024), 0, c->stream, c->ws, nblocks, ncoef, dsums);
         RAILS_TRY(rails_allreduce_dev(c, dsums, (size_t)ncoef));
         if (only_start) break;
         RAILS_LAUNCH(k_lz_small, dim3(1), dim3(1024), 0, c->stream, dsums, dT, k, p, step, dcoef, dstate, dalpha, dbeta);
@@ -603,6 +601,15 @@ extern "C" int rails_resid_lanczos(rails_ctx *c, const rails_panel *AV, int avc0
 {
     if (c) hipSetDevice(c->device); // allocations and launches go to the context's device whatever the caller's current device is
     return lz_run(c, AV, avc0, MV, mvc0, k, T_host, ldt, B, bc0, p, L, H_host, ldh, steps_out, nullptr);
+}
+
+extern "C" int rails_resid_lanczos_sparse(rails_ctx *c, const rails_panel *AV, int avc0, const rails_panel *MV, int mvc0, int k,
+                                          const double *T_host, int ldt, const rails_sprhs *SR, int L, double *H_host, int ldh, int *steps_out)
+{
+    if (c) hipSetDevice(c->device); // allocations and launches go to the context's device whatever the caller's current device is
+    RAILS_REQUIRE(c && SR, "rails_resid_lanczos_sparse: null argument");
+    RAILS_REQUIRE(c == SR->ctx && c->nranks == 1 && !c->rccl, "rails_resid_lanczos_sparse: single GPU only, on the context the right-hand side was made on");
+    return lz_run(c, AV, avc0, MV, mvc0, k, T_host, ldt, nullptr, 0, SR->p, L, H_host, ldh, steps_out, nullptr, SR);
 }
 
 extern "C" int rails_lanczos_start(rails_ctx *c, const rails_panel *AV, int avc0, const rails_panel *MV, int mvc0, int k,

@@ -174,6 +174,31 @@ struct rails_csr {
     void *apply_user = nullptr;
     // operator that solves with a sparse LU (rails_csr_create_lu, splu.hip): rails_spmm is rails_lu_solve; the caller owns the object
     rails_lu *lu = nullptr;
+    // operator that applies a sparse right-hand side (rails_csr_create_sprhs, sprhs.hip): rails_spmm is rails_sprhs_apply; the caller owns the object
+    rails_sprhs *sprhs = nullptr;
+};
+
+// Sparse right-hand side B (m x p) and its transpose, both as rectangular CSR operators on the device (sprhs.hip), and the host-made plan
+// of the transposed product c = B'r of the fused Lanczos (lanczos.hip): transposed rows of at most RAILS_SPRHS_SHORT entries are summed by
+// one thread each, longer ones are cut into items of RAILS_SPRHS_CHUNK entries, one wave per item, and their partial sums added per row
+// in item order.
+constexpr int RAILS_SPRHS_SHORT = 32;
+constexpr int RAILS_SPRHS_CHUNK = 512;
+struct rails_sprhs {
+    rails_ctx *ctx = nullptr;
+    int64_t m = 0, nnz = 0;
+    int p = 0;
+    rails_csr *B = nullptr;  // m x max(p, 1)
+    rails_csr *Bt = nullptr; // max(p, 1) x m, from rails_csr_transpose_host
+    double gram_norm2 = 0.0; // ||B'B||_F^2 (rails_csr_gram_norm2_host)
+    // items of the long transposed rows: entries [item_beg[i], item_beg[i] + item_len[i]) of Bt; long row l is long_row[l], its items
+    // [long_item0[l], long_item0[l + 1])
+    int64_t n_items = 0, n_long = 0;
+    int64_t *item_beg = nullptr;
+    int32_t *item_len = nullptr;
+    int32_t *long_row = nullptr;
+    int64_t *long_item0 = nullptr;
+    double *item_partial = nullptr; // n_items doubles
 };
 
 // Diagnostics: with RAILS_TRACE_SLOW_MS=x every guarded entry point synchronises before and after its work and reports on stderr

@@ -41,6 +41,8 @@ struct rails_solver {
     rails_ctx *ctx = nullptr;
     rails::HipOperatorWrapper A, M;
     rails::HipMultiVectorWrapper B;
+    rails::HipOperatorWrapper Bop; // rails_solver_create_sparse: B as an operator over the caller's rails_sprhs
+    rails_sprhs *sprhs = nullptr;
     rails::HipSolver *solver = nullptr;
     ParameterList params;
     rails::HipMultiVectorWrapper V;
@@ -105,6 +107,47 @@ try {
     return RAILS_EINVAL;
 }
 
+extern "C" int rails_solver_create_sparse(rails_ctx *ctx, rails_csr *A, rails_csr *M, rails_sprhs *S, int64_t m_global, rails_solver **out)
+try {
+    if (!ctx || !A || !S || !out) {
+        rails_set_error("rails_solver_create_sparse: null argument");
+        return RAILS_EINVAL;
+    }
+    const int64_t m = rails_csr_rows(A);
+    if (rails_sprhs_rows(S) != m || (M && rails_csr_rows(M) != m)) {
+        rails_set_error("rails_solver_create_sparse: A has %lld rows, B %lld, M %lld", (long long)m, (long long)rails_sprhs_rows(S),
+                        (long long)(M ? rails_csr_rows(M) : m));
+        return RAILS_EINVAL;
+    }
+    if (m_global > 0 && m_global != m) {
+        rails_set_error("rails_solver_create_sparse: single GPU only (%lld global rows, %lld local)", (long long)m_global, (long long)m);
+        return RAILS_EINVAL;
+    }
+    rails_solver *s = new rails_solver();
+    s->ctx = ctx;
+    s->m_local = s->m_global = m;
+    s->A = rails::HipOperatorWrapper(ctx, A, m);
+    s->has_M = (M != nullptr);
+    s->M = M ? rails::HipOperatorWrapper(ctx, M, m) : s->A;
+    s->sprhs = S;
+    s->Bop = rails::HipOperatorWrapper(ctx, S);
+    if (!s->Bop.csr()) {
+        delete s;
+        return RAILS_EINVAL; // rails_csr_create_sprhs has set the message
+    }
+    s->solver = new rails::HipSolver(s->A, s->Bop, s->M);
+    s->V = rails::HipMultiVectorWrapper(m, 1, ctx);
+    s->subspace = false;
+    *out = s;
+    return RAILS_OK;
+} catch (std::bad_alloc const &) {
+    rails_set_error("rails_solver_create_sparse: out of host memory");
+    return RAILS_ENOMEM;
+} catch (std::exception const &e) {
+    rails_set_error("rails_solver_create_sparse: %s", e.what());
+    return RAILS_EINVAL;
+}
+
 extern "C" int rails_solver_destroy(rails_solver *s)
 {
     if (!s) return RAILS_OK;
@@ -156,7 +199,7 @@ extern "C" int rails_solver_set_option(rails_solver *s, const char *name, double
         s->projected = value != 0;
         s->solver->set_projected_lanczos(s->projected);
     } else if (n == "subspace")
-        s->subspace = value != 0;
+        s->subspace = value != 0 && !s->sprhs; // a sparse B always runs the direct back end (the option is accepted and ignored)
     else {
         rails_set_error("rails_solver_set_option: unknown option '%s'", name);
         return RAILS_EINVAL;
@@ -285,7 +328,7 @@ extern "C" int rails_solver_solve(rails_solver *s, int *code, int *k)
     const bool restart_from_solution = s->params.get("Restart from solution", 0.0) != 0.0;
     // a warm start needs the caller's V; "Restart from solution" without one is the direct back end's business (it starts from
     // the single column the solver object holds, like the reference)
-    s->last_was_subspace = s->subspace && (s->have_V0 || !restart_from_solution);
+    s->last_was_subspace = s->subspace && !s->sprhs && (s->have_V0 || !restart_from_solution);
     { // the projection method: a valid value (rails_solver_apply_parameters reports it) with the inverse it needs
         rails::HipSolver::Projection proj;
         const double method = s->params.get("Projection method", 1.0);
@@ -347,6 +390,13 @@ extern "C" int rails_solver_get_T(rails_solver *s, double *T_host, int ldt)
 
 extern "C" int rails_solver_trips(rails_solver *s) { return s ? (s->last_was_subspace ? s->sub_trips : s->solver->trips()) : -1; }
 
+extern "C" int rails_solver_scale(rails_solver *s, double *scale)
+{
+    if (!s || !scale) return RAILS_EINVAL;
+    *scale = s->last_was_subspace ? 0.0 : s->solver->scale();
+    return RAILS_OK;
+}
+
 extern "C" const char *rails_solver_backend_stats(rails_solver *s) { return (s && s->last_was_subspace) ? s->sub_stats.c_str() : "{}"; }
 
 extern "C" int rails_solver_history(rails_solver *s, double *res, int cap)
@@ -375,17 +425,58 @@ extern "C" int rails_solver_profile(rails_solver *s, char *buf, int cap)
     return RAILS_OK;
 }
 
+// The same with a sparse B: P = [AV MV], K = [[0 T],[T 0]], Z = B'P;  ||R||_F^2 = tr((P'P K)^2) + 2 tr(K Z'Z) + ||B'B||_F^2
+static int sparse_relative_residual(rails_solver *s, rails::HipMultiVectorWrapper const &AV, rails::HipMultiVectorWrapper const &MV, double *rel)
+{
+    const int k = AV.N(), n = 2 * k;
+    const rails::HipOperatorWrapper Bt = s->Bop.transpose();
+    rails::HipMultiVectorWrapper ZA = Bt * AV, ZM = Bt * MV; // p x k each
+    std::vector<double> S((size_t)n * n, 0.0), W((size_t)n * n, 0.0);
+    rails::HipMultiVectorWrapper const *blk[2] = {&AV, &MV}, *zbl[2] = {&ZA, &ZM};
+    for (int a = 0; a < 2; ++a)
+        for (int b = a; b < 2; ++b) {
+            rails::HostDenseMatrix C = blk[a]->dot(*blk[b]), D = zbl[a]->dot(*zbl[b]);
+            for (int j = 0; j < k; ++j)
+                for (int i = 0; i < k; ++i) {
+                    S[(a * k + i) + (size_t)(b * k + j) * n] = S[(b * k + j) + (size_t)(a * k + i) * n] = C(i, j);
+                    W[(a * k + i) + (size_t)(b * k + j) * n] = W[(b * k + j) + (size_t)(a * k + i) * n] = D(i, j);
+                }
+        }
+    // SK = S K: column block 0 of S K is S[:, MV] T, column block 1 is S[:, AV] T
+    std::vector<double> SK((size_t)n * n, 0.0);
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < k; ++j) {
+            double s1 = 0.0, s2 = 0.0;
+            for (int l = 0; l < k; ++l) {
+                s1 += S[i + (size_t)(k + l) * n] * s->T(l, j);
+                s2 += S[i + (size_t)l * n] * s->T(l, j);
+            }
+            SK[i + (size_t)j * n] = s1;
+            SK[i + (size_t)(k + j) * n] = s2;
+        }
+    double tr = 0.0; // tr(SK SK)
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) tr += SK[i + (size_t)j * n] * SK[j + (size_t)i * n];
+    double cross = 0.0; // tr(K W) = 2 sum_ij T_ij W[MV_j, AV_i]
+    for (int j = 0; j < k; ++j)
+        for (int i = 0; i < k; ++i) cross += s->T(i, j) * (W[(k + j) + (size_t)i * n] + W[j + (size_t)(k + i) * n]);
+    const double bb = rails_sprhs_gram_norm2(s->sprhs);
+    *rel = std::sqrt(std::fabs(tr + 2.0 * cross + bb)) / std::sqrt(bb);
+    return RAILS_OK;
+}
+
 // ||R||_F with R = P G P^T, P = [AV MV B], G = [[0 T 0],[T 0 0],[0 0 I]]:  ||R||_F^2 = tr(G S G S), S = P^T P
 extern "C" int rails_solver_relative_residual(rails_solver *s, double *rel)
 {
     if (!s || !rel) return RAILS_EINVAL;
-    int k = s->V.N(), p = s->B.N();
+    int k = s->V.N(), p = s->sprhs ? 0 : s->B.N();
     if (k != s->T.M()) {
         rails_set_error("rails_solver_relative_residual: V has %d columns but T is %d x %d", k, s->T.M(), s->T.N());
         return RAILS_EINVAL;
     }
     rails::HipMultiVectorWrapper AV = s->A * s->V;
     rails::HipMultiVectorWrapper MV = s->mass ? (s->M * s->V) : s->V.view();
+    if (s->sprhs) return sparse_relative_residual(s, AV, MV, rel);
     int n = 2 * k + p;
     std::vector<double> S((size_t)n * n, 0.0);
     rails::HipMultiVectorWrapper const *blk[3] = {&AV, &MV, &s->B};

@@ -605,6 +605,7 @@ extern "C" int rails_csr_set_halo(rails_csr *A, int64_t n_send, const int64_t *s
 {
     RAILS_REQUIRE(A, "null operator");
     RAILS_REQUIRE(!A->lu, "rails_csr_set_halo: an LU solve operator is single GPU only");
+    RAILS_REQUIRE(!A->sprhs, "rails_csr_set_halo: a sparse right-hand side is single GPU only");
     RAILS_REQUIRE(n_send >= 0 && n_ghost >= 0 && A->m + n_ghost == A->ncols_ext,
                   "rails_csr_set_halo: m_local %lld + ghosts %lld != extended columns %lld", (long long)A->m, (long long)n_ghost,
                   (long long)A->ncols_ext);
@@ -679,7 +680,7 @@ extern "C" int rails_csr_prepare(rails_ctx *c, rails_csr *A, int trans, int nc, 
 {
     RAILS_REQUIRE(c && A && nc >= 1, "rails_csr_prepare: bad argument");
     if (kernel_ready) *kernel_ready = 0;
-    if (A->apply_cb || A->lu) return RAILS_OK;
+    if (A->apply_cb || A->lu || A->sprhs) return RAILS_OK;
     if (trans) {
         RAILS_TRY(build_transpose(A));
         A->AT->variant = A->variant;
@@ -702,6 +703,7 @@ extern "C" int rails_spmm(rails_ctx *c, rails_csr *A, int trans, const rails_pan
     if (c) hipSetDevice(c->device); // allocations and launches go to the context's device whatever the caller's current device is
     rails_slow_guard slow__(c, "rails_spmm", nc, A ? A->m : 0);
     RAILS_REQUIRE(c && A && X && Y, "rails_spmm: null argument");
+    if (A->sprhs) return rails_sprhs_apply(c, A->sprhs, trans, X, xc0, nc, Y, yc0); // m x p: it checks the shapes of either direction itself
     RAILS_REQUIRE(xc0 >= 0 && nc >= 0 && xc0 + nc <= X->cap, "rails_spmm: X columns [%d,%d) outside capacity %d", xc0, xc0 + nc, X->cap);
     RAILS_REQUIRE(yc0 >= 0 && yc0 + nc <= Y->cap, "rails_spmm: Y columns [%d,%d) outside capacity %d", yc0, yc0 + nc, Y->cap);
     RAILS_REQUIRE(X->m == (A->rect ? A->ncols_ext : A->m) && Y->m == A->m, "rails_spmm: operator is %lld x %lld, X has %lld rows, Y %lld", (long long)A->m,

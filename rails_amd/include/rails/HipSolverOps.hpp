@@ -175,6 +175,26 @@ struct SolverOps<HipOperatorWrapper, HipMultiVectorWrapper, HostDenseMatrix> {
         return 0;
     }
 
+    // the same with B a sparse right-hand side (rails_sprhs): any number of columns
+    static int lanczos_fused_sparse(rails_sprhs *S, HipMultiVectorWrapper const &AV, HipMultiVectorWrapper const &MV, HostDenseMatrix const &T,
+                                    int max_iter, Lanczos &out)
+    {
+        HostDenseMatrix H(max_iter + 1, max_iter + 1);
+        HostDenseMatrix Tc = T.copy();
+        int steps = 0;
+        if (!hip_ok(rails_resid_lanczos_sparse(out.ctx, AV.panel(), AV.offset(), MV.panel(), MV.offset(), AV.N(), (double *)Tc, Tc.LDA(), S, max_iter,
+                                               (double *)H, H.LDA(), &steps),
+                    "rails_resid_lanczos_sparse"))
+            return -1;
+        H.resize(steps, steps);
+        out.v = HostDenseMatrix(steps, steps);
+        out.eigenvalues = HostDenseMatrix(max_iter, 1);
+        H.eigs(out.v, out.eigenvalues);
+        out.steps = steps;
+        out.mode = 1;
+        return 0;
+    }
+
     // returns 0 on success, 1 when the projected form is not applicable this trip (caller falls back)
     static int lanczos_projected(SolverT &solver, State &st, HipMultiVectorWrapper const &AV, HipMultiVectorWrapper const &V,
                                  HostDenseMatrix const &T, HostDenseMatrix const &VAVm, HipMultiVectorWrapper const &BV, int L, Lanczos &out)
@@ -399,6 +419,10 @@ struct SolverOps<HipOperatorWrapper, HipMultiVectorWrapper, HostDenseMatrix> {
         out.ctx = AV.context();
         bool can_fuse = !solver.B().given_as_operator() && AV.N() <= 512 && solver.B().panel().N() <= 128 && ((AV.offset() | MV.offset()) & 1) == 0 &&
                         (solver.B().panel().offset() & 1) == 0;
+        if (solver.B().given_as_operator() && solver.B().op().sprhs() && AV.N() <= 512 && ((AV.offset() | MV.offset()) & 1) == 0) {
+            st.fused_trips++;
+            return lanczos_fused_sparse(solver.B().op().sprhs(), AV, MV, T, max_iter, out);
+        }
         if (!can_fuse) {
             HostDenseMatrix H(max_iter + 1, max_iter + 1);
             out.eigenvalues = HostDenseMatrix(max_iter, 1);

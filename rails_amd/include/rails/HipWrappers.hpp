@@ -507,6 +507,7 @@ class HipOperatorWrapper
     std::shared_ptr<CsrHandle> h_;
     bool transpose_;
     int64_t m_global_;
+    int64_t n_cols_ = -1; // columns of a rectangular operator (a sparse right-hand side, m x p); -1: square, m_global_ of them
 
 public:
     HipOperatorWrapper() : ctx_(default_context()), transpose_(false), m_global_(-1) {}
@@ -525,6 +526,18 @@ public:
         : ctx_(ctx ? ctx : default_context()), transpose_(false), m_global_(m_global < 0 && A ? rails_csr_rows(A) : m_global)
     {
         if (A) h_ = std::make_shared<CsrHandle>(ctx_, A, false);
+        if (A && rails_csr_sprhs(A)) n_cols_ = rails_csr_cols(A);
+    }
+
+    // The right-hand side B as an operator, m x p (rails_sprhs: the sparse form the reference's driver uses, src/main.cpp:67,98, through
+    // src/MatrixOrMultiVectorWrapper.hpp).  The wrapper owns the operator handle it makes; the caller keeps S alive.  Single GPU.
+    HipOperatorWrapper(rails_ctx *ctx, rails_sprhs *S) : ctx_(ctx ? ctx : default_context()), transpose_(false), m_global_(S ? rails_sprhs_rows(S) : -1)
+    {
+        rails_csr *A = nullptr;
+        if (S && hip_ok(rails_csr_create_sprhs(ctx_, S, &A), "rails_csr_create_sprhs")) {
+            h_ = std::make_shared<CsrHandle>(ctx_, A);
+            n_cols_ = rails_sprhs_cols(S);
+        }
     }
 
     // An operator given by its action: apply(transposed, X, Y) must write op(A) * X into Y (both are views of device panels, work
@@ -548,7 +561,9 @@ public:
     rails_ctx *context() const { return ctx_; }
 
     int M() const { return (int)m_global_; }
-    int N() const { return (int)m_global_; }
+    int N() const { return (int)(n_cols_ < 0 ? m_global_ : n_cols_); }
+    // the sparse right-hand side behind the handle (null for any other operator)
+    rails_sprhs *sprhs() const { return h_ && h_->A ? rails_csr_sprhs(h_->A) : nullptr; }
 
     HipOperatorWrapper transpose() const // flag flip (src/Epetra_OperatorWrapper.cpp)
     {
@@ -579,6 +594,11 @@ public:
     // A * X (src/LyapunovSolver.hpp:146)
     HipMultiVectorWrapper operator*(HipMultiVectorWrapper const &X) const
     {
+        if (n_cols_ >= 0) { // rectangular: the result is sized by the operator, p rows for the transposed product and m otherwise
+            HipMultiVectorWrapper out(transpose_ ? n_cols_ : m_global_, X.n_, ctx_);
+            if (h_) apply_into(X, out, 0);
+            return out;
+        }
         HipMultiVectorWrapper out(X, X.n_);
         out.m_global_ = X.m_global_;
         if (!h_) {
@@ -596,13 +616,54 @@ public:
         return hip_ok(rails_spmm(ctx_, h_->A, transpose_ ? 1 : 0, X.panel_->p, X.c0_, X.n_, Y.panel_->p, Y.c0_ + ycol), "rails_spmm");
     }
 
+    // ||B||_2 of a rectangular operator (m x nc as applied): the largest Ritz value of min(nc, 200) Lanczos steps on B'B from a random
+    // start vector (one RNG stream, as the power iteration below draws one).  Where the power iteration gains a factor
+    // (lambda_2 / lambda_1)^2 per product pair, Lanczos gains the Chebyshev rate, and with nc <= 200 it spans the whole space; a Ritz value
+    // never exceeds the norm.  The scale of the stopping test of a solve with a sparse B (src/LyapunovSolver.hpp:134).
+    double norm_rectangular(int64_t m, int64_t nc) const
+    {
+        const int steps = (int)std::min<int64_t>(nc, 200);
+        HipMultiVectorWrapper v(nc, 1, ctx_), vp(nc, 1, ctx_), w(nc, 1, ctx_), y(m, 1, ctx_);
+        v.random();
+        const double nv = v.norm();
+        if (nv == 0.0) return 0.0;
+        v /= nv;
+        std::vector<double> d, e;
+        double beta = 0.0;
+        for (int j = 0; j < steps; ++j) {
+            if (rails_spmm(ctx_, h_->A, transpose_ ? 1 : 0, v.panel_->p, 0, 1, y.panel_->p, 0) != RAILS_OK) return 0.0;
+            if (rails_spmm(ctx_, h_->A, transpose_ ? 0 : 1, y.panel_->p, 0, 1, w.panel_->p, 0) != RAILS_OK) return 0.0;
+            const double ny = y.norm(), alpha = ny * ny; // v'B'Bv
+            d.push_back(alpha);
+            rails_panel_axpy(ctx_, -alpha, v.panel_->p, 0, 1, w.panel_->p, 0);
+            if (j > 0) rails_panel_axpy(ctx_, -beta, vp.panel_->p, 0, 1, w.panel_->p, 0);
+            beta = w.norm();
+            if (j + 1 == steps || !(beta > 1e-14 * d[0])) break;
+            e.push_back(beta);
+            w /= beta;
+            std::swap(vp.panel_, v.panel_);
+            std::swap(v.panel_, w.panel_);
+        }
+        const int n = (int)d.size();
+        e.resize(std::max(n, 1), 0.0);
+        std::vector<double> work(1);
+        int info = 0;
+        rails_dsteqr('N', n, d.data(), e.data(), nullptr, 1, work.data(), &info);
+        if (info != 0) return 0.0;
+        const double lam = *std::max_element(d.begin(), d.end());
+        return lam > 0.0 ? std::sqrt(lam) : 0.0;
+    }
+
     // 2-norm of the operator, needed only when B is given as a Matrix (src/MatrixOrMultiVectorWrapper.hpp:33-38):
-    // power iteration on A^T A with the device kernels.
+    // power iteration on A^T A with the device kernels (x of the operator's columns, y of its rows).
     double norm() const
     {
         if (!h_) return 0.0;
-        int64_t m = rails_csr_rows(h_->A);
-        HipMultiVectorWrapper x(m, 1, ctx_), y(m, 1, ctx_);
+        int64_t m = rails_csr_rows(h_->A), nc = rails_csr_cols(h_->A);
+        if (transpose_) std::swap(m, nc);
+        if (m == 0 || nc == 0) return 0.0;
+        if (n_cols_ >= 0) return norm_rectangular(m, nc);
+        HipMultiVectorWrapper x(nc, 1, ctx_), y(m, 1, ctx_);
         x.random();
         double lam = 0.0;
         for (int it = 0; it < 200; ++it) {

@@ -90,6 +90,7 @@ public:
 
     bool given_as_operator() const { return kind_ == Operator; }
     MultiVector const &panel() const { return panel_; }
+    Matrix const &op() const { return op_; }
     // ||B||_2, the scale of the stopping test (src/LyapunovSolver.hpp:134)
     double norm2() const { return kind_ == Operator ? op_.norm() : panel_.norm(); }
     // B X and B'X
@@ -110,6 +111,7 @@ public:
     BOperand(Both const &b) : b_(b) {}
     bool given_as_operator() const { return false; }
     Both const &panel() const { return b_; }
+    Both const &op() const { return b_; }
     double norm2() const { return b_.norm(); }
     Both times(Both const &X) const { return b_ * X; }
     Both transposed_times(Both const &X) const { return b_.transpose() * X; }
@@ -342,6 +344,8 @@ public:
     // asked once per trip: true ends the run with the code of "stopped without converging" (a back end whose device work has failed)
     void set_failure_check(std::function<bool()> f) { broken_ = f; }
     int trips() const { return trips_; }
+    // ||B||_2^2 as the last solve computed it: the scale of its stopping test (src/LyapunovSolver.hpp:134)
+    double scale() const { return scale_; }
     std::vector<double> const &residual_history() const { return estimates_; }
     std::map<std::string, double> const &profile() const { return sections_; }
     void reset_profile() { sections_.clear(); }
@@ -656,6 +660,7 @@ private:
             }
             const double nb = s_.rhs_.norm2();
             scale_ = nb * nb;
+            s_.scale_ = scale_;
         }
 
         // The start space of methods x.1 and x.2 (matlab/RAILSsolver.m:288-314): V0 (the columns open() made, x.1) or B (x.2), then
@@ -940,6 +945,7 @@ private:
 protected:
     Matrix op_A_;
     BType rhs_;
+    double scale_ = 0.0;
     Matrix op_M_;
     Matrix op_Ainv_;
     bool has_inverse_ = false;

@@ -1,7 +1,7 @@
 """Command-line driver: solve A X M' + M X A' + B B' = 0 for X = V T V' with matrices from MatrixMarket files.
 
     python -m rails_amd.main [params.xml] [--dir DIR] [--A A.mtx] [--B B.mtx] [--M M.mtx] [--V V.mtx] [--T T.mtx]
-                               [--eigs K] [--variance FILE]
+                               [--eigs K] [--variance FILE] [--sparse-B]
     python -m torch.distributed.run --nproc-per-node N -m rails_amd.main ...      (one rank per GPU, rows partitioned)
 
 File names, formats and the parameter file follow the reference's driver (src/main.cpp:57-68,111,123-126): `A.mtx`, `B.mtx`
@@ -10,6 +10,10 @@ mass matrix with zeros on its diagonal (a descriptor system) is handled as the r
 Lyapunov equation is solved on the Schur complement A22 - A21 A11^-1 A12 of the rows where M is nonzero (rails_amd/schur.py; one
 rank), B is restricted to those rows and V has that many rows.  Otherwise M must be absent (identity) or symmetric positive
 definite.
+
+`--sparse-B` keeps B sparse, as the reference's driver does (src/main.cpp:67 reads B.mtx as a CrsMatrix, :98 hands the operator to the
+solver): B.mtx is read as CSR and goes to the solver as a rails_amd.SparseRHS (one rank, direct back end); after a Schur reduction it
+keeps the rows of the Schur complement.
 
 `--eigs K` and `--variance FILE` are the second half of the reference's driver (src/main.cpp:140-170) on the solution object
 (rails_amd.Solution): the K eigenvalues of largest modulus of the covariance X, each next to its share of the trace, written to
@@ -48,6 +52,7 @@ def main(argv=None):
     ap.add_argument("--variance", default=None, metavar="FILE", help="write diag(X), the pointwise variance, to FILE (MatrixMarket array)")
     ap.add_argument("--direct", action="store_true", help="direct back end (device panels for V, AV) instead of the default coordinate-space back end")
     ap.add_argument("--projected-lanczos", action="store_true", help="direct back end with the coefficient-space residual Lanczos (M = I only)")
+    ap.add_argument("--sparse-B", action="store_true", help="keep B sparse (B.mtx in coordinate format): a device CSR operator instead of a dense panel; one rank")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args(argv)
@@ -81,7 +86,15 @@ def main(argv=None):
     m, n, rowptr, col, val = mmio.read_csr(path(args.A))
     if m != n:
         raise SystemExit("A must be square, got %d x %d" % (m, n))
-    B = mmio.read_dense(path(args.B))
+    if args.sparse_B:
+        if world > 1:
+            raise SystemExit("--sparse-B: a sparse right-hand side runs on one rank")
+        import scipy.sparse as sp
+
+        bm, bp, brp, bcol, bval = mmio.read_csr(path(args.B))
+        B = sp.csr_matrix((bval, bcol, brp), shape=(bm, bp))
+    else:
+        B = mmio.read_dense(path(args.B))
     if B.shape[0] != m:
         raise SystemExit("B has %d rows, A has %d" % (B.shape[0], m))
     Mcsr = None
@@ -131,7 +144,13 @@ def main(argv=None):
             t0 = time.time()
             schur = SchurOperator(ctx, (rowptr, col, val), mdiag)
             _log(rank, "  %d algebraic rows eliminated, %d remain; A11 factorised in %.2f s" % (schur.m1, schur.m2, time.time() - t0))
-            B = schur.restrict(B)
+            if args.sparse_B:  # the rows of the Schur complement; the correction A21 A11^-1 B1 of restrict() would fill B
+                B1 = B[schur.idx1]
+                if B1.nnz and np.abs(B1.data).max() > np.sqrt(np.finfo(float).eps):
+                    raise SystemExit("--sparse-B: B has entries on the eliminated rows; run without --sparse-B")
+                B = B[schur.idx2]
+            else:
+                B = schur.restrict(B)
             if V0 is not None and V0.shape[0] == m:
                 V0 = V0[schur.idx2]
             d2 = schur.mass22
@@ -149,7 +168,7 @@ def main(argv=None):
     Mop = operator(Mcsr) if Mcsr else None
     if world > 1:
         ctx.set_allreduce(partition.make_allreduce(on_device=True))
-    solver = rails_amd.Solver(ctx, A, B[r0:r1], M=Mop, m_global=m)
+    solver = rails_amd.Solver(ctx, A, B if args.sparse_B else B[r0:r1], M=Mop, m_global=m)
     code = solver.set_parameters(params)
     if code != 0:
         raise SystemExit("set_parameters rejected the parameter set (code %d)" % code)

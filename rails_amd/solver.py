@@ -15,15 +15,27 @@ from .wrappers import HipOperatorWrapper, _f, _p
 
 class Solver:
     def __init__(self, ctx, A, B, M=None, m_global=None):
-        """A, M: HipOperatorWrapper (M None = identity).  B: host array, local rows x p."""
+        """A, M: HipOperatorWrapper (M None = identity).  B: host array, local rows x p; or a rails_amd.SparseRHS, or anything with
+        .tocsr() (a scipy sparse matrix), which is kept sparse (include/rails_solver.h: rails_solver_create_sparse; single GPU, direct
+        back end)."""
+        from .sparse_rhs import SparseRHS
+
         self.ctx = ctx
         self.lib = ctx.lib
         self.A, self.M = A, M
-        B = _f(B)
-        self.m_local, self.p = B.shape
         h = C.c_void_p()
-        check(self.lib.rails_solver_create(ctx.h, A.h.h, M.h.h if M is not None else None, _p(B), B.shape[0], B.shape[1],
-                                           m_global if m_global is not None else -1, C.byref(h)), "rails_solver_create")
+        if not isinstance(B, SparseRHS) and hasattr(B, "tocsr"):
+            B = SparseRHS.from_scipy(ctx, B)
+        if isinstance(B, SparseRHS):
+            self.B = B  # the object must live as long as the solver uses it
+            self.m_local, self.p = B.m, B.p
+            check(self.lib.rails_solver_create_sparse(ctx.h, A.h.h, M.h.h if M is not None else None, B.h, m_global if m_global is not None else -1,
+                                                      C.byref(h)), "rails_solver_create_sparse")
+        else:
+            B = _f(B)
+            self.m_local, self.p = B.shape
+            check(self.lib.rails_solver_create(ctx.h, A.h.h, M.h.h if M is not None else None, _p(B), B.shape[0], B.shape[1],
+                                               m_global if m_global is not None else -1, C.byref(h)), "rails_solver_create")
         self.h = h
         self._cb = None
         self.k = 0
@@ -108,6 +120,12 @@ class Solver:
 
     def trips(self):
         return self.lib.rails_solver_trips(self.h)
+
+    def scale(self):
+        """||B||_2^2 as the last solve computed it (the scale of the stopping test); 0 when the coordinate-space back end ran"""
+        out = C.c_double(0.0)
+        check(self.lib.rails_solver_scale(self.h, C.byref(out)), "rails_solver_scale")
+        return out.value
 
     def history(self):
         n = self.trips()

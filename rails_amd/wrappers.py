@@ -396,7 +396,10 @@ class HipOperatorWrapper:
         return self.ctx.lib.rails_csr_nnz(self.h.h)
 
     def transpose(self):
-        return HipOperatorWrapper(self.ctx, None, None, None, _handle=self.h, _trans=not self.trans)
+        t = HipOperatorWrapper(self.ctx, None, None, None, _handle=self.h, _trans=not self.trans)
+        if hasattr(self, "n_rows"):  # a rectangular operator: apply() sizes a new result by it
+            t.n_rows, t.n_cols = self.n_cols, self.n_rows
+        return t
 
     def set_variant(self, v):
         check(self.ctx.lib.rails_csr_set_variant(self.h.h, v), "rails_csr_set_variant")
