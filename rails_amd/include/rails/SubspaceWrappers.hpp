@@ -22,7 +22,6 @@
 #define RAILS_SUBSPACEWRAPPERS_HPP
 
 #include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
@@ -31,20 +30,11 @@
 #include <memory>
 #include <vector>
 
+#include "rails/BlockOrthHost.hpp"
 #include "rails/HipWrappers.hpp"
 
 namespace rails
 {
-
-// coefficient block: column-major, ld rows of capacity (rows past the basis dimension are zero), ncap columns
-struct CoefStore {
-    std::vector<double> c;
-    int ld = 0, ncap = 0;
-    bool in_basis = true; // false: a plain small replicated matrix with ld rows (B'W and friends)
-    CoefStore(int ld_, int ncap_, bool in_basis_) : c((size_t)std::max(ld_, 1) * std::max(ncap_, 1), 0.0), ld(ld_), ncap(std::max(ncap_, 1)), in_basis(in_basis_) {}
-    double *col(int j) { return c.data() + (size_t)j * ld; }
-    const double *col(int j) const { return c.data() + (size_t)j * ld; }
-};
 
 class SubspaceBasis
 {
@@ -63,7 +53,7 @@ public:
     double t_materialise = 0, t_absorb = 0, t_qr = 0, t_rotate = 0, t_recoef = 0;
     bool profile_sync = getenv("RAILS_SUBSPACE_PROFILE") != nullptr;
     bool trace = getenv("RAILS_SUBSPACE_TRACE") != nullptr;
-    double reorth_survival = getenv("RAILS_SUBSPACE_REORTH") ? atof(getenv("RAILS_SUBSPACE_REORTH")) : 0.5;
+    double reorth_survival = getenv("RAILS_SUBSPACE_REORTH") ? atof(getenv("RAILS_SUBSPACE_REORTH")) : block_orth::reorth_survival;
     // RAILS_SUBSPACE_SLOW_MS=x (with RAILS_SUBSPACE_PROFILE): one line on stderr for every part that took longer than x ms
     double slow_ms = getenv("RAILS_SUBSPACE_SLOW_MS") ? atof(getenv("RAILS_SUBSPACE_SLOW_MS")) : 0.0;
     struct Tick {
@@ -101,7 +91,7 @@ public:
     // coefficient store is re-based from the predicted new basis columns to the real ones (a w x w and a dim x w map, exact).
     // RAILS_SUBSPACE_OVERLAP=0 switches it off (every block then waits for its own orthogonalisation, as in round 1).
     bool overlap = !(getenv("RAILS_SUBSPACE_OVERLAP") && atoi(getenv("RAILS_SUBSPACE_OVERLAP")) == 0);
-    double overlap_min_survival = 1e-4; // below: rounding in the Pythagorean Gram matrix (eps / survival) is no longer negligible
+    double overlap_min_survival = block_orth::overlap_min_survival;
     long n_overlapped = 0;
     struct Pending {
         bool active = false;
@@ -201,6 +191,24 @@ public:
         return dim;
     }
 
+    // Fill the tail with n columns, at most 64 at a time, and absorb them.  fill(t0, j0, w) writes the columns [j0, j0 + w) of the
+    // caller's block into the panel columns [t0, t0 + w); false from it is latched in `failed`.  dest(j0) says where the coordinates
+    // of the columns from j0 on go (ld row_cap); it is asked after fill, when the rows are final, and what it names is zeroed here.
+    template <class Fill, class Dest>
+    void absorb_filled(int n, Fill &&fill, Dest &&dest)
+    {
+        for (int j0 = 0; j0 < n; j0 += 64) {
+            const int w = std::min(64, n - j0);
+            const int t0 = tail(w);
+            P.resize(t0 + w);
+            if (!fill(t0, j0, w)) failed = true;
+            P.resize(t0);
+            double *coef = dest(j0);
+            std::fill_n(coef, (size_t)row_cap * w, 0.0);
+            absorb_tail(w, coef);
+        }
+    }
+
     // The w columns X sitting in P's tail [dim, dim+w) are expressed in the basis: the part of X outside span(P) becomes new
     // orthonormal basis columns, coef (row_cap x w, zero-initialised by the caller, ld = row_cap) receives the coordinates of X in
     // the extended basis.  Block CGS2 against P, CholQR2 inside the block; the representation is X = P_old (C1 + C2) + Q (R2 R1).
@@ -226,19 +234,11 @@ public:
         double worst = 0.0;
         for (int j = 0; j < w; ++j)
             if (n0[j + (size_t)j * w] > 0.0) worst = std::max(worst, std::sqrt(n1[j + (size_t)j * w] / n0[j + (size_t)j * w]));
-        std::vector<double> PP((size_t)dim * dim);
-        if (!hip_ok(rails_gram(ctx, P.panel(), 0, dim, P.panel(), 0, dim, PP.data(), dim), "rails_gram")) return fail();
-        double orth = 0.0, against_old = 0.0;
-        int wi = -1, wj = -1;
-        for (int j = 0; j < dim; ++j)
-            for (int i = 0; i < dim; ++i) {
-                const double e = std::fabs(PP[i + (size_t)j * dim] - (i == j ? 1.0 : 0.0));
-                if (e > orth) { orth = e; wi = i; wj = j; }
-                if (j >= dim_before && i < dim_before) against_old = std::max(against_old, e);
-            }
-        if (trace) std::cerr << "absorb verified: dim " << dim_before << " -> " << dim << " w " << w << ": |X - P c| / |X| <= " << worst << ", |P'P - I| = " << orth << " at (" << wi << ", " << wj << "), new against old columns " << against_old << std::endl;
+        OrthDefect o;
+        if (!measure_orthonormality(dim_before, o)) return false;
+        if (trace) std::cerr << "absorb verified: dim " << dim_before << " -> " << dim << " w " << w << ": |X - P c| / |X| <= " << worst << ", |P'P - I| = " << o.orth << " at (" << o.i << ", " << o.j << "), new against old columns " << o.against_old << std::endl;
         verify_repr = std::max(verify_repr, worst);
-        verify_orth = std::max(verify_orth, orth);
+        verify_orth = std::max(verify_orth, o.orth);
         return true;
     }
     bool absorb_tail_impl(int w, double *coef)
@@ -248,185 +248,17 @@ public:
         n_absorb_cols += w;
         if (w <= 0) return true;
         Tick tick(this, &t_absorb, "absorb");
-        const int ld = row_cap;
-        rails_panel *pp = P.panel();
-        // one Gram call per round gives both the projections P'X (first dim rows) and the block's own Gram matrix X'X (last w rows):
-        // X sits right behind P in the same panel
-        const int dw = dim + w;
-        std::vector<double> CG((size_t)dw * w), G0((size_t)w * w), G((size_t)w * w);
-        bool have_G = false;
-        int w2 = w;                // columns [0, w2) take part in the second round
-        std::vector<double> C1t;   // first-round coefficients of the columns [w2, w) (for their Gram entries, see below)
-        for (int round = 0; round < 2; ++round) {
-            const int wr = round == 0 ? w : w2;
-            if (!hip_ok(rails_gram(ctx, pp, 0, dw, pp, dim, wr, CG.data(), dw), "rails_gram")) return fail();
-            if (round == 0) {
-                for (int j = 0; j < w; ++j)
-                    for (int i = 0; i < w; ++i) G0[i + (size_t)j * w] = CG[(dim + i) + (size_t)j * dw];
-            }
-            if (dim == 0) {
-                G = G0;
-                have_G = true;
-                break;
-            }
-            std::vector<double> c2(wr, 0.0); // squared length of what this round finds along P, per column
-            for (int j = 0; j < wr; ++j)
-                for (int i = 0; i < dim; ++i) c2[j] += CG[i + (size_t)j * dw] * CG[i + (size_t)j * dw];
-            for (int j = 0; j < wr; ++j)
-                for (int i = 0; i < dim; ++i) coef[i + (size_t)j * ld] += CG[i + (size_t)j * dw];
-            if (round == 0) {
-                // "twice is enough" (Kahan / Parlett; the DGKS rule): one projection leaves a component (eps + delta) * ||x|| / ||x'||
-                // along P, delta = ||P'P - I||.  Where at least half of a column's squared norm survives that factor is <= sqrt(2)
-                // and a second projection has nothing to repair.  A looser rule is unstable over long runs: the defect of each new
-                // basis column is the old delta times ||x|| / ||x'||, and chains of small survivals compound it (measured with 1 %: V'V - I
-                // of 1e-14, 2e-12, 6e-7, 0.9 after 50, 100, 200, 400 trips of a stagnating solve).
-                // The rule is applied per column; the second round runs on the leading columns up to the last one that needs it (the
-                // prefetched random vector at the end of an A*W block never does: one MFMA tile of 16 columns instead of two).
-                double worst = 1.0; // smallest fraction of a column's squared norm that survives the projection
-                w2 = 0;
-                for (int j = 0; j < w; ++j) {
-                    const double g = G0[j + (size_t)j * w];
-                    const double surv = g > 0.0 ? 1.0 - c2[j] / g : 0.0;
-                    worst = std::min(worst, surv);
-                    if (!(surv > reorth_survival)) w2 = j + 1;
-                }
-                if (trace) std::cerr << "absorb: dim " << dim << " w " << w << " first round: smallest survival " << worst << ", second round on " << w2 << " columns" << std::endl;
-                // (the overlapped form queues the update of this round itself: fused with the second projection, one pass over P)
-                if (overlap && w <= 48 && worst >= overlap_min_survival && start_overlapped(w, w2, coef, CG, G0)) return true;
-                if (failed) return false; // (the chain could not be queued: part of it may have run, the block is not to be touched again)
-                if (!hip_ok(rails_panel_gemm(ctx, -1.0, pp, 0, dim, CG.data(), dw, wr, 1.0, pp, dim), "rails_panel_gemm")) return fail();
-                if (w2 == 0) break;
-                n_second_round++;
-                if (w2 < w) { // keep what the Gram entries of the untouched columns need
-                    C1t.assign((size_t)dim * (w - w2), 0.0);
-                    for (int j = w2; j < w; ++j) memcpy(C1t.data() + (size_t)(j - w2) * dim, CG.data() + (size_t)j * dw, sizeof(double) * dim);
-                }
-            } else {
-                if (!hip_ok(rails_panel_gemm(ctx, -1.0, pp, 0, dim, CG.data(), dw, wr, 1.0, pp, dim), "rails_panel_gemm")) return fail();
-                // The block's Gram matrix after the second round.  Columns i, j < w2: the one just measured minus the (tiny) second
-                // correction.  One of them >= w2: as measured (the correction term is the product of two rounding-level quantities).
-                // Both >= w2 (projected once, more than half survived): the first Gram matrix minus the first correction.
-                for (int j = 0; j < w2; ++j)
-                    for (int i = 0; i < w; ++i) {
-                        double v = CG[(dim + i) + (size_t)j * dw];
-                        if (i < w2) {
-                            double s2 = 0.0;
-                            for (int l = 0; l < dim; ++l) s2 += CG[l + (size_t)i * dw] * CG[l + (size_t)j * dw];
-                            v -= s2;
-                        }
-                        G[i + (size_t)j * w] = v;
-                        G[j + (size_t)i * w] = v;
-                    }
-                for (int j = w2; j < w; ++j)
-                    for (int i = w2; i < w; ++i) {
-                        double s1 = 0.0;
-                        const double *ci = C1t.data() + (size_t)(i - w2) * dim, *cj = C1t.data() + (size_t)(j - w2) * dim;
-                        for (int l = 0; l < dim; ++l) s1 += ci[l] * cj[l];
-                        G[i + (size_t)j * w] = G0[i + (size_t)j * w] - s1;
-                    }
-                have_G = true;
-            }
-        }
-        if (!have_G && !hip_ok(rails_gram(ctx, pp, dim, w, pp, dim, w, G.data(), w), "rails_gram")) return fail();
-        // columns that (numerically) lie in span(P): nothing new to add
-        std::vector<int> keep;
-        for (int j = 0; j < w; ++j) {
-            if (G[j + (size_t)j * w] > 1e-26 * G0[j + (size_t)j * w] && G[j + (size_t)j * w] > 0.0)
-                keep.push_back(j);
-            else {
-                n_dropped++;
-                if (trace) std::cerr << "absorb: column " << j << " dropped after the projections: " << G[j + (size_t)j * w] << " left of " << G0[j + (size_t)j * w] << std::endl;
-            }
-        }
-        // A column of which less than 1e-4 of its length survived the projections may be nothing but their rounding error --
-        // normalised, such a "direction" would not be orthogonal to P (error ~ eps / survival) and poison the basis; this happens
-        // when span(P) is (nearly) the whole space or the block repeats old vectors.  Test: normalise the survivors and project
-        // once more; a genuine direction keeps most of its unit length, rounding noise does not.
-        std::vector<double> colscale(w, 1.0); // original residual column = colscale * column now in the panel
-        bool delicate = false;
-        for (int j : keep)
-            if (G[j + (size_t)j * w] < 1e-8 * G0[j + (size_t)j * w]) delicate = true;
-        if (delicate && dim > 0) {
-            n_delicate++;
-            for (int j : keep) {
-                colscale[j] = std::sqrt(G[j + (size_t)j * w]);
-                if (!hip_ok(rails_panel_scale(ctx, pp, dim + j, 1, 1.0 / colscale[j]), "rails_panel_scale")) return fail();
-            }
-            if (!hip_ok(rails_gram(ctx, pp, 0, dim, pp, dim, w, CG.data(), dim), "rails_gram")) return fail();
-            if (!hip_ok(rails_panel_gemm(ctx, -1.0, pp, 0, dim, CG.data(), dim, w, 1.0, pp, dim), "rails_panel_gemm")) return fail();
-            if (!hip_ok(rails_gram(ctx, pp, dim, w, pp, dim, w, G.data(), w), "rails_gram")) return fail();
-            std::vector<int> survivors;
-            for (int j : keep) {
-                // (what the third projection took out belongs to the column whether or not the rest of it is kept)
-                for (int i = 0; i < dim; ++i) coef[i + (size_t)j * ld] += colscale[j] * CG[i + (size_t)j * dim];
-                if (G[j + (size_t)j * w] > 0.25)
-                    survivors.push_back(j);
-                else {
-                    n_dropped++;
-                    if (trace) std::cerr << "absorb: delicate column " << j << " dropped: " << G[j + (size_t)j * w] << " of its unit length left (it was " << colscale[j] << " long)" << std::endl;
-                }
-            }
-            keep.swap(survivors);
-        }
-        const int r = (int)keep.size();
-        if (r == 0) return true;
-        // Cholesky of the diagonally scaled Gram matrix of the kept columns
-        std::vector<double> d(r), S((size_t)r * r);
-        for (int a = 0; a < r; ++a) d[a] = std::sqrt(G[keep[a] + (size_t)keep[a] * w]);
-        for (int b = 0; b < r; ++b)
-            for (int a = 0; a < r; ++a) S[a + (size_t)b * r] = G[keep[a] + (size_t)keep[b] * w] / (d[a] * d[b]);
-        std::vector<double> R1 = S;
-        int info = 0;
-        rails_dpotrf('U', r, R1.data(), r, &info);
-        bool ok = info == 0;
-        for (int a = 0; a < r && ok; ++a)
-            if (!(R1[a + (size_t)a * r] > 1e-6)) ok = false;
-        if (!ok) return absorb_one_by_one(w, coef, keep, colscale);
-        for (int b = 0; b < r; ++b)
-            for (int a = b + 1; a < r; ++a) R1[a + (size_t)b * r] = 0.0;
-        // Q1 = X[:, keep] D^-1 R1^-1, written over the whole tail block in place (dropped columns become zero, Q1 fills the
-        // first r tail columns)
-        std::vector<double> M1((size_t)w * w, 0.0), Rinv((size_t)r * r, 0.0);
-        upper_inverse(R1, r, Rinv);
-        for (int b = 0; b < r; ++b)
-            for (int a = 0; a <= b; ++a) M1[keep[a] + (size_t)b * w] = Rinv[a + (size_t)b * r] / d[a];
-        if (!hip_ok(rails_panel_gemm(ctx, 1.0, pp, dim, w, M1.data(), w, w, 0.0, pp, dim), "rails_panel_gemm")) return fail();
-        // second pass: Q = Q1 R2^-1
-        std::vector<double> G2((size_t)r * r), R2;
-        if (!hip_ok(rails_gram(ctx, pp, dim, r, pp, dim, r, G2.data(), r), "rails_gram")) return fail();
-        R2 = G2;
-        rails_dpotrf('U', r, R2.data(), r, &info);
-        if (info != 0) return fail("Cholesky of a nearly orthonormal block failed");
-        for (int b = 0; b < r; ++b)
-            for (int a = b + 1; a < r; ++a) R2[a + (size_t)b * r] = 0.0;
-        std::vector<double> R2inv((size_t)r * r, 0.0);
-        upper_inverse(R2, r, R2inv);
-        if (!hip_ok(rails_panel_gemm(ctx, 1.0, pp, dim, r, R2inv.data(), r, r, 0.0, pp, dim), "rails_panel_gemm")) return fail();
-        // X[:, keep[b]] = Q * (R2 * R1(:, b)) * d[b]
-        std::vector<double> Rf((size_t)r * r, 0.0);
-        for (int b = 0; b < r; ++b)
-            for (int a = 0; a <= b; ++a) {
-                double s = 0.0;
-                for (int l = a; l <= b; ++l) s += R2[a + (size_t)l * r] * R1[l + (size_t)b * r];
-                Rf[a + (size_t)b * r] = s * d[b] * colscale[keep[b]];
-                coef[(dim + a) + (size_t)keep[b] * ld] = Rf[a + (size_t)b * r];
-            }
-        // An ill-conditioned block: Q = X R^-1 has magnified what rounding left of span(P) in X by up to 1 / min diag(R1).  Take
-        // it out again (it is tiny: the block stays orthonormal to second order) and book it on the old coordinates.
-        double rmin = 1.0;
-        for (int a = 0; a < r; ++a) rmin = std::min(rmin, R1[a + (size_t)a * r]);
-        if (rmin < 1e-2 && dim > 0) {
-            n_reprojected++;
-            std::vector<double> C3((size_t)dim * r);
-            if (!hip_ok(rails_gram(ctx, pp, 0, dim, pp, dim, r, C3.data(), dim), "rails_gram")) return fail();
-            if (!hip_ok(rails_panel_gemm(ctx, -1.0, pp, 0, dim, C3.data(), dim, r, 1.0, pp, dim), "rails_panel_gemm")) return fail();
-            for (int b = 0; b < r; ++b)
-                for (int l = 0; l <= b; ++l) {
-                    const double f = Rf[l + (size_t)b * r];
-                    for (int i = 0; i < dim; ++i) coef[i + (size_t)keep[b] * ld] += C3[i + (size_t)l * dim] * f;
-                }
-        }
-        dim += r;
+        Block blk(w);
+        bool handed_over = false, dependent = false;
+        if (!project_rounds(blk, coef, handed_over)) return false; // block CGS2 against P: X = P (C1 + C2) + X'
+        if (handed_over) return true;                              // (the overlapped form has queued the rest)
+        if (!screen_survivors(blk, coef)) return false;            // columns of X' that are nothing but span(P) or rounding error go
+        if (blk.keep.empty()) return true;
+        if (!cholqr2(blk, dependent)) return false;                // X'[:, keep] = Q (R2 R1 D)
+        if (dependent) return absorb_one_by_one(w, coef, blk.keep, blk.colscale);
+        book_new_coordinates(blk, coef);
+        if (!reproject_ill_conditioned(blk, coef)) return false;
+        dim += (int)blk.keep.size();
         P.resize(dim);
         return true;
     }
@@ -454,27 +286,14 @@ public:
         std::vector<double> Call((size_t)dim * ncols);
         int c0 = 0;
         for (auto &s : stores)
-            for (int j = 0; j < s->ncap; ++j) {
-                const double *cj = s->col(j);
-                bool nz = false;
-                for (int i = 0; i < dim && !nz; ++i) nz = cj[i] != 0.0;
-                if (!nz) continue;
-                memcpy(Call.data() + (size_t)c0 * dim, cj, sizeof(double) * dim);
-                ++c0;
-            }
+            for (int j = 0; j < s->ncap; ++j)
+                if (s->in_use(j, dim)) memcpy(Call.data() + (size_t)c0++ * dim, s->col(j), sizeof(double) * dim);
         ncols = c0;
         if (trace) {
             std::cerr << "compress: dim " << dim << ", " << stores.size() << " live stores, columns in use:";
             for (auto &st : stores) {
                 int used = 0;
-                for (int j = 0; j < st->ncap; ++j) {
-                    const double *cj = st->col(j);
-                    for (int i = 0; i < dim; ++i)
-                        if (cj[i] != 0.0) {
-                            ++used;
-                            break;
-                        }
-                }
+                for (int j = 0; j < st->ncap; ++j) used += st->in_use(j, dim) ? 1 : 0;
                 std::cerr << " " << used << "/" << st->ncap;
             }
             std::cerr << " -> " << ncols << " columns" << std::endl;
@@ -504,14 +323,8 @@ public:
         // host: C <- Q' C (columns up to the last non-zero one of every store)
         for (auto &s : stores) {
             int used = 0;
-            for (int j = s->ncap - 1; j >= 0 && !used; --j) {
-                const double *cj = s->col(j);
-                for (int i = 0; i < dim; ++i)
-                    if (cj[i] != 0.0) {
-                        used = j + 1;
-                        break;
-                    }
-            }
+            for (int j = s->ncap - 1; j >= 0 && !used; --j)
+                if (s->in_use(j, dim)) used = j + 1;
             if (used == 0) continue;
             std::vector<double> nc((size_t)rank * used);
             rails_dgemm('T', 'N', rank, used, dim, 1.0, Q.data(), dim, s->c.data(), s->ld, 0.0, nc.data(), rank);
@@ -525,32 +338,13 @@ public:
         n_compress++;
     }
 
-    // The first round of a block has been applied (X <- X - P C1 is queued, coef holds C1): predict the block's coordinates along its
-    // own new basis columns, queue the rest of the orthogonalisation on the device, and return without waiting.  false: conditions not
-    // met (nothing was queued; the caller goes on in the ordinary way).
+    // The first round of a block has been measured (coef holds C1, CG = [C1; X'X]): predict the block's coordinates along its own new
+    // basis columns, queue the first update and the rest of the orthogonalisation on the device, and return without waiting.  false:
+    // conditions not met (nothing was queued; the caller goes on in the ordinary way).
     bool start_overlapped(int w, int w2, double *coef, std::vector<double> const &CG, std::vector<double> const &G0)
     {
         const int ld = row_cap, dw = dim + w;
-        // Gram matrix of the projected block by Pythagoras, its scaled Cholesky factor
-        std::vector<double> Gp((size_t)w * w), d(w);
-        for (int j = 0; j < w; ++j)
-            for (int i = 0; i <= j; ++i) {
-                double s = 0.0;
-                for (int l = 0; l < dim; ++l) s += CG[l + (size_t)i * dw] * CG[l + (size_t)j * dw];
-                Gp[i + (size_t)j * w] = Gp[j + (size_t)i * w] = G0[i + (size_t)j * w] - s;
-            }
-        for (int j = 0; j < w; ++j) {
-            if (!(Gp[j + (size_t)j * w] > 1e-8 * G0[j + (size_t)j * w]) || !(Gp[j + (size_t)j * w] > 0.0)) return false;
-            d[j] = std::sqrt(Gp[j + (size_t)j * w]);
-        }
-        std::vector<double> R1((size_t)w * w);
-        for (int b = 0; b < w; ++b)
-            for (int a = 0; a < w; ++a) R1[a + (size_t)b * w] = Gp[a + (size_t)b * w] / (d[a] * d[b]);
-        int info = 0;
-        rails_dpotrf('U', w, R1.data(), w, &info);
-        if (info != 0) return false;
-        for (int a = 0; a < w; ++a)
-            if (!(R1[a + (size_t)a * w] > 1e-2)) return false; // an ill-conditioned block takes the careful way (re-projection)
+        if (!block_orth::predict_block(CG.data(), dim, w, pending.Rfp)) return false;
         if (!hip_ok(rails_deferred_reserve(ctx, N_SLOTS, (int64_t)(P.capacity() + 64) * (w <= 32 ? 32 : 48)), "rails_deferred_reserve")) return false;
         // the device's part: the first update, the second round on the leading w2 columns, Gram matrix of the block, its Cholesky
         // factor inverted, Q1 = X M1, the same once more (CholQR2)
@@ -569,19 +363,15 @@ public:
         ok = ok && hip_ok(rails_chol_inverse_deferred(ctx, SLOT_G2, w, SLOT_M2), "rails_chol_inverse_deferred");
         ok = ok && hip_ok(rails_panel_gemm_deferred(ctx, 1.0, pp, dim, w, SLOT_M2, w, w, 0.0, pp, dim), "rails_panel_gemm_deferred");
         if (!ok) return fail("the overlapped block orthogonalisation could not be queued"); // false, with `failed` latched: the caller gives up
-        // predicted coordinates along the new columns: X = Q Rfp, Rfp = R1 D
+        // predicted coordinates along the new columns: X = Q Rfp
         pending.active = true;
         pending.dim0 = dim;
         pending.w = w;
         pending.w2 = w2;
-        pending.Rfp.assign((size_t)w * w, 0.0);
         pending.g0diag.resize(w);
         for (int b = 0; b < w; ++b) {
             pending.g0diag[b] = G0[b + (size_t)b * w];
-            for (int a = 0; a <= b; ++a) {
-                pending.Rfp[a + (size_t)b * w] = R1[a + (size_t)b * w] * d[b];
-                coef[(dim + a) + (size_t)b * ld] = pending.Rfp[a + (size_t)b * w];
-            }
+            for (int a = 0; a <= b; ++a) coef[(dim + a) + (size_t)b * ld] = pending.Rfp[a + (size_t)b * w];
         }
         if (w2 > 0) n_second_round++;
         n_overlapped++;
@@ -597,18 +387,8 @@ public:
         return true;
     }
 
-    // What is checked here can only fail if the prediction was grossly wrong: the block was taken on because (by Pythagoras, relative
-    // error eps / survival <= 1e-12) every column keeps >= 1e-4 of its squared length and the scaled Cholesky factor's diagonal is above
-    // 1e-2; the read-back asks for 1e-8 and 1e-6 and for the predicted factor to match the real one to 1e-4.  A block that misses those by
-    // four to ten orders of magnitude means the device did not meet the block the host was promised (a faulted kernel, non-finite data):
-    // by then the host has used the predicted coordinates in a projected solve and a Lanczos run, and the block itself has been
-    // overwritten in place -- there is nothing sound to fall back to, so the failure is latched (`failed`), reported on stderr, and ends the
-    // run at the next trip (Solver::set_failure_check); rails_solver_solve returns RAILS_EHIP.  Blocks that need the careful treatment
-    // (nearly dependent columns, directions already in span(P)) never get here: they fail the conditions of start_overlapped and take the
-    // synchronous path of absorb_tail.
     // Read back what the queued orthogonalisation produced and move every live coefficient store from the predicted new basis columns to
-    // the real ones: with X = P (C1 + C2) + Q Rft the truth and (C1, Rfp) what was booked, a vector with booked coordinates
-    // (a_old, a_new) is P (a_old + C2 Rfp^-1 a_new) + Q (Rft Rfp^-1 a_new).
+    // the real ones (block_orth::rebase_maps; why a rejected block ends the run is said with the thresholds in BlockOrthHost.hpp).
     bool resolve_pending()
     {
         if (!pending.active) return !failed;
@@ -616,88 +396,21 @@ public:
         const int d0 = pending.dim0, w = pending.w, w2 = pending.w2;
         if (!hip_ok(rails_ctx_sync(ctx), "rails_ctx_sync")) return fail();
         std::vector<double> C2((size_t)d0 * w, 0.0), G((size_t)w * w), G2((size_t)w * w);
-        bool ok = true;
-        if (w2 > 0) ok = ok && hip_ok(rails_deferred_fetch(ctx, SLOT_C2, (int64_t)d0 * w2, C2.data()), "rails_deferred_fetch");
-        ok = ok && hip_ok(rails_deferred_fetch(ctx, SLOT_G, (int64_t)w * w, G.data()), "rails_deferred_fetch");
-        ok = ok && hip_ok(rails_deferred_fetch(ctx, SLOT_G2, (int64_t)w * w, G2.data()), "rails_deferred_fetch");
-        if (!ok) return fail();
-        // the factors the device applied, repeated on the host's copies of the two Gram matrices
-        auto factor = [&](std::vector<double> const &Gm, std::vector<double> &R, std::vector<double> &dd) {
-            dd.resize(w);
-            R.assign((size_t)w * w, 0.0);
-            for (int j = 0; j < w; ++j) {
-                if (!(Gm[j + (size_t)j * w] > 0.0) || !std::isfinite(Gm[j + (size_t)j * w])) return false;
-                dd[j] = std::sqrt(Gm[j + (size_t)j * w]);
-            }
-            for (int b = 0; b < w; ++b)
-                for (int a = 0; a < w; ++a) R[a + (size_t)b * w] = Gm[a + (size_t)b * w] / (dd[a] * dd[b]);
-            int inf = 0;
-            rails_dpotrf('U', w, R.data(), w, &inf);
-            if (inf != 0) return false;
-            for (int b = 0; b < w; ++b)
-                for (int a = b + 1; a < w; ++a) R[a + (size_t)b * w] = 0.0;
-            return true;
-        };
-        std::vector<double> R1, d1, R2, d2;
-        if (!factor(G, R1, d1) || !factor(G2, R2, d2)) return fail("the overlapped block orthogonalisation met a block that is not of full rank");
-        for (int j = 0; j < w; ++j)
-            if (!(G[j + (size_t)j * w] > 1e-8 * pending.g0diag[j]) || !(R1[j + (size_t)j * w] > 1e-6))
-                return fail("the overlapped block orthogonalisation met a block it should have treated with care");
-        // Rft = (R2 D2) (R1 D1), upper triangular
-        std::vector<double> Rft((size_t)w * w, 0.0);
-        for (int b = 0; b < w; ++b)
-            for (int a = 0; a <= b; ++a) {
-                double sum = 0.0;
-                for (int l = a; l <= b; ++l) sum += R2[a + (size_t)l * w] * d2[l] * R1[l + (size_t)b * w];
-                Rft[a + (size_t)b * w] = sum * d1[b];
-            }
-        // Tn = Rft Rfp^-1 (w x w, upper), To = [C2 0] Rfp^-1 (d0 x w)
-        std::vector<double> Rpi((size_t)w * w, 0.0), Tn((size_t)w * w, 0.0), To((size_t)d0 * w, 0.0);
-        upper_inverse(pending.Rfp, w, Rpi);
-        double off = 0.0;
-        for (int b = 0; b < w; ++b)
-            for (int a = 0; a <= b; ++a) {
-                double sum = 0.0;
-                for (int l = a; l <= b; ++l) sum += Rft[a + (size_t)l * w] * Rpi[l + (size_t)b * w];
-                Tn[a + (size_t)b * w] = sum;
-                off = std::max(off, std::fabs(sum - (a == b ? 1.0 : 0.0)));
-            }
-        if (!(off < 1e-4)) return fail("the overlapped block orthogonalisation did not confirm its prediction");
-        if (w2 > 0) rails_dgemm('N', 'N', d0, w, w2, 1.0, C2.data(), d0, Rpi.data(), w, 0.0, To.data(), d0);
-        if (trace) std::cerr << "absorb (overlapped): dim " << d0 << " w " << w << ": prediction off by " << off << std::endl;
-        std::vector<double> an(w), bn(w);
+        if (w2 > 0 && !hip_ok(rails_deferred_fetch(ctx, SLOT_C2, (int64_t)d0 * w2, C2.data()), "rails_deferred_fetch")) return fail();
+        if (!hip_ok(rails_deferred_fetch(ctx, SLOT_G, (int64_t)w * w, G.data()), "rails_deferred_fetch")) return fail();
+        if (!hip_ok(rails_deferred_fetch(ctx, SLOT_G2, (int64_t)w * w, G2.data()), "rails_deferred_fetch")) return fail();
+        block_orth::RebaseMaps maps;
+        if (const char *why = block_orth::rebase_maps(C2.data(), d0, w2, G.data(), G2.data(), w, pending.Rfp, pending.g0diag, maps)) return fail(why);
+        if (trace) std::cerr << "absorb (overlapped): dim " << d0 << " w " << w << ": prediction off by " << maps.off << std::endl;
         for (auto &wk : live)
-            if (auto st = wk.lock()) {
-                for (int j = 0; j < st->ncap; ++j) {
-                    double *cj = st->col(j);
-                    bool nz = false;
-                    for (int a = 0; a < w; ++a) {
-                        an[a] = cj[d0 + a];
-                        nz = nz || an[a] != 0.0;
-                    }
-                    if (!nz) continue;
-                    if (w2 > 0)
-                        for (int a = 0; a < w; ++a) {
-                            if (an[a] == 0.0) continue;
-                            const double *t = To.data() + (size_t)a * d0;
-                            for (int i = 0; i < d0; ++i) cj[i] += t[i] * an[a];
-                        }
-                    for (int a = 0; a < w; ++a) {
-                        double sum = 0.0;
-                        for (int l = a; l < w; ++l) sum += Tn[a + (size_t)l * w] * an[l];
-                        bn[a] = sum;
-                    }
-                    for (int a = 0; a < w; ++a) cj[d0 + a] = bn[a];
-                }
-            }
+            if (auto st = wk.lock())
+                for (int j = 0; j < st->ncap; ++j)
+                    if (st->in_use(j, d0 + w, d0)) block_orth::rebase_column(maps, st->col(j));
         if (verify && !failed) { // (RAILS_SUBSPACE_VERIFY: the basis with the block the device has just finished)
-            std::vector<double> PP((size_t)dim * dim);
-            if (!hip_ok(rails_gram(ctx, P.panel(), 0, dim, P.panel(), 0, dim, PP.data(), dim), "rails_gram")) return fail();
-            double orth = 0.0;
-            for (int j = 0; j < dim; ++j)
-                for (int i = 0; i < dim; ++i) orth = std::max(orth, std::fabs(PP[i + (size_t)j * dim] - (i == j ? 1.0 : 0.0)));
-            if (trace) std::cerr << "absorb (overlapped) verified: dim " << d0 << " -> " << dim << ": |P'P - I| = " << orth << std::endl;
-            verify_orth = std::max(verify_orth, orth);
+            OrthDefect o;
+            if (!measure_orthonormality(dim, o)) return false;
+            if (trace) std::cerr << "absorb (overlapped) verified: dim " << d0 << " -> " << dim << ": |P'P - I| = " << o.orth << std::endl;
+            verify_orth = std::max(verify_orth, o.orth);
         }
         return !failed;
     }
@@ -710,16 +423,186 @@ private:
         return false;
     }
 
-    static void upper_inverse(std::vector<double> const &R, int r, std::vector<double> &Rinv)
+    // the largest entry of P'P - I and where it sits; against_old: the largest among the columns from dim_before on against the ones before
+    struct OrthDefect { double orth = 0.0, against_old = 0.0; int i = -1, j = -1; };
+    bool measure_orthonormality(int dim_before, OrthDefect &o)
     {
-        for (int j = 0; j < r; ++j) {
-            Rinv[j + (size_t)j * r] = 1.0 / R[j + (size_t)j * r];
-            for (int i = j - 1; i >= 0; --i) {
-                double s = 0.0;
-                for (int l = i + 1; l <= j; ++l) s += R[i + (size_t)l * r] * Rinv[l + (size_t)j * r];
-                Rinv[i + (size_t)j * r] = -s / R[i + (size_t)i * r];
+        std::vector<double> PP((size_t)dim * dim);
+        if (!hip_ok(rails_gram(ctx, P.panel(), 0, dim, P.panel(), 0, dim, PP.data(), dim), "rails_gram")) return fail();
+        for (int j = 0; j < dim; ++j)
+            for (int i = 0; i < dim; ++i) {
+                const double e = std::fabs(PP[i + (size_t)j * dim] - (i == j ? 1.0 : 0.0));
+                if (e > o.orth) { o.orth = e; o.i = i; o.j = j; }
+                if (j >= dim_before && i < dim_before) o.against_old = std::max(o.against_old, e);
+            }
+        return true;
+    }
+
+    static void add_scaled(double *coefcol, const double *Ccol, int nb, double scale) { for (int i = 0; i < nb; ++i) coefcol[i] += scale * Ccol[i]; }
+    // Project the columns [c, c+n) of the tail (panel columns from dim + c) against the first nb basis columns: C = P'X, measured with
+    // `rows` >= nb rows (the rows past dim are the products with the tail's own leading columns), X -= P C, and where coef (ld row_cap)
+    // is given, coef += scale * C.
+    bool project_tail(int c, int n, int nb, std::vector<double> &C, int rows, double scale = 0.0, double *coef = nullptr)
+    {
+        C.resize((size_t)rows * n);
+        if (!hip_ok(rails_gram(ctx, P.panel(), 0, rows, P.panel(), dim + c, n, C.data(), rows), "rails_gram")) return fail();
+        if (!hip_ok(rails_panel_gemm(ctx, -1.0, P.panel(), 0, nb, C.data(), rows, n, 1.0, P.panel(), dim + c), "rails_panel_gemm")) return fail();
+        for (int j = 0; coef && j < n; ++j) add_scaled(coef + (size_t)j * row_cap, C.data() + (size_t)j * rows, nb, scale);
+        return true;
+    }
+
+    // ---- the steps of absorb_tail_impl ---------------------------------------------------------------------------------------------
+    // a block on its way into the basis: w columns in P's tail
+    // G0, G: its Gram matrix before the projections and after them (w x w); colscale: original residual column = colscale * column now
+    // in the panel; keep: the columns that bring something new; d, R1, R2: the scaling and the factor of each pass of their CholQR2;
+    // Rf: X'[:, keep] = Q Rf
+    struct Block {
+        int w;
+        std::vector<double> G0, G, colscale, d, R1, R2, Rf;
+        std::vector<int> keep;
+        explicit Block(int w_) : w(w_), G0((size_t)w_ * w_), G((size_t)w_ * w_), colscale(w_, 1.0) {}
+    };
+
+    // Up to two projection rounds against P; coef receives C1 + C2, b.G0 and b.G the block's Gram matrix before and after.  One Gram
+    // call per round gives both the projections P'X (first dim rows) and the block's own products X'X (last w rows): X sits right
+    // behind P in the same panel.  The second round runs by the DGKS rule, per column (block_orth::dgks_rule; the prefetched random
+    // vector at the end of an A*W block never needs it: one MFMA tile of 16 columns instead of two).  handed_over: the overlapped form
+    // has taken the block after the first round's measurement.
+    bool project_rounds(Block &b, double *coef, bool &handed_over)
+    {
+        const int w = b.w, dw = dim + w, ld = row_cap;
+        rails_panel *pp = P.panel();
+        std::vector<double> CG((size_t)dw * w), CG2;
+        if (!hip_ok(rails_gram(ctx, pp, 0, dw, pp, dim, w, CG.data(), dw), "rails_gram")) return fail();
+        for (int j = 0; j < w; ++j)
+            for (int i = 0; i < w; ++i) b.G0[i + (size_t)j * w] = CG[(dim + i) + (size_t)j * dw];
+        if (dim == 0) {
+            b.G = b.G0;
+            return true;
+        }
+        std::vector<double> c2(w); // squared length of what the first round finds along P, per column
+        for (int j = 0; j < w; ++j) {
+            c2[j] = block_orth::dot(CG.data() + (size_t)j * dw, CG.data() + (size_t)j * dw, dim);
+            add_scaled(coef + (size_t)j * ld, CG.data() + (size_t)j * dw, dim, 1.0);
+        }
+        int w2 = 0; // columns [0, w2) take part in the second round
+        const double worst = block_orth::dgks_rule(b.G0.data(), w, c2.data(), reorth_survival, w2);
+        if (trace) std::cerr << "absorb: dim " << dim << " w " << w << " first round: smallest survival " << worst << ", second round on " << w2 << " columns" << std::endl;
+        // (the overlapped form queues the update of this round itself: fused with the second projection, one pass over P)
+        if (overlap && w <= 48 && worst >= overlap_min_survival && start_overlapped(w, w2, coef, CG, b.G0)) return handed_over = true;
+        if (failed) return false; // (the chain could not be queued: part of it may have run, the block is not to be touched again)
+        if (!hip_ok(rails_panel_gemm(ctx, -1.0, pp, 0, dim, CG.data(), dw, w, 1.0, pp, dim), "rails_panel_gemm")) return fail();
+        if (w2 == 0) return hip_ok(rails_gram(ctx, pp, dim, w, pp, dim, w, b.G.data(), w), "rails_gram") || fail();
+        n_second_round++;
+        if (!project_tail(0, w2, dim, CG2, dw, 1.0, coef)) return false;
+        // The block's Gram matrix after the second round.  Columns i, j < w2: the one just measured minus the (tiny) second correction.
+        // One of them >= w2: as measured (the correction term is the product of two rounding-level quantities).  Both >= w2 (projected
+        // once, more than half survived): the first Gram matrix minus the first correction.
+        for (int j = 0; j < w2; ++j)
+            for (int i = 0; i < w; ++i) {
+                double v = CG2[(dim + i) + (size_t)j * dw];
+                if (i < w2) v -= block_orth::dot(CG2.data() + (size_t)i * dw, CG2.data() + (size_t)j * dw, dim);
+                b.G[i + (size_t)j * w] = b.G[j + (size_t)i * w] = v;
+            }
+        for (int j = w2; j < w; ++j)
+            for (int i = w2; i < w; ++i) b.G[i + (size_t)j * w] = b.G0[i + (size_t)j * w] - block_orth::dot(CG.data() + (size_t)i * dw, CG.data() + (size_t)j * dw, dim);
+        return true;
+    }
+
+    // Which columns bring something new (b.keep).  Columns that (numerically) lie in span(P) go.  A column of which less than 1e-4 of
+    // its length survived the projections may be nothing but their rounding error -- normalised, such a "direction" would not be
+    // orthogonal to P (error ~ eps / survival) and poison the basis; this happens when span(P) is (nearly) the whole space or the
+    // block repeats old vectors.  Test: normalise the survivors and project once more; a genuine direction keeps most of its unit
+    // length, rounding noise does not.
+    bool screen_survivors(Block &b, double *coef)
+    {
+        const int w = b.w;
+        auto left = [&](int j) { return b.G[j + (size_t)j * w]; };
+        auto before = [&](int j) { return b.G0[j + (size_t)j * w]; };
+        for (int j = 0; j < w; ++j) {
+            if (left(j) > block_orth::drop_fraction * before(j) && left(j) > 0.0)
+                b.keep.push_back(j);
+            else {
+                n_dropped++;
+                if (trace) std::cerr << "absorb: column " << j << " dropped after the projections: " << left(j) << " left of " << before(j) << std::endl;
             }
         }
+        bool delicate = false;
+        for (int j : b.keep)
+            if (left(j) < block_orth::delicate_fraction * before(j)) delicate = true;
+        if (!delicate || dim == 0) return true;
+        n_delicate++;
+        for (int j : b.keep) {
+            b.colscale[j] = std::sqrt(left(j));
+            if (!hip_ok(rails_panel_scale(ctx, P.panel(), dim + j, 1, 1.0 / b.colscale[j]), "rails_panel_scale")) return fail();
+        }
+        std::vector<double> C;
+        if (!project_tail(0, w, dim, C, dim)) return false;
+        if (!hip_ok(rails_gram(ctx, P.panel(), dim, w, P.panel(), dim, w, b.G.data(), w), "rails_gram")) return fail();
+        std::vector<int> survivors;
+        for (int j : b.keep) {
+            // (what the third projection took out belongs to the column whether or not the rest of it is kept)
+            add_scaled(coef + (size_t)j * row_cap, C.data() + (size_t)j * dim, dim, b.colscale[j]);
+            if (left(j) > block_orth::delicate_keep)
+                survivors.push_back(j);
+            else {
+                n_dropped++;
+                if (trace) std::cerr << "absorb: delicate column " << j << " dropped: " << left(j) << " of its unit length left (it was " << b.colscale[j] << " long)" << std::endl;
+            }
+        }
+        b.keep.swap(survivors);
+        return true;
+    }
+
+    // CholQR2 of the kept columns, in place: Cholesky of their diagonally scaled Gram matrix, Q1 = X[:, keep] D^-1 R1^-1 written over
+    // the whole tail block (dropped columns become zero, Q1 fills the first r tail columns), then Q = Q1 R2^-1 from Q1's own Gram
+    // matrix.  dependent: the kept columns depend on each other; nothing was done to them.
+    bool cholqr2(Block &b, bool &dependent)
+    {
+        const int w = b.w, r = (int)b.keep.size();
+        rails_panel *pp = P.panel();
+        dependent = !block_orth::scaled_cholesky(b.G.data(), w, b.keep.data(), r, b.d, b.R1);
+        for (int a = 0; a < r && !dependent; ++a)
+            if (!(b.R1[a + (size_t)a * r] > block_orth::dependent_diag)) dependent = true;
+        if (dependent) return true;
+        std::vector<double> M1((size_t)w * w, 0.0), Rinv;
+        block_orth::upper_inverse(b.R1, r, Rinv);
+        for (int c = 0; c < r; ++c)
+            for (int a = 0; a <= c; ++a) M1[b.keep[a] + (size_t)c * w] = Rinv[a + (size_t)c * r] / b.d[a];
+        if (!hip_ok(rails_panel_gemm(ctx, 1.0, pp, dim, w, M1.data(), w, w, 0.0, pp, dim), "rails_panel_gemm")) return fail();
+        b.R2.resize((size_t)r * r);
+        if (!hip_ok(rails_gram(ctx, pp, dim, r, pp, dim, r, b.R2.data(), r), "rails_gram")) return fail();
+        if (!block_orth::cholesky_upper(b.R2, r)) return fail("Cholesky of a nearly orthonormal block failed");
+        block_orth::upper_inverse(b.R2, r, Rinv);
+        return hip_ok(rails_panel_gemm(ctx, 1.0, pp, dim, r, Rinv.data(), r, r, 0.0, pp, dim), "rails_panel_gemm") || fail();
+    }
+
+    // X'[:, keep[c]] = Q * (R2 * R1(:, c)) * d[c]: the coordinates along the new basis columns
+    void book_new_coordinates(Block &b, double *coef)
+    {
+        const int r = (int)b.keep.size();
+        block_orth::upper_product(b.R2, b.R1, r, b.Rf);
+        for (int c = 0; c < r; ++c)
+            for (int a = 0; a <= c; ++a) {
+                b.Rf[a + (size_t)c * r] = b.Rf[a + (size_t)c * r] * b.d[c] * b.colscale[b.keep[c]];
+                coef[(dim + a) + (size_t)b.keep[c] * row_cap] = b.Rf[a + (size_t)c * r];
+            }
+    }
+
+    // An ill-conditioned block: Q = X R^-1 has magnified what rounding left of span(P) in X by up to 1 / min diag(R1).  Take it out
+    // again (it is tiny: the block stays orthonormal to second order) and book it on the old coordinates.
+    bool reproject_ill_conditioned(Block &b, double *coef)
+    {
+        const int r = (int)b.keep.size();
+        double rmin = 1.0;
+        for (int a = 0; a < r; ++a) rmin = std::min(rmin, b.R1[a + (size_t)a * r]);
+        if (!(rmin < block_orth::reproject_diag && dim > 0)) return true;
+        n_reprojected++;
+        std::vector<double> C3;
+        if (!project_tail(0, r, dim, C3, dim)) return false;
+        for (int c = 0; c < r; ++c)
+            for (int l = 0; l <= c; ++l) add_scaled(coef + (size_t)b.keep[c] * row_cap, C3.data() + (size_t)l * dim, dim, b.Rf[l + (size_t)c * r]);
+        return true;
     }
 
     // degenerate block (its kept columns are dependent among themselves after the projection): take the columns one at a
@@ -731,11 +614,12 @@ private:
         const int ld = row_cap;
         rails_panel *pp = P.panel();
         const int base = dim;
+        std::vector<double> c;
         // move the kept columns to the front of the tail one at a time: column j of the block sits at base + j
         int accepted = 0;
         for (int idx = 0; idx < (int)keep.size(); ++idx) {
             const int j = keep[idx];
-            const int src = base + j, dst = base + accepted;
+            const int src = base + j, dst = base + accepted, nb = base + accepted;
             if (src != dst && !hip_ok(rails_panel_copy(ctx, pp, src, 1, pp, dst), "rails_panel_copy")) return fail();
             double g0 = 0.0, g = 0.0;
             if (!hip_ok(rails_gram(ctx, pp, dst, 1, pp, dst, 1, &g0, 1), "rails_gram")) return fail();
@@ -744,15 +628,10 @@ private:
             // chain of nearly dependent columns (the first residual directions of a run all lie close to span(B)) that compounds
             // geometrically -- measured on BASELINE configs[1]: P'P - I of 2e-14, 2e-12, 1e-10, 4e-9, 1e-8 along one block of 25
             // columns, 3e-5 two trips later, and projected matrices V'AV off by the same.
-            for (int round = 0; round < 2 && accepted > 0; ++round) {
-                const int nb = base + accepted;
-                std::vector<double> c(nb);
-                if (!hip_ok(rails_gram(ctx, pp, 0, nb, pp, dst, 1, c.data(), nb), "rails_gram")) return fail();
-                if (!hip_ok(rails_panel_gemm(ctx, -1.0, pp, 0, nb, c.data(), nb, 1, 1.0, pp, dst), "rails_panel_gemm")) return fail();
-                for (int a = 0; a < nb; ++a) coef[a + (size_t)j * ld] += colscale[j] * c[a];
-            }
+            for (int round = 0; round < 2 && accepted > 0; ++round)
+                if (!project_tail(accepted, 1, nb, c, nb, colscale[j], coef + (size_t)j * ld)) return false;
             if (!hip_ok(rails_gram(ctx, pp, dst, 1, pp, dst, 1, &g, 1), "rails_gram")) return fail();
-            if (!(g > 1e-24 * g0) || !(g > 0.0)) {
+            if (!(g > block_orth::single_drop_fraction * g0) || !(g > 0.0)) {
                 n_dropped++;
                 if (trace) std::cerr << "absorb one by one: column " << j << " dropped: " << g << " left of " << g0 << " (scale " << colscale[j] << ")" << std::endl;
                 continue;
@@ -760,18 +639,14 @@ private:
             const double nrm = std::sqrt(g);
             if (!hip_ok(rails_panel_scale(ctx, pp, dst, 1, 1.0 / nrm), "rails_panel_scale")) return fail();
             double last = nrm;
-            if (g < 1e-8 * g0 && base + accepted > 0) {
+            if (g < block_orth::delicate_fraction * g0 && nb > 0) {
                 // less than 1e-4 of the column was left: is it a direction or the rounding error of the projections?  Project the
-                // normalised vector against the whole basis so far; a direction survives (and is now orthogonal to rounding)
-                const int nb = base + accepted;
-                std::vector<double> c(nb);
+                // normalised vector against the whole basis so far; a direction survives (and is now orthogonal to rounding).
+                // What the projection takes out belongs to the column whether or not the rest of it is kept.
                 double n2 = 0.0;
-                if (!hip_ok(rails_gram(ctx, pp, 0, nb, pp, dst, 1, c.data(), nb), "rails_gram")) return fail();
-                if (!hip_ok(rails_panel_gemm(ctx, -1.0, pp, 0, nb, c.data(), nb, 1, 1.0, pp, dst), "rails_panel_gemm")) return fail();
+                if (!project_tail(accepted, 1, nb, c, nb, colscale[j] * nrm, coef + (size_t)j * ld)) return false;
                 if (!hip_ok(rails_gram(ctx, pp, dst, 1, pp, dst, 1, &n2, 1), "rails_gram")) return fail();
-                // what the projection took out belongs to the column whether or not the rest of it is kept
-                for (int a = 0; a < nb; ++a) coef[a + (size_t)j * ld] += colscale[j] * nrm * c[a];
-                if (!(n2 > 0.25)) {
+                if (!(n2 > block_orth::delicate_keep)) {
                     n_dropped++;
                     if (trace) std::cerr << "absorb one by one: column " << j << " dropped after the check against the whole basis: " << n2 << " of its unit length left (it was " << colscale[j] * nrm << " long)" << std::endl;
                     continue;
@@ -779,14 +654,14 @@ private:
                 if (!hip_ok(rails_panel_scale(ctx, pp, dst, 1, 1.0 / std::sqrt(n2)), "rails_panel_scale")) return fail();
                 last = nrm * std::sqrt(n2);
             }
-            coef[(base + accepted) + (size_t)j * ld] = colscale[j] * last;
-            if (trace) std::cerr << "absorb one by one: column " << j << " -> basis column " << base + accepted << ": " << g << " left of " << g0 << " (scale " << colscale[j] << ")" << std::endl;
-            if (verify && trace && base + accepted > 0) {
-                std::vector<double> c(base + accepted);
-                rails_gram(ctx, pp, 0, base + accepted, pp, dst, 1, c.data(), base + accepted);
+            coef[nb + (size_t)j * ld] = colscale[j] * last;
+            if (trace) std::cerr << "absorb one by one: column " << j << " -> basis column " << nb << ": " << g << " left of " << g0 << " (scale " << colscale[j] << ")" << std::endl;
+            if (verify && trace && nb > 0) {
+                c.resize(nb);
+                rails_gram(ctx, pp, 0, nb, pp, dst, 1, c.data(), nb);
                 double e = 0.0;
                 int at = -1;
-                for (int a = 0; a < base + accepted; ++a)
+                for (int a = 0; a < nb; ++a)
                     if (std::fabs(c[a]) > e) { e = std::fabs(c[a]); at = a; }
                 std::cerr << "    against the basis so far: " << e << " at column " << at << std::endl;
             }
@@ -815,6 +690,12 @@ class SubspaceMultiVector
     double *cptr(int j = 0) const { return store_->col(c0_ + j); }
     int ld() const { return store_->ld; }
     bool in_basis() const { return !store_ || store_->in_basis; }
+
+    bool fits(bool shapes_agree, int om, int on) const // says so where they do not
+    {
+        if (!shapes_agree) std::cerr << "rails_amd: operands of " << M() << " x " << N() << " and " << om << " x " << on << " do not fit together" << std::endl;
+        return shapes_agree;
+    }
 
     void ensure_cols(int n)
     {
@@ -891,12 +772,7 @@ public:
         }
         // every entry of the m-dimensional columns equal to v: one constant vector, expressed in the basis
         SubspaceBasis &b = *basis_;
-        int t0 = b.tail(1);
-        b.P.resize(t0 + 1);
-        if (!hip_ok(rails_panel_fill(b.ctx, b.P.panel(), t0, 1, v), "rails_panel_fill")) b.failed = true;
-        b.P.resize(t0);
-        std::fill_n(cptr(0), ld(), 0.0);
-        b.absorb_tail(1, cptr(0));
+        b.absorb_filled(1, [&](int t0, int, int) { return hip_ok(rails_panel_fill(b.ctx, b.P.panel(), t0, 1, v), "rails_panel_fill"); }, [&](int) { return cptr(0); });
         for (int j = 1; j < n_; ++j) memcpy(cptr(j), cptr(0), sizeof(double) * ld());
         return *this;
     }
@@ -1002,15 +878,7 @@ public:
             }
             std::cerr << "rails_amd: a prefetched random vector is discarded (random() on " << n_ << " columns)" << std::endl;
         }
-        for (int j0 = 0; j0 < n_; j0 += 64) {
-            int w = std::min(64, n_ - j0);
-            int t0 = b.tail(w);
-            b.P.resize(t0 + w);
-            if (!hip_ok(rails_panel_random(b.ctx, b.P.panel(), t0, w), "rails_panel_random")) b.failed = true;
-            b.P.resize(t0);
-            for (int j = 0; j < w; ++j) std::fill_n(cptr(j0 + j), ld(), 0.0);
-            b.absorb_tail(w, cptr(j0));
-        }
+        b.absorb_filled(n_, [&](int t0, int, int w) { return hip_ok(rails_panel_random(b.ctx, b.P.panel(), t0, w), "rails_panel_random"); }, [&](int j0) { return cptr(j0); });
         orthogonalized_ = 0;
     }
 
@@ -1027,10 +895,7 @@ public:
     HostDenseMatrix dot(SubspaceMultiVector const &o) const
     {
         HostDenseMatrix out(n_, o.n_);
-        if (in_basis() != o.in_basis() || rows() != o.rows()) {
-            std::cerr << "Incomplatible matrices of sizes " << M() << "x" << N() << " and " << o.M() << "x" << o.N() << std::endl;
-            return out;
-        }
+        if (!fits(in_basis() == o.in_basis() && rows() == o.rows(), o.M(), o.N())) return out;
         if (n_ > 0 && o.n_ > 0 && rows() > 0) rails_dgemm('T', 'N', n_, o.n_, rows(), 1.0, cptr(), ld(), o.cptr(), o.ld(), 0.0, (double *)out, out.LDA());
         return out;
     }
@@ -1038,10 +903,7 @@ public:
     SubspaceMultiVector operator*(HostDenseMatrix const &C) const // src/StlWrapper.cpp:168-187
     {
         SubspaceMultiVector out(*this, C.N());
-        if (C.M() != n_) {
-            std::cerr << "Incomplatible matrices of sizes " << M() << "x" << N() << " and " << C.M() << "x" << C.N() << std::endl;
-            return out;
-        }
+        if (!fits(C.M() == n_, C.M(), C.N())) return out;
         if (C.N() > 0 && n_ > 0 && rows() > 0)
             rails_dgemm('N', C.transposed() ? 'T' : 'N', rows(), C.N(), n_, 1.0, cptr(), ld(), (double *)C, C.raw_ld(), 0.0, out.cptr(), out.ld());
         return out;
@@ -1052,18 +914,12 @@ public:
     {
         if (transpose_) {
             SubspaceMultiVector out = Plain(basis_, n_, o.n_);
-            if (rows() != o.rows() || in_basis() != o.in_basis()) {
-                std::cerr << "Incomplatible matrices of sizes " << M() << "x" << N() << " and " << o.M() << "x" << o.N() << std::endl;
-                return out;
-            }
+            if (!fits(rows() == o.rows() && in_basis() == o.in_basis(), o.M(), o.N())) return out;
             if (n_ > 0 && o.n_ > 0 && rows() > 0) rails_dgemm('T', 'N', n_, o.n_, rows(), 1.0, cptr(), ld(), o.cptr(), o.ld(), 0.0, out.cptr(), out.ld());
             return out;
         }
         SubspaceMultiVector out(*this, o.n_);
-        if (o.in_basis() || o.rows() != n_) {
-            std::cerr << "Incomplatible matrices of sizes " << M() << "x" << N() << " and " << o.M() << "x" << o.N() << std::endl;
-            return out;
-        }
+        if (!fits(!o.in_basis() && o.rows() == n_, o.M(), o.N())) return out;
         if (o.n_ > 0 && n_ > 0 && rows() > 0) rails_dgemm('N', 'N', rows(), o.n_, n_, 1.0, cptr(), ld(), o.cptr(), o.ld(), 0.0, out.cptr(), out.ld());
         return out;
     }
@@ -1177,14 +1033,8 @@ public:
     {
         const int n = X.N();
         SubspaceMultiVector out(b, n);
-        for (int j0 = 0; j0 < n; j0 += 64) {
-            int w = std::min(64, n - j0);
-            int t0 = b->tail(w);
-            b->P.resize(t0 + w);
-            if (!hip_ok(rails_panel_copy(b->ctx, X.panel(), X.offset() + j0, w, b->P.panel(), t0), "rails_panel_copy")) b->failed = true;
-            b->P.resize(t0);
-            b->absorb_tail(w, out.cptr(j0));
-        }
+        b->absorb_filled(n, [&](int t0, int j0, int w) { return hip_ok(rails_panel_copy(b->ctx, X.panel(), X.offset() + j0, w, b->P.panel(), t0), "rails_panel_copy"); },
+                         [&](int j0) { return out.cptr(j0); });
         return out;
     }
 };
@@ -1219,28 +1069,24 @@ public:
         SubspaceMultiVector out(basis_, n);
         if (n <= 0) return out;
         HipMultiVectorWrapper Xd = X.materialise();
-        for (int j0 = 0; j0 < n; j0 += 64) {
-            int w = std::min(64, n - j0);
-            const bool pre = b.prefetch_random && !b.cached_valid && j0 + w == n && w < 64;
-            int t0 = b.tail(w + (pre ? 1 : 0));
-            b.P.resize(t0 + w + (pre ? 1 : 0));
-            HipMultiVectorWrapper Xw = (w == 1) ? Xd.view(j0) : Xd.view(j0, j0 + w - 1);
-            if (!A_.apply_into(Xw, b.P, t0)) b.failed = true;
-            if (pre && !hip_ok(rails_panel_random(b.ctx, b.P.panel(), t0 + w, 1), "rails_panel_random")) b.failed = true;
-            b.P.resize(t0);
-            if (!pre) {
-                b.absorb_tail(w, out.cptr(j0));
-                continue;
-            }
-            // the block [A*W | q] is absorbed as one; its last column's coordinates are kept for the coming random()
-            std::vector<double> coef((size_t)b.row_cap * (w + 1), 0.0);
-            b.absorb_tail(w + 1, coef.data());
-            for (int j = 0; j < w; ++j) memcpy(out.cptr(j0 + j), coef.data() + (size_t)j * b.row_cap, sizeof(double) * b.row_cap);
-            if (!b.cached_random || b.cached_random->ld != b.row_cap) b.cached_random = b.new_store(1, true);
-            memcpy(b.cached_random->col(0), coef.data() + (size_t)w * b.row_cap, sizeof(double) * b.row_cap);
-            b.cached_valid = true;
-            b.n_prefetched++;
-        }
+        auto product = [&](int t0, int j0, int w) { return A_.apply_into((w == 1) ? Xd.view(j0) : Xd.view(j0, j0 + w - 1), b.P, t0); };
+        // the last chunk of 64 takes the coming random() along where there is room for it
+        const int wl = n - (n - 1) / 64 * 64;
+        const bool pre = b.prefetch_random && !b.cached_valid && wl < 64;
+        const int n_main = pre ? n - wl : n;
+        b.absorb_filled(n_main, product, [&](int j0) { return out.cptr(j0); });
+        if (!pre) return out;
+        // the block [A*W | q] is absorbed as one; its last column's coordinates are kept for the coming random()
+        std::vector<double> coef;
+        b.absorb_filled(wl + 1, [&](int t0, int, int) {
+            const bool ok = product(t0, n_main, wl);
+            return hip_ok(rails_panel_random(b.ctx, b.P.panel(), t0 + wl, 1), "rails_panel_random") && ok;
+        }, [&](int) { return coef.resize((size_t)b.row_cap * (wl + 1)), coef.data(); });
+        for (int j = 0; j < wl; ++j) memcpy(out.cptr(n_main + j), coef.data() + (size_t)j * b.row_cap, sizeof(double) * b.row_cap);
+        if (!b.cached_random || b.cached_random->ld != b.row_cap) b.cached_random = b.new_store(1, true);
+        memcpy(b.cached_random->col(0), coef.data() + (size_t)wl * b.row_cap, sizeof(double) * b.row_cap);
+        b.cached_valid = true;
+        b.n_prefetched++;
         return out;
     }
 };

@@ -551,6 +551,48 @@ static void subspace_basis_cases(rails_ctx *ctx)
         CHECK(orthonormal(basis2->P));
         CHECK(same(c.materialise(), X2, 1e-13));
     }
+    g_case = "Subspace.Basis second round, synchronous and overlapped";
+    {
+        // a block whose leading two columns keep 30 % of their squared length outside span(P) (the DGKS rule sends them through a
+        // second round) and whose other three are random (one round): once waiting for its orthogonalisation, once in the overlapped
+        // form, on the same basis and the same block
+        uint64_t seed = 0, stream = 0;
+        CHECK(rails_ctx_rng_state(ctx, &seed, &stream) == 0);
+        std::vector<double> coef[2];
+        for (int run = 0; run < 2; ++run) {
+            CHECK(rails_ctx_set_seed(ctx, seed, stream) == 0);
+            auto basis = std::make_shared<SubspaceBasis>(ctx, m, m, 16);
+            basis->overlap = run == 1;
+            SubspaceMultiVector p(basis, 10);
+            p.random();
+            HipMultiVectorWrapper inside = p.materialise().copy(), X(m, 5, ctx);
+            X.random();
+            std::vector<double> hi = host_of(inside), hx = host_of(X);
+            for (int j = 0; j < 2; ++j) {
+                double ni = 0.0, no = 0.0;
+                std::vector<double> in(m);
+                for (int i = 0; i < m; ++i) {
+                    in[i] = j == 0 ? hi[i + 2 * (size_t)m] - 0.5 * hi[i + 7 * (size_t)m] : hi[i + 4 * (size_t)m] + 0.25 * hi[i + (size_t)m];
+                    ni += in[i] * in[i];
+                    no += hx[i + j * (size_t)m] * hx[i + j * (size_t)m];
+                }
+                for (int i = 0; i < m; ++i) hx[i + j * (size_t)m] = std::sqrt(0.7 / ni) * in[i] + std::sqrt(0.3 / no) * hx[i + j * (size_t)m];
+            }
+            X.from_host(hx.data(), m);
+            const long second_before = basis->n_second_round, overlapped_before = basis->n_overlapped;
+            SubspaceMultiVector c = SubspaceMultiVector::Absorb(basis, X);
+            CHECK(basis->n_second_round == second_before + 1 && basis->dim == 15);
+            CHECK(basis->n_overlapped == overlapped_before + run);
+            HipMultiVectorWrapper image = c.materialise().copy(); // (in the overlapped form this is where the block is read back)
+            CHECK(!basis->failed);
+            CHECK(orthonormal(basis->P));
+            CHECK(same(image, X, 1e-13));
+            for (int j = 0; j < 5; ++j)
+                for (int i = 0; i < c.coefficient_rows(); ++i) coef[run].push_back(c.coefficients()[i + (size_t)j * c.coefficient_ld()]);
+        }
+        CHECK(coef[0].size() == 75 && coef[1].size() == 75);
+        for (size_t k = 0; k < std::min(coef[0].size(), coef[1].size()); ++k) CHECK_NEAR(coef[0][k], coef[1][k], 1e-11);
+    }
     g_case = "Subspace.Basis growth and compress";
     {
         auto basis = std::make_shared<SubspaceBasis>(ctx, m, m, 16);
