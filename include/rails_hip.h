@@ -344,6 +344,21 @@ int rails_orthogonalize(rails_ctx *ctx, rails_panel *V, int k_old, int w, int me
  * q = 0 is rails_orthogonalize. */
 int rails_orthogonalize_deflated(rails_ctx *ctx, rails_panel *V, int k_old, int w, const rails_panel *N, int nc0, int q, int method, int *used);
 
+/* Column sums of squares of X[:, c0:c0+nc), all-reduced over the ranks, to the host.  One pass over the window for any nc
+ * (a kernel of its own, 16-byte loads along the rows, every order of summation fixed: two calls agree bit for bit).  Synchronises. */
+int rails_panel_colnorms2(rails_ctx *ctx, const rails_panel *X, int c0, int nc, double *out_host);
+
+/* An orthonormal basis of the range of columns that may be rank deficient: the reference's Morth for a start space
+ * (matlab/RAILSsolver.m:567-580), in column order.  Column i of W = V[:, k_old:k_old+w) is scaled to unit length, projected twice
+ * against N[:, nc0:nc0+q), V[:, 0:k_old) and the columns kept before it, and kept, normalised, when at least `tol` of its unit length
+ * survives; otherwise it is dropped.  A column whose own norm is zero or not finite is dropped.  [N, V_old] must be orthonormal.
+ * On return V[:, k_old:k_old+*kept) holds the kept directions and V[:, k_old+*kept : k_old+w) is zero; kept_idx (may be NULL, room for w)
+ * receives the original column index (0 .. w-1) of each kept direction, in increasing order.  tol <= 0 means 1e-8.  Any w with
+ * k_old + w <= capacity; q = 0 means no nullspace (N may then be NULL).  Works in blocks of 128 columns with block operations only:
+ * the number of synchronisations grows with the number of blocks, not of columns (orth.hip). */
+int rails_orthogonalize_range(rails_ctx *ctx, rails_panel *V, int k_old, int w, const rails_panel *N, int nc0, int q, double tol, int *kept,
+                              int32_t *kept_idx);
+
 /* Fused residual Lanczos (src/LyapunovSolver.hpp:367-447): L steps of Lanczos on the implicit
  *   R = AV*T*MV^T + MV*T*AV^T + B*B^T      (MV == V for M = I)
  * started from a fresh random unit vector (one RNG stream is consumed, as Q.random() does at :374).

@@ -32,7 +32,8 @@ int rails_solver_destroy(rails_solver *s);
 
 /* set_parameters -- src/LyapunovSolver.hpp:72-98.  Names are the reference's ("Maximum iterations",
  * "Tolerance", "Expand size", "Lanczos iterations", "Restart size", "Reduced size", "Restart iterations",
- * "Restart tolerance", "Minimize solution space", "Restart from solution"; any capitalisation the
+ * "Restart tolerance", "Minimize solution space", "Restart from solution", "Restart upon start" (opts.restart_upon_start of
+ * matlab/RAILSsolver.m:53-57: shrink the space right after the first projected solve of a warm start); any capitalisation the
  * reference accepts).  Values are stored until rails_solver_apply_parameters, which returns the
  * reference's code (0 ok, 1 = Lanczos iterations <= Expand size). */
 int rails_solver_set_parameter(rails_solver *s, const char *name, double value);
@@ -67,6 +68,18 @@ int rails_solver_set_trip_callback(rails_solver *s, rails_trip_fn fn, void *user
 
 /* warm start: set V (host column-major, local rows x k); assumed orthonormal ("Restart from solution") */
 int rails_solver_set_V(rails_solver *s, const double *V_host, int64_t ldv, int k);
+
+/* opts.space of matlab/RAILSsolver.m:25-28: columns [c0, c0+k) of a device panel of the solver's local rows (a previous solution's
+ * rails_solution_panel, [V_prev, B], the union of two earlier solutions) become the start space of the NEXT solve, copied device to
+ * device.  They need not be orthonormal or independent: the solve orthonormalises them (rails_orthogonalize_range), drops every column
+ * of which less than 1e-8 survives and projects the nullspace out.  The next solve is a warm start whatever "Restart from solution"
+ * says; one solve consumes the space, as rails_solver_set_V is consumed.  The solve is refused (*code = -2, V and T unchanged) when no
+ * column survives.  Both back ends; with a nullspace set as well the solve runs on the direct back end (as a sparse B always does),
+ * whose orthonormalisation projects the nullspace out column block by column block.  (On the direct back end such a solve applies the
+ * parameters set so far, as rails_solver_apply_parameters does.)  A panel with another row count, or k < 1: RAILS_EINVAL. */
+int rails_solver_set_start_space(rails_solver *s, const rails_panel *P, int c0, int k);
+/* columns the last solve kept of its start space; 1 after a cold start */
+int rails_solver_start_rank(rails_solver *s);
 
 /* solve(V, T) -- src/LyapunovSolver.hpp:100-346.  *code = 0 converged, -1 not converged, 1 loop exhausted,
  * 2 stopped by max_trips; *k = V.N(). */

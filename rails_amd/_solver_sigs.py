@@ -18,6 +18,8 @@ SOLVER_SIGNATURES = {
     "rails_solver_set_trip_callback": (C.c_int, [_vp, TRIP_FN, _vp]),
     "rails_solver_set_inverse": (C.c_int, [_vp, _vp]),
     "rails_solver_set_V": (C.c_int, [_vp, _dp, C.c_int64, C.c_int]),
+    "rails_solver_set_start_space": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),
+    "rails_solver_start_rank": (C.c_int, [_vp]),
     "rails_solver_set_nullspace": (C.c_int, [_vp, _dp, C.c_int64, C.c_int]),
     "rails_solver_nullspace_rank": (C.c_int, [_vp]),
     "rails_solver_solve": (C.c_int, [_vp, _ip, _ip]),

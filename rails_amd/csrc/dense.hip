@@ -458,6 +458,121 @@ extern "C" int rails_gram(rails_ctx *c, const rails_panel *X, int xc0, int a, co
     return RAILS_OK;
 }
 
+// ---- column sums of squares ------------------------------------------------------------------------------------------------------
+// The column norms of a wide window (the pre-scaling and the second stage of the rank decision of rails_orthogonalize_range, orth.hip)
+// are the diagonal of its Gram matrix, but a 512 x 512 Gram product computed for its diagonal does 2 m 512^2 flops where reading the
+// 8 m 512 bytes once suffices.  k_colnorms2: thread (tx, ty) of a block owns the column pair 2 tx, 2 tx + 1 of the window and every
+// TY-th row of the block's slab, TX * TY = 256 with TX the next power of two above the number of pairs -- so a wave reads up to 1 KiB of
+// one row with 16-byte loads (a window that starts at an odd column is read 8 bytes at a time, same sums).  A thread adds its rows in
+// increasing order into four interleaved strands, the strands 0..3, then the TY row classes through LDS in a tree of fixed shape, then
+// the slabs in k_reduce_partials: every order is fixed by (m, nc) alone, so two runs agree bit for bit.  nc <= 512.
+namespace {
+
+__global__ __launch_bounds__(256) void k_colnorms2(const double *__restrict__ X, int ldx, int nc, int64_t m, int64_t rows_per_slab, int tx_bits,
+                                                   int vec_ok, double *__restrict__ partial)
+{
+    __shared__ double sh[256][2];
+    const int TX = 1 << tx_bits, TY = 256 >> tx_bits;
+    const int tx = threadIdx.x & (TX - 1), ty = threadIdx.x >> tx_bits;
+    const int c = 2 * tx;
+    const bool has0 = c < nc, has1 = c + 1 < nc;
+    const int64_t r_begin = (int64_t)blockIdx.x * rows_per_slab;
+    const int64_t r_end = r_begin + rows_per_slab < m ? r_begin + rows_per_slab : m;
+    double s0[4] = {0.0, 0.0, 0.0, 0.0}, s1[4] = {0.0, 0.0, 0.0, 0.0};
+    if (has0) {
+        const bool pair = has1 && vec_ok;
+        auto load = [&](int64_t r, double &a, double &b) {
+            const double *src = X + r * ldx + c;
+            if (pair) {
+                const v2f64 t = *reinterpret_cast<const v2f64 *>(src);
+                a = t.x;
+                b = t.y;
+            } else {
+                a = src[0];
+                b = has1 ? src[1] : 0.0;
+            }
+        };
+        int64_t r = r_begin + ty;
+        for (; r + 3 * (int64_t)TY < r_end; r += 4 * (int64_t)TY) { // four rows in flight, one per strand
+            double a[4], b[4];
+#pragma unroll
+            for (int s = 0; s < 4; ++s) load(r + s * (int64_t)TY, a[s], b[s]);
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                s0[s] += a[s] * a[s];
+                s1[s] += b[s] * b[s];
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < 3; ++s) // at most three rows are left: strands 0, 1, 2
+            if (r + s * (int64_t)TY < r_end) {
+                double a, b;
+                load(r + s * (int64_t)TY, a, b);
+                s0[s] += a * a;
+                s1[s] += b * b;
+            }
+    }
+    sh[threadIdx.x][0] = ((s0[0] + s0[1]) + s0[2]) + s0[3];
+    sh[threadIdx.x][1] = ((s1[0] + s1[1]) + s1[2]) + s1[3];
+    __syncthreads();
+    for (int half = TY >> 1; half > 0; half >>= 1) { // row class ty += row class ty + half: a tree of fixed shape
+        if (ty < half) {
+            sh[threadIdx.x][0] += sh[threadIdx.x + (half << tx_bits)][0];
+            sh[threadIdx.x][1] += sh[threadIdx.x + (half << tx_bits)][1];
+        }
+        __syncthreads();
+    }
+    if (ty == 0 && has0) {
+        double *dst = partial + (int64_t)blockIdx.x * nc + c;
+        dst[0] = sh[tx][0];
+        if (has1) dst[1] = sh[tx][1];
+    }
+}
+
+} // namespace
+
+// out_dev[j] = sum over the local rows of X[:, j]^2, j < nc <= 512 (no all-reduce, no host copy)
+int rails_colnorms2_dev(rails_ctx *c, const double *X, int ldx, int64_t m, int nc, double *out_dev)
+{
+    if (nc <= 0) return RAILS_OK;
+    if (m <= 0) {
+        RAILS_HIP_CHECK(hipMemsetAsync(out_dev, 0, (size_t)nc * sizeof(double), c->stream));
+        return RAILS_OK;
+    }
+    const int pairs = (nc + 1) / 2;
+    int tx_bits = 0;
+    while ((1 << tx_bits) < pairs) ++tx_bits; // <= 8: nc <= 512
+    const int TY = 256 >> tx_bits;
+    // slabs of at least 8 rows per thread, at most 1024 of them
+    int64_t nslab = std::max<int64_t>(1, std::min<int64_t>(1024, m / ((int64_t)TY * 8)));
+    const int64_t rps = (m + nslab - 1) / nslab;
+    nslab = (m + rps - 1) / rps;
+    RAILS_TRY(rails_ws_reserve(c, (size_t)nslab * nc * sizeof(double)));
+    const int vec_ok = ((((uintptr_t)X) & 15) == 0 && (ldx % 2) == 0) ? 1 : 0;
+    RAILS_LAUNCH(k_colnorms2, dim3((unsigned)nslab), dim3(256), 0, c->stream, X, ldx, nc, m, rps, tx_bits, vec_ok, c->ws);
+    RAILS_LAUNCH(k_reduce_partials, dim3((unsigned)((nc + 63) / 64)), dim3(1024), 0, c->stream, c->ws, nslab, (int64_t)nc, out_dev);
+    RAILS_HIP_CHECK(hipGetLastError());
+    return RAILS_OK;
+}
+
+extern "C" int rails_panel_colnorms2(rails_ctx *c, const rails_panel *X, int c0, int nc, double *out_host)
+{
+    if (c) hipSetDevice(c->device);
+    RAILS_REQUIRE(c && X, "rails_panel_colnorms2: null argument");
+    RAILS_REQUIRE(c0 >= 0 && nc >= 0 && c0 + nc <= X->cap, "rails_panel_colnorms2: window [%d,%d) outside capacity %d", c0, c0 + nc, X->cap);
+    RAILS_REQUIRE(nc == 0 || out_host, "rails_panel_colnorms2: null output buffer");
+    if (nc == 0) return RAILS_OK;
+    RAILS_TRY(rails_small_reserve(c, (size_t)nc * sizeof(double)));
+    RAILS_TRY(rails_pinned_reserve(c, (size_t)nc * sizeof(double)));
+    for (int j0 = 0; j0 < nc; j0 += 512) // every column is read once whatever nc
+        RAILS_TRY(rails_colnorms2_dev(c, X->d + c0 + j0, X->ld, X->m, std::min(512, nc - j0), c->small + j0));
+    RAILS_TRY(rails_allreduce_dev(c, c->small, (size_t)nc));
+    RAILS_HIP_CHECK(hipMemcpyAsync(c->pinned, c->small, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    RAILS_HIP_CHECK(rails_stream_sync(c));
+    memcpy(out_host, c->pinned, (size_t)nc * sizeof(double));
+    return RAILS_OK;
+}
+
 // ---- deferred small results --------------------------------------------------------------------------------------------------
 // The block orthogonalisation of the coordinate-space back end is a chain Gram -> update -> Gram -> Cholesky -> update ... whose small
 // matrices the host only needs for bookkeeping.  With these entry points the chain runs on the device without the host in between:

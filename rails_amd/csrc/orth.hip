@@ -17,6 +17,9 @@
 // projection round: [N | V_old] is one left operand, so a round is one Gram pass over W, one all-reduce and one update pass
 // (rails_gram2_dev, rails_panel_gemm2_dev).  With q = 0 it is rails_orthogonalize.
 //
+// rails_orthogonalize_range (further down) is the rank-revealing form for a start space: columns that may be dependent, any number of
+// them, dropped instead of replaced; it shares project_block with the two above and never takes their column-wise paths.
+//
 // This file is the algorithm only: every kernel it launches is in dense.hip, where the one- and two-segment forms share one body.
 #include "rails_internal.h"
 
@@ -301,7 +304,212 @@ int orthogonalize(rails_ctx *c, rails_panel *V, int k_old, int w, Nullspace cons
     return columnwise_in_block(c, V, k_old, w, ns);
 }
 
+// ---- rank-revealing range basis (rails_orthogonalize_range) --------------------------------------------------------------------------
+// The reference's Morth for a start space that may be rank deficient (matlab/RAILSsolver.m:567-580): every column is scaled to unit
+// length, projected twice against the nullspace and everything kept before it, and dropped when less than `tol` of it survives.  Here in
+// blocks of at most RANGE_BLOCK columns, with the block operations of orthogonalize() above and no per-column pass:
+//
+//   pre-scale   column norms of the block (rails_panel_colnorms2), W <- W diag(1 / norm), packed to the left at k_cur (zero columns go)
+//   project     twice W -= [N V(:, 0:k_cur)] ([N V]'W)                                                        (project_block)
+//   decide      G = W'W; Cholesky with the dependent pivots skipped (as repair_block); W <- W R^-1
+//   measure     a column skipped at the pivot test is not dropped yet: the Gram matrix cannot decide a residual of 1e-8, which is 1e-16 of
+//               its diagonal.  After W R^-1 such a column IS its residual against the independent columns before it; its norm (a second
+//               rails_panel_colnorms2) is the fraction of the unit length that survived.  Below tol: dropped.  Above: scaled back to unit
+//               length and the block goes round once more (the repair idea), which takes the column as an ordinary one.
+//   second CholQR round on what remains (after one more projection when the first round left a column less than 1e-2 of its length:
+//   its rounding error along [N V] was magnified by the inverse of that fraction).
+//
+// Every product that moves columns is ONE launch of k_panel_gemm (at most 256 output columns) reading and writing overlapping windows
+// of V: see apply_in_place.
+constexpr int RANGE_BLOCK = 128;
+
+// V[:, dst : dst + r) <- V[:, src : src + k) C (C host, k x r column-major, ld k), dst <= src, r <= 256, the windows may overlap.
+// In place this is safe only because a wave of k_panel_gemm reads all k columns of its 16 rows before it stores anything, and no other
+// wave touches those rows (dense_panel_gemm.inc: the accumulators are complete when the store loop starts; beta = 0 reads no Y).  So
+// the product stays inside one launch -- r <= 256 -- and goes through the internal entry point: rails_panel_gemm refuses partially
+// overlapping windows, rightly, for callers that cannot know this.
+int apply_in_place(rails_ctx *c, rails_panel *V, int src, int k, const std::vector<double> &C, int r, int dst)
+{
+    if (r == 0 || k == 0) return RAILS_OK;
+    const size_t bytes = (size_t)k * r * sizeof(double);
+    RAILS_TRY(rails_small_reserve(c, bytes));
+    RAILS_TRY(rails_pinned_begin_write(c, bytes)); // the upload does not make the host wait (as in rails_panel_gemm)
+    memcpy(c->pinned, C.data(), bytes);
+    RAILS_HIP_CHECK(hipMemcpyAsync(c->small, c->pinned, bytes, hipMemcpyHostToDevice, c->stream));
+    RAILS_TRY(rails_pinned_end_write(c));
+    c->n_orth_range_passes++;
+    return rails_panel_gemm_dev(c, 1.0, V->d + src, V->ld, k, c->small, r, 0.0, V->d + dst, V->ld, V->m);
+}
+
+// Cholesky of the n x n Gram matrix G with the dependent pivots skipped, as in repair_block: r_ii = 1 and row i of R zero beyond the
+// diagonal for a column i that keeps at most 1e-5 of its length against the independent columns before it (pivot <= 1e-10 G_ii), or
+// that has lost that much to the projection already (G_ii <= 1e-10: the column had unit length before it).  Returns R^-1; min_kept is
+// the smallest fraction an independent column keeps of the length it came with.
+std::vector<double> skipping_cholesky_inverse(const std::vector<double> &G, int n, std::vector<char> &grey, double *min_kept)
+{
+    std::vector<double> R((size_t)n * n, 0.0);
+    grey.assign(n, 0);
+    *min_kept = 1.0;
+    for (int i = 0; i < n; ++i) {
+        const double gii = G[i + (size_t)i * n];
+        double piv = gii;
+        for (int j = 0; j < i; ++j) {
+            if (grey[j]) continue;
+            double s = G[j + (size_t)i * n];
+            for (int l = 0; l < j; ++l)
+                if (!grey[l]) s -= R[l + (size_t)j * n] * R[l + (size_t)i * n];
+            s /= R[j + (size_t)j * n];
+            R[j + (size_t)i * n] = s;
+            piv -= s * s;
+        }
+        if (piv > 1e-10 * gii && gii > 1e-10 && std::isfinite(gii)) {
+            R[i + (size_t)i * n] = std::sqrt(piv);
+            *min_kept = std::min(*min_kept, std::sqrt(piv));
+        } else {
+            grey[i] = 1;
+            R[i + (size_t)i * n] = 1.0;
+            for (int j = 0; j < i; ++j)
+                if (!std::isfinite(R[j + (size_t)i * n])) R[j + (size_t)i * n] = 0.0;
+        }
+    }
+    return upper_inverse(R, n);
+}
+
+int gram_to_host(rails_ctx *c, rails_panel *V, int c0, int n, std::vector<double> &G)
+{
+    RAILS_TRY(rails_small_reserve(c, (size_t)n * n * sizeof(double)));
+    RAILS_TRY(rails_gram_dev(c, V->d + c0, V->ld, V->d + c0, V->ld, V->m, n, n, c->small));
+    RAILS_TRY(rails_allreduce_dev(c, c->small, (size_t)n * n));
+    c->n_orth_range_passes++;
+    c->n_orth_range_syncs++;
+    return sync_small_to_host(c, (size_t)n * n, G);
+}
+
+// One block: the wb columns from column src on become n <= wb orthonormal columns at k_cur <= src; idx receives their positions in the
+// block.  What lies between k_cur + n and src + wb is left as it is (the caller clears the tail once).
+int range_block(rails_ctx *c, rails_panel *V, int k_cur, int src, int wb, Nullspace const &ns, double tol, int *n_out, std::vector<int> &idx)
+{
+    std::vector<double> n2(wb);
+    RAILS_TRY(rails_panel_colnorms2(c, V, src, wb, n2.data()));
+    c->n_orth_range_passes++;
+    c->n_orth_range_syncs++;
+    idx.clear();
+    for (int i = 0; i < wb; ++i) {
+        if (n2[i] > 0.0 && std::isfinite(n2[i]))
+            idx.push_back(i);
+        else if (n2[i] != 0.0) // not finite: a zero coefficient does not silence such a column in the product below
+            RAILS_TRY(rails_panel_fill(c, V, src + i, 1, 0.0));
+    }
+    int n = (int)idx.size();
+    std::vector<double> C((size_t)wb * n, 0.0);
+    for (int j = 0; j < n; ++j) C[idx[j] + (size_t)j * wb] = 1.0 / std::sqrt(n2[idx[j]]);
+    RAILS_TRY(apply_in_place(c, V, src, wb, C, n, k_cur));
+    std::vector<double> kept_of_unit(n, 1.0); // the fraction of its unit length each column still stands for
+    int project = 2, clean_rounds = 0;
+    // a round with grey columns multiplies the fraction of each by at most 1e-5 or drops it, so the rounds are bounded by tol
+    for (int round = 0; n > 0 && clean_rounds < 2; ++round) {
+        if (round > 40) {
+            rails_set_error("rails_orthogonalize_range: the rank decision of a block did not settle");
+            return RAILS_ELAPACK;
+        }
+        for (int pass = 0; pass < project; ++pass) {
+            RAILS_TRY(project_block(c, V, k_cur, n, ns));
+            if (ns.q + k_cur > 0) c->n_orth_range_passes += 2;
+        }
+        std::vector<double> G;
+        RAILS_TRY(gram_to_host(c, V, k_cur, n, G));
+        std::vector<char> grey;
+        double min_kept = 1.0;
+        const std::vector<double> Rinv = skipping_cholesky_inverse(G, n, grey, &min_kept);
+        RAILS_TRY(apply_in_place(c, V, k_cur, n, Rinv, n, k_cur));
+        int n_grey = 0;
+        for (int i = 0; i < n; ++i) n_grey += grey[i];
+        if (n_grey == 0) {
+            ++clean_rounds;
+            project = min_kept < 1e-2 ? 1 : 0;
+            continue;
+        }
+        // second stage of the rank decision: the grey columns now hold their residuals
+        n2.assign(n, 0.0);
+        RAILS_TRY(rails_panel_colnorms2(c, V, k_cur, n, n2.data()));
+        c->n_orth_range_passes++;
+        c->n_orth_range_syncs++;
+        std::vector<int> stay;
+        std::vector<double> scale;
+        for (int i = 0; i < n; ++i) {
+            if (!grey[i]) {
+                stay.push_back(i);
+                scale.push_back(1.0);
+                continue;
+            }
+            const double res = std::sqrt(n2[i]);
+            if (!std::isfinite(res)) RAILS_TRY(rails_panel_fill(c, V, k_cur + i, 1, 0.0)); // (as above)
+            if (!(res > 0.0) || !std::isfinite(res) || !(kept_of_unit[i] * res >= tol)) continue;
+            kept_of_unit[i] *= res;
+            stay.push_back(i);
+            scale.push_back(1.0 / res);
+        }
+        const int n_new = (int)stay.size();
+        std::vector<double> S((size_t)n * n_new, 0.0);
+        std::vector<int> idx_new(n_new);
+        std::vector<double> kept_new(n_new);
+        for (int j = 0; j < n_new; ++j) {
+            S[stay[j] + (size_t)j * n] = scale[j];
+            idx_new[j] = idx[stay[j]];
+            kept_new[j] = kept_of_unit[stay[j]];
+        }
+        RAILS_TRY(apply_in_place(c, V, k_cur, n, S, n_new, k_cur));
+        idx.swap(idx_new);
+        kept_of_unit.swap(kept_new);
+        n = n_new;
+        project = 2;
+        clean_rounds = 0;
+    }
+    idx.resize(n);
+    *n_out = n;
+    return RAILS_OK;
+}
+
+int orthogonalize_range(rails_ctx *c, rails_panel *V, int k_old, int w, Nullspace const &ns, double tol, int *kept, int32_t *kept_idx)
+{
+    c->n_orth_range++;
+    int k_cur = k_old;
+    std::vector<int> idx;
+    for (int b0 = 0; b0 < w; b0 += RANGE_BLOCK) {
+        const int wb = std::min(RANGE_BLOCK, w - b0);
+        int n = 0;
+        RAILS_TRY(range_block(c, V, k_cur, k_old + b0, wb, ns, tol, &n, idx));
+        if (kept_idx)
+            for (int j = 0; j < n; ++j) kept_idx[k_cur - k_old + j] = (int32_t)(b0 + idx[j]);
+        k_cur += n;
+    }
+    *kept = k_cur - k_old;
+    if (k_cur < k_old + w) RAILS_TRY(rails_panel_fill(c, V, k_cur, k_old + w - k_cur, 0.0));
+    return RAILS_OK;
+}
+
 } // namespace
+
+extern "C" int rails_orthogonalize_range(rails_ctx *c, rails_panel *V, int k_old, int w, const rails_panel *N, int nc0, int q, double tol,
+                                         int *kept, int32_t *kept_idx)
+{
+    if (c) hipSetDevice(c->device);
+    RAILS_REQUIRE(c && V && kept && (q == 0 || N), "rails_orthogonalize_range: null argument");
+    RAILS_REQUIRE(k_old >= 0 && w >= 0 && k_old + w <= V->cap, "rails_orthogonalize_range: columns [%d,%d) outside capacity %d", k_old, k_old + w,
+                  V->cap);
+    RAILS_REQUIRE(q >= 0 && (q == 0 || (nc0 >= 0 && nc0 + q <= N->cap)), "rails_orthogonalize_range: nullspace columns [%d,%d) outside capacity %d",
+                  nc0, nc0 + q, q ? N->cap : 0);
+    RAILS_REQUIRE(q == 0 || N->m == V->m, "rails_orthogonalize_range: the nullspace has %lld rows, V %lld", q ? (long long)N->m : 0LL,
+                  (long long)V->m);
+    RAILS_REQUIRE(q == 0 || (N != V && N->d != V->d), "rails_orthogonalize_range: the nullspace must be a panel of its own");
+    *kept = 0;
+    if (w == 0) return RAILS_OK;
+    Nullspace ns;
+    ns.N = N;
+    ns.c0 = nc0;
+    ns.q = q;
+    return orthogonalize_range(c, V, k_old, w, ns, tol > 0.0 ? tol : 1e-8, kept, kept_idx);
+}
 
 extern "C" int rails_orthogonalize(rails_ctx *c, rails_panel *V, int k_old, int w, int method, int *used)
 {

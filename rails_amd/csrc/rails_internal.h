@@ -93,6 +93,7 @@ struct rails_ctx {
     // counters (rails_ctx_stats)
     void *lz = nullptr; // rails_lanczos_state (lanczos.hip), released by rails_lanczos_release
     long n_orth_block = 0, n_orth_columnwise = 0, n_spmm_tiled = 0, n_spmm_planes = 0, n_spmm_overlapped = 0, n_spmm_sweep = 0, n_spmm_rowgather = 0, n_spmm_callback = 0, n_dev_alloc = 0, n_allreduce = 0, n_lanczos = 0, n_lanczos_start = 0, n_orth_repair = 0, n_update_gram_fused = 0, n_rowquad = 0;
+    long n_orth_range = 0, n_orth_range_passes = 0, n_orth_range_syncs = 0; // rails_orthogonalize_range: calls, passes over a block of columns, host synchronisations
 };
 
 // the busy meter (see rails_ctx): RAILS_LAUNCH brackets a launch, rails_stream_sync reads what has been bracketed since the last one
@@ -285,6 +286,8 @@ int rails_gram_dev(rails_ctx *ctx, const double *X, int ldx, const double *Y, in
                    double *C_dev);
 int rails_panel_gemm_dev(rails_ctx *ctx, double alpha, const double *X, int ldx, int k, const double *C_dev,
                          int r, double beta, double *Y, int ldy, int64_t m);
+// dense.hip: local column sums of squares of nc <= 512 columns into device memory (no all-reduce, no host copy)
+int rails_colnorms2_dev(rails_ctx *ctx, const double *X, int ldx, int64_t m, int nc, double *out_dev);
 // the same with the left operand in two panels, [X1 X2] with a1 + a2 columns (b, r <= 32; Y += alpha [X1 X2] C)
 int rails_gram2_dev(rails_ctx *ctx, const double *X1, int ldx1, int a1, const double *X2, int ldx2, int a2, const double *Y, int ldy, int64_t m,
                     int b, double *C_dev);

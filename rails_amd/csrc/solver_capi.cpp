@@ -61,6 +61,9 @@ struct rails_solver {
     bool subspace = true, verbose = true, projected = false; // default: coordinate-space back end where applicable (M = I, cold start)
     int max_trips = 0;
     bool have_V0 = false;
+    rails::HipMultiVectorWrapper start; // rails_solver_set_start_space: the raw start space of the next solve (a device copy)
+    bool have_start = false;
+    int start_rank = 0;
     bool last_was_subspace = false;
     int sub_trips = 0;
     std::vector<double> sub_hist;
@@ -268,8 +271,37 @@ extern "C" int rails_solver_set_V(rails_solver *s, const double *V_host, int64_t
     s->V.from_host(V_host, ldv);
     s->V.set_orthogonalized(k); // the caller's V is assumed orthonormal
     s->have_V0 = true;
+    s->have_start = false;
+    s->start = rails::HipMultiVectorWrapper();
     return RAILS_OK;
 }
+
+extern "C" int rails_solver_set_start_space(rails_solver *s, const rails_panel *P, int c0, int k)
+{
+    if (!s || !P) {
+        rails_set_error("rails_solver_set_start_space: null argument");
+        return RAILS_EINVAL;
+    }
+    if (k < 1 || c0 < 0 || c0 + k > rails_panel_capacity(P)) {
+        rails_set_error("rails_solver_set_start_space: columns [%d,%d) of a panel of capacity %d", c0, c0 + k, rails_panel_capacity(P));
+        return RAILS_EINVAL;
+    }
+    if (rails_panel_rows(P) != s->m_local) {
+        rails_set_error("rails_solver_set_start_space: the panel has %lld rows, the solver %lld local rows", (long long)rails_panel_rows(P),
+                        (long long)s->m_local);
+        return RAILS_EINVAL;
+    }
+    rails::HipMultiVectorWrapper W(s->m_local, k, s->ctx);
+    W.set_global_rows(s->m_global);
+    const int rc = rails_panel_copy(s->ctx, P, c0, k, W.panel(), 0); // device to device
+    if (rc != RAILS_OK) return rc;
+    s->start = W;
+    s->have_start = true;
+    s->have_V0 = false;
+    return RAILS_OK;
+}
+
+extern "C" int rails_solver_start_rank(rails_solver *s) { return s ? s->start_rank : -1; }
 
 // the same solve on the coordinate-space back end: B and every later vector are expressed in one orthonormal device basis
 static int solve_in_coordinates(rails_solver *s)
@@ -279,7 +311,7 @@ static int solve_in_coordinates(rails_solver *s)
     const int expand = s->params.get("Expand size", 3);
     rails::HipSolver::Projection proj;
     const bool pair = rails::HipSolver::parse_projection(s->params.get("Projection method", 1.0), proj) && proj.pair; // 2.x: twice per trip
-    const int kmax = std::max(restart > 0 ? restart : 100, 1) + (pair ? 2 : 1) * expand + 100;
+    const int kmax = std::max(restart > 0 ? restart : 100, 1) + (pair ? 2 : 1) * expand + 100 + (s->have_start ? s->start.N() : 0);
     auto basis = std::make_shared<rails::SubspaceBasis>(s->ctx, s->m_local, s->m_global, 2 * kmax + p + 128);
     if (restart > 0 || s->params.get("Restart iterations", 20) > 0) basis->preallocate_compress_panel(); // restarts will re-base the basis
     rails::SubspaceMultiVector Bc = rails::SubspaceMultiVector::Absorb(basis, s->B);
@@ -288,7 +320,9 @@ static int solve_in_coordinates(rails_solver *s)
     rails::SubspaceSolver solver(Ac, Bc, Mc);
     if (s->has_inv) solver.set_inverse(rails::SubspaceOperator(s->Ainv, basis));
     if (s->null_q > 0) solver.set_nullspace(rails::SubspaceMultiVector::Absorb(basis, s->N)); // the one absorb of N: a live store from then on
-    int prc = solver.set_parameters(s->params);
+    ParameterList params = s->params;
+    if (s->have_start) params.set("Restart from solution", 1.0); // a start space makes a warm start whatever the parameter says
+    int prc = solver.set_parameters(params);
     if (prc != 0) return prc + 100;
     solver.set_verbose(s->verbose);
     solver.set_max_trips(s->max_trips);
@@ -301,8 +335,23 @@ static int solve_in_coordinates(rails_solver *s)
         Vc = rails::SubspaceMultiVector::Absorb(basis, s->V);
         Vc.set_orthogonalized(Vc.N());
     }
+    if (s->have_start) { // opts.space: orthonormalised on the device with dependent columns dropped, then absorbed like the warm start's V
+        if (s->start.orthogonalize_range(nullptr, 0.0) < 1) {
+            if (rails::sticky_error() == RAILS_OK) std::cerr << "rails::Solver: no column of the start space is left after orthonormalisation" << std::endl;
+            return -2;
+        }
+        // A start space that is a converged solution holds B to within the tolerance: projected against B's basis columns the block keeps
+        // every column's length but loses rank, which is not what the overlapped orthogonalisation predicts from -- absorbed the
+        // waiting way, where every block is decided before the next step
+        const bool overlap = basis->overlap;
+        basis->overlap = false;
+        Vc = rails::SubspaceMultiVector::Absorb(basis, s->start);
+        basis->overlap = overlap;
+        Vc.set_orthogonalized(Vc.N());
+    }
     int rc = solver.solve(Vc, s->T);
     s->null_rank = solver.nullspace_rank();
+    s->start_rank = solver.start_rank();
     if (rc == -2) return rc; // refused before the first trip: V and T stay as they were
     s->V = Vc.materialise();
     s->V.set_orthogonalized(s->V.N());
@@ -328,7 +377,8 @@ extern "C" int rails_solver_solve(rails_solver *s, int *code, int *k)
     const bool restart_from_solution = s->params.get("Restart from solution", 0.0) != 0.0;
     // a warm start needs the caller's V; "Restart from solution" without one is the direct back end's business (it starts from
     // the single column the solver object holds, like the reference)
-    s->last_was_subspace = s->subspace && !s->sprhs && (s->have_V0 || !restart_from_solution);
+    // (a raw start space together with a nullspace: the direct back end, whose orthonormalisation projects the nullspace out as it goes)
+    s->last_was_subspace = s->subspace && !s->sprhs && (s->have_V0 || s->have_start || !restart_from_solution) && !(s->have_start && s->null_q > 0);
     { // the projection method: a valid value (rails_solver_apply_parameters reports it) with the inverse it needs
         rails::HipSolver::Projection proj;
         const double method = s->params.get("Projection method", 1.0);
@@ -347,9 +397,36 @@ extern "C" int rails_solver_solve(rails_solver *s, int *code, int *k)
         if (s->last_was_subspace) {
             rc = solve_in_coordinates(s);
             if (rc == -1000) return RAILS_EHIP;
+        } else if (s->have_start) { // on the start space's own copy: a refused solve leaves V and T as they were
+            const bool was_warm = s->solver->settings().warm_start;
+            struct Restore { // also when the parameters are refused or the solve throws
+                rails_solver *s;
+                bool warm; // (a parameter that is not in the list keeps its current value: put the former one back by name)
+                ~Restore()
+                {
+                    ParameterList back = s->params;
+                    back.set("Restart from solution", warm ? 1.0 : 0.0);
+                    s->solver->set_raw_start_space(false);
+                    s->solver->set_parameters(back);
+                }
+            } restore{s, was_warm};
+            ParameterList params = s->params;
+            params.set("Restart from solution", 1.0);
+            const int prc = s->solver->set_parameters(params);
+            if (prc != 0) {
+                rails_set_error("rails_solver_solve: the parameters are not valid (code %d, rails_solver_apply_parameters)", prc);
+                return RAILS_EINVAL;
+            }
+            s->solver->set_raw_start_space(true);
+            rails::HipMultiVectorWrapper Vs = s->start;
+            rc = s->solver->solve(Vs, s->T);
+            s->null_rank = s->solver->nullspace_rank();
+            s->start_rank = s->solver->start_rank();
+            if (rc != -2) s->V = Vs;
         } else {
             rc = s->solver->solve(s->V, s->T);
             s->null_rank = s->solver->nullspace_rank();
+            s->start_rank = s->solver->start_rank();
         }
     } catch (std::bad_alloc const &) {
         rails_set_error("rails_solver_solve: out of host memory");
@@ -358,6 +435,8 @@ extern "C" int rails_solver_solve(rails_solver *s, int *code, int *k)
         rails_set_error("rails_solver_solve: %s", e.what());
         return RAILS_EINVAL;
     }
+    s->have_start = false; // one solve consumes the start space
+    s->start = rails::HipMultiVectorWrapper();
     s->have_V0 = false; // V now holds the result; a later warm start passes its V again (or runs on the direct back end)
     if (code) *code = rc;
     if (k) *k = s->V.N();

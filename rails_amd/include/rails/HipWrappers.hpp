@@ -449,6 +449,28 @@ public:
         orthogonalized_ = n_;
     }
 
+    // columns [watermark, N), which need be neither orthonormal nor independent, replaced by an orthonormal basis of their range, in column
+    // order, against the orthonormal columns of N (null: none) and the columns before the watermark (rails_orthogonalize_range: a column of
+    // which less than tol survives is dropped; tol <= 0: 1e-8).  The object shrinks to the columns kept, all of them orthogonalised
+    // then; returns how many of the new columns were kept (-1 with a message when the call cannot be made).
+    int orthogonalize_range(HipMultiVectorWrapper const *N = nullptr, double tol = 0.0)
+    {
+        const bool with_N = N && N->n_ > 0;
+        if (replicated_ || !panel_ || c0_ != 0 || (with_N && (N->replicated_ || !N->panel_))) {
+            std::cerr << "rails_amd: orthogonalize_range() needs distributed multivectors, this one starting at column 0" << std::endl;
+            return -1;
+        }
+        int kept = 0;
+        if (n_ > orthogonalized_ &&
+            !hip_ok(rails_orthogonalize_range(ctx_, panel_->p, orthogonalized_, n_ - orthogonalized_, with_N ? N->panel_->p : nullptr, with_N ? N->c0_ : 0,
+                                              with_N ? N->n_ : 0, tol, &kept, nullptr),
+                    "rails_orthogonalize_range"))
+            return -1;
+        n_ = orthogonalized_ + kept;
+        orthogonalized_ = n_;
+        return kept;
+    }
+
     // diag(this * S * this') as an m x 1 multivector: the one-pass kernel of solution.hip (rails::Solution::variance picks it up)
     HipMultiVectorWrapper rowquad(HostDenseMatrix const &S) const
     {

@@ -76,6 +76,67 @@ void orthogonalize_deflated(MultiVector &V, MultiVector const &N, int first, std
     }
 }
 
+// Whether a MultiVector offers `int orthogonalize_range(MultiVector const *N, double tol)`: ALL its columns, which need be neither
+// orthonormal nor independent, replaced by an orthonormal basis of their range with N (orthonormal columns; null: none) projected out,
+// in column order; the object is resized to the columns kept, marks them orthogonalised and returns their number.
+template <class MultiVector, class = void>
+struct has_range_orthogonalize : std::false_type {
+};
+template <class MultiVector>
+struct has_range_orthogonalize<MultiVector,
+                               decltype(std::declval<MultiVector &>().orthogonalize_range(std::declval<MultiVector const *>(), std::declval<double>()), void())>
+    : std::true_type {
+};
+
+// `V = Morth(V0, [], nullspace, [])` for a start space V0 = opts.space (matlab/RAILSsolver.m:160-204,310-314,567-580): every column is
+// scaled to unit length, loses -- twice -- its part along N and along the columns kept before it, and is dropped when less than `tol` of
+// it survives (a column of norm zero, or not finite, is dropped too); the later columns move up.  Returns the columns kept.
+// A back end with the member does it itself; any other goes through the contract, column by column, like Solver::prepare_nullspace.  The
+// contract moves a watermark only in orthogonalize(), so the generic form ends with one such call on the columns it kept: they are
+// orthonormal by then and stay what they are up to rounding.
+template <class MultiVector>
+int orthogonalize_range(MultiVector &V, MultiVector const *N, double tol, std::true_type)
+{
+    const int n = V.N();
+    V.resize(0); // from column 0 (the contract's resize keeps the data: this only moves the watermark)
+    V.resize(n);
+    return V.orthogonalize_range(N, tol);
+}
+template <class MultiVector>
+int orthogonalize_range(MultiVector &V, MultiVector const *N, double tol, std::false_type)
+{
+    int n = V.N(), j = 0;
+    while (j < n) {
+        MultiVector v = V.view(j);
+        const double n0 = v.norm();
+        double nrm = 0.0;
+        if (n0 > 0.0 && std::isfinite(n0)) {
+            v /= n0;
+            for (int pass = 0; pass < 2; ++pass) {
+                if (N) v -= *N * N->dot(v);
+                if (j > 0) {
+                    MultiVector const before = V.view(0, j - 1);
+                    v -= before * before.dot(v);
+                }
+            }
+            nrm = v.norm();
+        }
+        if (!(nrm >= tol)) { // nothing new in this column: the later ones move up
+            for (int l = j + 1; l < n; ++l) V.view(l - 1) = V.view(l);
+            V.resize(--n);
+            continue;
+        }
+        v /= nrm;
+        ++j;
+    }
+    if (n > 0) {
+        V.resize(0); // (the watermark goes back to the first column)
+        V.resize(n);
+        V.orthogonalize();
+    }
+    return n;
+}
+
 // The right-hand side factor B, given either as an operator (Matrix) or as a tall panel (MultiVector) -- the two forms the
 // reference accepts through its B adaptor (src/MatrixOrMultiVectorWrapper.hpp:7-98).  Both members exist (the contract asks
 // for default-constructible types, :11-12); `kind_` says which one is in use.
@@ -236,6 +297,7 @@ public:
         double keep_above = 1e-3 * 1e-3;  // "Restart tolerance": |eigenvalue of T| a kept direction must exceed (absolute, :471)
         bool shrink_on_convergence = true; // "Minimize solution space"
         bool warm_start = false;          // "Restart from solution": V holds an orthonormal basis to continue from
+        bool shrink_at_start = false;     // "Restart upon start": shrink right after the first projected solve (opts.restart_upon_start)
         double projection_method = 1.0;   // "Projection method": opts.projection_method of matlab/RAILSsolver.m:7-16 (see projection())
     };
 
@@ -287,6 +349,7 @@ public:
         s.keep_above = lookup_parameter(params, "Restart tolerance", s.tolerance * 1e-3); // default follows the tolerance (:84)
         s.shrink_on_convergence = lookup_parameter(params, "Minimize solution space", s.shrink_on_convergence);
         s.warm_start = lookup_parameter(params, "Restart from solution", s.warm_start);
+        s.shrink_at_start = lookup_parameter(params, "Restart upon start", s.shrink_at_start);
         const double method = lookup_parameter(params, "Projection method", s.projection_method);
         Projection unused;
         if (!parse_projection(method, unused)) {
@@ -334,6 +397,14 @@ public:
     bool has_nullspace() const { return has_nullspace_; }
     // columns of the nullspace the last solve kept (0 without one)
     int nullspace_rank() const { return null_rank_; }
+    // opts.space of matlab/RAILSsolver.m:25-28,160-204,310-314: with "Restart from solution" the caller's V is ANY start space -- a previous
+    // solution's V, [V_prev, B], the union of two earlier solutions -- neither orthonormal nor independent.  The solve orthonormalises it
+    // from column 0 with the nullspace projected out and drops every column of which less than 1e-8 survives (orthogonalize_range above;
+    // m_orthogonalize under mass_orthogonalisation()); it is refused (-2, V and T unchanged) when no column survives.
+    void set_raw_start_space(bool on) { raw_start_ = on; }
+    bool raw_start_space() const { return raw_start_; }
+    // columns the last solve kept of its start space (1 after a cold start)
+    int start_rank() const { return start_rank_; }
     void set_verbose(bool on) { verbose_ = on; }
     void set_max_trips(int n) { trip_budget_ = n; }
     // residual Lanczos carried in the (2k+p+1)-dimensional coefficient space where the backend supports it
@@ -356,7 +427,7 @@ public:
     // Low-rank solution X = V T V' of A X + X A' + B B' = 0 (A X M' + M X A' + B B' = 0 with a mass matrix)   (src/LyapunovSolver.hpp:100-346)
     // A projection method other than 1 needs set_inverse(), and one that starts from B (x.2) needs B as a multivector: then the
     // solve is refused (-2) and V, T are left as they are.  So is a nullspace (set_nullspace) with a row count other than A's, with no
-    // independent column, or with as many as the problem has dimensions.
+    // independent column, or with as many as the problem has dimensions; and a raw start space (set_raw_start_space) without one.
     int solve(MultiVector &V, DenseMatrix &T)
     {
         null_rank_ = 0;
@@ -571,7 +642,7 @@ private:
 
         int go()
         {
-            open();
+            if (!open()) return -2;
             // RAILS_SOLVER_TRIP_TRACE=x: after every trip that took more than x ms, its time per section on stderr
             static const double trace_ms = getenv("RAILS_SOLVER_TRIP_TRACE") ? atof(getenv("RAILS_SOLVER_TRIP_TRACE")) : 0.0;
             std::map<std::string, double> before;
@@ -623,11 +694,14 @@ private:
 
     private:
         // Room for min(shrink_at or 100, n) columns (:106); a cold start draws one random unit vector (:110-114), a warm start keeps
-        // the caller's columns (:116-121).
-        void open()
+        // the caller's columns (:116-121) -- orthonormalised with rank detection first when they are a raw start space.  False: the
+        // solve is refused (no column of the raw start space survived); V is as it was.
+        bool open()
         {
             s_.trips_ = 0;
             s_.estimates_.clear();
+            s_.start_rank_ = 0;
+            if (opt_.warm_start && s_.raw_start_ && !orthonormalise_start_space()) return false;
             capacity_ = std::max(V_.N(), std::min(opt_.shrink_at > 0 ? opt_.shrink_at : 100, n_));
             if (!opt_.warm_start) {
                 V_.resize(capacity_);
@@ -639,7 +713,7 @@ private:
                     orthogonalize(0);
             } else {
                 if (V_.N() != capacity_) reserve_columns(V_, capacity_);
-                if (deflating()) { // the caller's V loses its part along the nullspace like any start space (matlab/RAILSsolver.m:311-313)
+                if (deflating() && !s_.raw_start_) { // the caller's V loses its part along the nullspace like any start space (matlab/RAILSsolver.m:311-313)
                     if (s_.mass_orthogonalisation())
                         m_orthogonalize(0);
                     else
@@ -648,6 +722,7 @@ private:
             }
             const Projection proj = s_.projection();
             if (proj.uses_inverse() && proj.start != 3) open_with_inverse(proj);
+            s_.start_rank_ = V_.N();
             fresh_ = MultiVector(V_); // a deep copy: every column is still to be multiplied (:123)
             AV_ = MultiVector(V_, capacity_);
             AV_.resize(0);
@@ -661,6 +736,24 @@ private:
             const double nb = s_.rhs_.norm2();
             scale_ = nb * nb;
             s_.scale_ = scale_;
+            return true;
+        }
+
+        // The caller's V as a raw start space, orthonormalised in place; a copy taken first is what V goes back to when the solve is refused.
+        bool orthonormalise_start_space()
+        {
+            MultiVector const saved(V_);
+            int kept = 0;
+            if (s_.mass_orthogonalisation())
+                kept = m_orthogonalize(0);
+            else
+                kept = orthogonalize_range(V_, deflating() ? &s_.null_basis_ : (MultiVector const *)nullptr, 1e-8, has_range_orthogonalize<MultiVector>());
+            if (kept < 1) {
+                std::cerr << "rails::Solver: no column of the start space is left after orthonormalisation" << std::endl;
+                V_ = saved;
+                return false;
+            }
+            return true;
         }
 
         // The start space of methods x.1 and x.2 (matlab/RAILSsolver.m:288-314): V0 (the columns open() made, x.1) or B (x.2), then
@@ -801,7 +894,10 @@ private:
         // by size, by trips since the last shrink, or on (first) convergence (:245-247)
         bool shrink_due(bool converged) const
         {
-            return (opt_.shrink_at > 0 && V_.N() >= opt_.shrink_at) || (opt_.shrink_every > 0 && trip_ - last_shrink_ >= opt_.shrink_every) || converged;
+            // opts.restart_upon_start (matlab/RAILSsolver.m:53-57,455): the first trip of a start space of more than one column ends in a
+            // shrink.  (A single column -- every cold start -- has nothing to give up, and a shrink would only cost it a trip.)
+            const bool at_start = opt_.shrink_at_start && trip_ == 0 && V_.N() > 1;
+            return at_start || (opt_.shrink_at > 0 && V_.N() >= opt_.shrink_at) || (opt_.shrink_every > 0 && trip_ - last_shrink_ >= opt_.shrink_every) || converged;
         }
 
         // V <- V X with X the dominant eigenvectors of T; everything expressed in V follows (:263-298, matlab/RAILSsolver.m:499-504).
@@ -957,6 +1053,8 @@ protected:
 
     bool mass_ = false;
     bool ortho_m_ = false;
+    bool raw_start_ = false;
+    int start_rank_ = 0;
     bool verbose_ = true;
     int trip_budget_ = 0;
     int trips_ = 0;

@@ -1,7 +1,7 @@
 """Command-line driver: solve A X M' + M X A' + B B' = 0 for X = V T V' with matrices from MatrixMarket files.
 
     python -m rails_amd.main [params.xml] [--dir DIR] [--A A.mtx] [--B B.mtx] [--M M.mtx] [--V V.mtx] [--T T.mtx]
-                               [--eigs K] [--variance FILE] [--sparse-B]
+                               [--eigs K] [--variance FILE] [--sparse-B] [--warm-start V.mtx | --start-space S.mtx] [--restart-upon-start]
     python -m torch.distributed.run --nproc-per-node N -m rails_amd.main ...      (one rank per GPU, rows partitioned)
 
 File names, formats and the parameter file follow the reference's driver (src/main.cpp:57-68,111,123-126): `A.mtx`, `B.mtx`
@@ -44,6 +44,10 @@ def main(argv=None):
     ap.add_argument("--V", default="V.mtx")
     ap.add_argument("--T", default="T.mtx")
     ap.add_argument("--warm-start", default=None, help="V.mtx of a previous solve (orthonormal columns): sets 'Restart from solution'")
+    ap.add_argument("--start-space", default=None, metavar="FILE.mtx", help="a raw start space (opts.space): any columns -- a previous V, [V, B], several "
+                                                                            "solutions side by side; orthonormalised on the device, dependent columns dropped")
+    ap.add_argument("--restart-upon-start", action="store_true", help="shrink the space right after the first projected solve (opts.restart_upon_start; "
+                                                                      "'Restart upon start' in the parameter file)")
     ap.add_argument("--set", action="append", default=[], metavar="NAME=VALUE", help="override one solver parameter, e.g. --set 'Tolerance=1e-6'")
     ap.add_argument("--nullspace", default=None, help="N.mtx (dense array): a space projected out of the solution space (opts.nullspace), "
                                                       "with the rows of the equation solved (the Schur rows after a Schur reduction)")
@@ -80,6 +84,12 @@ def main(argv=None):
     for kv in args.set:
         k, _, v = kv.partition("=")
         params[k.strip()] = float(v)
+    if "restart_upon_start" in params:  # the reference's (MATLAB) spelling
+        params["Restart upon start"] = params.pop("restart_upon_start")
+    if args.restart_upon_start:
+        params["Restart upon start"] = 1
+    if args.start_space and args.warm_start:
+        raise SystemExit("--start-space and --warm-start: give one of them")
 
     _log(rank, "Loading matrices")
     t0 = time.time()
@@ -104,6 +114,7 @@ def main(argv=None):
             raise SystemExit("M must be %d x %d" % (m, m))
         Mcsr = (mrp, mcol, mval)
     V0 = mmio.read_dense(path(args.warm_start)) if args.warm_start else None
+    S0 = mmio.read_dense(path(args.start_space)) if args.start_space else None
     Nsp = mmio.read_dense(path(args.nullspace)) if args.nullspace else None
     if V0 is not None:
         params["Restart from solution"] = 1
@@ -153,6 +164,8 @@ def main(argv=None):
                 B = schur.restrict(B)
             if V0 is not None and V0.shape[0] == m:
                 V0 = V0[schur.idx2]
+            if S0 is not None and S0.shape[0] == m:
+                S0 = S0[schur.idx2]
             d2 = schur.mass22
             Mcsr = None if np.all(d2 == 1.0) else (np.arange(schur.m2 + 1, dtype=np.int64), np.arange(schur.m2, dtype=np.int64), d2)
             m = schur.m2
@@ -197,6 +210,10 @@ def main(argv=None):
         solver.set_inverse(inverse)
         _log(rank, "Projection method %g: A^-1 is %s; nnz(L+U) %d, factorised in %.2f s" % (method, what, inverse.nnz, time.time() - t0))
 
+    if S0 is not None:
+        if S0.shape[0] != m:
+            raise SystemExit("--start-space: %d rows, the equation solved has %d" % (S0.shape[0], m))
+        solver.set_start_space(S0[r0:r1])  # uploaded once; each rank its own rows
     _log(rank, "Performing solve")
     ctx.sync()
     t0 = time.perf_counter()
@@ -209,6 +226,8 @@ def main(argv=None):
     _log(rank, "solve returned %d after %d iterations in %.3f s: V is %d x %d, relative residual %.3e" % (code, solver.trips(), dt, m, solver.k, rel))
     if Nsp is not None:
         _log(rank, "nullspace: %d of %d columns kept" % (solver.nullspace_rank, Nsp.shape[1]))
+    if S0 is not None:
+        _log(rank, "start space: %d of %d columns kept" % (solver.start_rank, S0.shape[1]))
     if world > 1:
         parts = [None] * world
         dist.all_gather_object(parts, V)

@@ -74,6 +74,29 @@ class Solver:
         """columns of the nullspace the last solve kept after orthonormalisation (0 without one)"""
         return self.lib.rails_solver_nullspace_rank(self.h)
 
+    def set_start_space(self, X):
+        """opts.space of matlab/RAILSsolver.m:25-28: the columns of X -- a HipMultiVectorWrapper, a Solution (its device factor, no host
+        round trip) or a host array (uploaded once) -- become the start space of the next solve.  They need not be orthonormal or
+        independent; the solve orthonormalises them, drops dependent columns and projects the nullspace out.  The next solve is a warm
+        start whatever "Restart from solution" says, and consumes the space.  See include/rails_solver.h."""
+        from .solution import Solution
+        from .wrappers import HipMultiVectorWrapper
+
+        if isinstance(X, Solution):
+            c0 = C.c_int(0)
+            panel = self.lib.rails_solution_panel(X.h, C.byref(c0))
+            c0, k = c0.value, self.lib.rails_solution_rank(X.h)
+        else:
+            if not isinstance(X, HipMultiVectorWrapper):
+                X = HipMultiVectorWrapper(self.ctx, data=X)
+            panel, c0, k = X.panel.h, X.c0, X.n
+        check(self.lib.rails_solver_set_start_space(self.h, panel, c0, k), "rails_solver_set_start_space")
+
+    @property
+    def start_rank(self):
+        """columns the last solve kept of its start space (1 after a cold start)"""
+        return self.lib.rails_solver_start_rank(self.h)
+
     def set_trip_callback(self, fn):
         if fn is None:
             self._cb = None

@@ -332,6 +332,30 @@ class HipMultiVectorWrapper:
         self.orthogonalized = self.n
         return used.value
 
+    def colnorms2(self):
+        """the column sums of squares, one pass over the window on the device (rails_panel_colnorms2); two calls agree bit for bit"""
+        out = np.zeros(max(self.n, 1))
+        check(self.ctx.lib.rails_panel_colnorms2(self.ctx.h, self.panel.h, self.c0, self.n, _p(out)), "rails_panel_colnorms2")
+        return out[:self.n]
+
+    def orthogonalize_range(self, N=None, tol=0.0):
+        """The columns past the watermark, which need be neither orthonormal nor independent, replaced by an orthonormal basis of their
+        range in column order, against the orthonormal columns of N (another multivector; None: none) and the columns before the
+        watermark; a column of which less than tol (<= 0: 1e-8) survives is dropped (rails_orthogonalize_range).  The object shrinks to
+        the columns kept.  Returns (kept, kept_idx): their number and their positions among the new columns."""
+        if self.c0 != 0:
+            raise _lib.RailsError("orthogonalize_range on a view that does not start at column 0 is not supported")
+        k0 = self.orthogonalized
+        w = self.n - k0
+        kept = C.c_int(0)
+        idx = np.zeros(max(w, 1), dtype=np.int32)
+        q = N.n if N is not None else 0
+        check(self.ctx.lib.rails_orthogonalize_range(self.ctx.h, self.panel.h, k0, w, N.panel.h if q else None, N.c0 if q else 0, q, float(tol),
+                                                     C.byref(kept), idx.ctypes.data_as(C.POINTER(C.c_int32))), "rails_orthogonalize_range")
+        self.n = k0 + kept.value
+        self.orthogonalized = self.n
+        return kept.value, idx[:kept.value].copy()
+
 
 class HipOperatorWrapper:
     """Device CSR operator: the Matrix role (`A * X`, `A.transpose() * X`)."""
