@@ -266,6 +266,9 @@ int rails_sweep_plan_array(const rails_sweep_plan *plan, int which, const void *
  * Role: the MultiVector template parameter's storage (StlWrapper m_max x n_max buffer,
  * src/StlWrapper.hpp:13-21). */
 int rails_panel_create(rails_ctx *ctx, int64_t m_local, int capacity, rails_panel **out);
+/* The same with rows exactly ld >= capacity doubles apart (no padding to 16 columns): for a narrow block that is swept whole several
+ * times in a row, where padded rows would only add cache lines.  Kernels that load 16 bytes at a time want ld even. */
+int rails_panel_create_ld(rails_ctx *ctx, int64_t m_local, int capacity, int ld, rails_panel **out);
 int rails_panel_destroy(rails_panel *P);
 int64_t rails_panel_rows(const rails_panel *P);
 int rails_panel_capacity(const rails_panel *P);
@@ -324,6 +327,13 @@ int rails_chol_inverse_deferred(rails_ctx *ctx, int slot_in, int w, int slot_out
  * over the ranks, on its way to the mirror).  Fused for r <= 17, r2 <= 16, 32 <= k <= 512; the two separate kernels otherwise. */
 int rails_update_gram_deferred(rails_ctx *ctx, double alpha, const rails_panel *X, int xc0, int k, const double *C_host, int ldc, int r,
                                rails_panel *Y, int yc0, int r2, int slot);
+/* The same with the updated columns written to Yout[:, oc0:oc0+r] and Y left as it was (Yout = Y, oc0 = yc0: the call above).  The
+ * arithmetic is that of the call above, operation for operation: the r columns of Yout and the slot hold the same bits whichever way
+ * it is called.  Where the two separate kernels run (k > 512, r > 17, r2 > 16, k < 32 or fewer than 4096 rows) Y is copied to Yout first.  Columns
+ * of Yout outside the window are not touched; no alignment of Yout is assumed.  X's window must not overlap Y's or Yout's; Y's and
+ * Yout's coincide or are disjoint. */
+int rails_update_gram_deferred_out(rails_ctx *ctx, double alpha, const rails_panel *X, int xc0, int k, const double *C_host, int ldc, int r,
+                                   const rails_panel *Y, int yc0, rails_panel *Yout, int oc0, int r2, int slot);
 int rails_deferred_fetch(rails_ctx *ctx, int slot, int64_t n, double *host_out);
 
 /* The same product for any number r of output columns: one upload of C, launches in slices of 128 columns with no host wait in

@@ -34,6 +34,7 @@ SIGNATURES = {
     "rails_deferred_reserve": (C.c_int, [_vp, C.c_int, C.c_int64]),
     "rails_gram_deferred": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int]),
     "rails_update_gram_deferred": (C.c_int, [_vp, C.c_double, _vp, C.c_int, C.c_int, _dp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int]),
+    "rails_update_gram_deferred_out": (C.c_int, [_vp, C.c_double, _vp, C.c_int, C.c_int, _dp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int]),
     "rails_panel_gemm_deferred": (C.c_int, [_vp, C.c_double, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _vp, C.c_int]),
     "rails_chol_inverse_deferred": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
     "rails_deferred_fetch": (C.c_int, [_vp, C.c_int, C.c_int64, _dp]),
@@ -65,6 +66,7 @@ SIGNATURES = {
     "rails_sweep_plan_info": (C.c_int, [_vp, _i64p, _dp]),
     "rails_sweep_plan_array": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), _i64p]),
     "rails_panel_create": (C.c_int, [_vp, C.c_int64, C.c_int, C.POINTER(_vp)]),
+    "rails_panel_create_ld": (C.c_int, [_vp, C.c_int64, C.c_int, C.c_int, C.POINTER(_vp)]),
     "rails_panel_destroy": (C.c_int, [_vp]),
     "rails_panel_rows": (C.c_int64, [_vp]),
     "rails_panel_capacity": (C.c_int, [_vp]),

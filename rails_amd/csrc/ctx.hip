@@ -264,16 +264,19 @@ extern "C" int rails_timer_stop(rails_ctx *c, double *ms)
 
 // ------------------------------------------------------------------- panels ---
 
-extern "C" int rails_panel_create(rails_ctx *c, int64_t m_local, int capacity, rails_panel **out)
+// a panel whose rows are exactly ld doubles apart (ld >= capacity, at least 1): a narrow block that is read and written whole, again and
+// again, takes the fewest cache lines when its rows are not padded to 16 columns (the scratch panel of the coordinate-space back end)
+extern "C" int rails_panel_create_ld(rails_ctx *c, int64_t m_local, int capacity, int ld, rails_panel **out)
 {
     if (c) hipSetDevice(c->device); // allocations and launches go to the context's device whatever the caller's current device is
     RAILS_REQUIRE(c && out, "rails_panel_create: null argument");
-    RAILS_REQUIRE(m_local >= 0 && capacity >= 0, "rails_panel_create: bad shape %lld x %d", (long long)m_local, capacity);
+    RAILS_REQUIRE(m_local >= 0 && capacity >= 0 && ld >= 1 && ld >= capacity, "rails_panel_create: bad shape %lld x %d (leading dimension %d)", (long long)m_local,
+                  capacity, ld);
     rails_panel *P = new rails_panel();
     P->ctx = c;
     P->m = m_local;
     P->cap = capacity;
-    P->ld = rails_pad_ld(capacity);
+    P->ld = ld;
     size_t bytes = (size_t)(m_local > 0 ? m_local : 1) * P->ld * sizeof(double);
     for (size_t q = 0; q < c->free_panels.size() && !P->d; ++q)
         if (c->free_panels[q].first == bytes) {
@@ -302,6 +305,12 @@ extern "C" int rails_panel_create(rails_ctx *c, int64_t m_local, int capacity, r
     RAILS_HIP_CHECK(hipMemsetAsync(P->d, 0, bytes, c->stream));
     *out = P;
     return RAILS_OK;
+}
+
+extern "C" int rails_panel_create(rails_ctx *c, int64_t m_local, int capacity, rails_panel **out)
+{
+    RAILS_REQUIRE(capacity >= 0, "rails_panel_create: bad shape %lld x %d", (long long)m_local, capacity);
+    return rails_panel_create_ld(c, m_local, capacity, rails_pad_ld(capacity), out);
 }
 
 extern "C" int rails_panel_destroy(rails_panel *P)

@@ -710,9 +710,13 @@ extern "C" int rails_panel_gemm_deferred(rails_ctx *c, double alpha, const rails
 // multiply-adds on the values the lanes hold anyway -- a second MFMA column tile for one column doubles the matrix work and makes the
 // pass MFMA-bound.  The next tile's rows are loaded while this one is worked on.  Per-workgroup partial C2 tiles go to the workspace
 // and are summed in a fixed order by k_reduce_partials, like every Gram matrix here.
+// Y is read from Yp (leading dimension ldy) and Y' is written to Yo (leading dimension ldo, no alignment assumed): the same place for the
+// update in place, or another panel -- a block that is orthogonalised next is better off in a compact panel of its own than in the tail
+// of the basis, where its 136 bytes per row are spread over two or three cache lines.  Only the two stores of Y' know Yo.
 template <int NBW, int NE>
 __global__ __launch_bounds__(256, (NBW <= 6 ? 2 : 1)) void k_update_gram(double alpha, const double *__restrict__ X, int ldx, int k, const double *__restrict__ C, int r,
-                                                     double *Yp, int ldy, int r2, int64_t m, int64_t ntiles, double *__restrict__ partial)
+                                                     const double *Yp, int ldy, double *Yo, int ldo, int r2, int64_t m, int64_t ntiles,
+                                                     double *__restrict__ partial)
 {
     constexpr int KMAX = 64 * NBW, RL = 20; // LDS row length of C (doubles): 16 + 4 keeps the four k-groups of a read on disjoint banks
     __shared__ double Cs[KMAX * RL];
@@ -796,11 +800,11 @@ __global__ __launch_bounds__(256, (NBW <= 6 ? 2 : 1)) void k_update_gram(double 
         {
             const double sum = ((red[0][wave][lane] + red[1][wave][lane]) + red[2][wave][lane]) + red[3][wave][lane];
             const double ynew = yv + alpha * sum;
-            if (yok) Yp[yrow * ldy + li] = ynew;
+            if (yok) Yo[yrow * ldo + li] = ynew;
             awL[(kk + 4 * wave) * 16 + li] = (yok && li < r2) ? ynew : 0.0;
             if (NE > 0 && eok) {
                 const double se = ((rede[0][ene][erow] + rede[1][ene][erow]) + rede[2][ene][erow]) + rede[3][ene][erow];
-                Yp[(row0 + erow) * ldy + 16 + ene] = ye + alpha * se;
+                Yo[(row0 + erow) * ldo + 16 + ene] = ye + alpha * se;
             }
         }
         __syncthreads();
@@ -844,27 +848,34 @@ __global__ __launch_bounds__(256, (NBW <= 6 ? 2 : 1)) void k_update_gram(double 
 }
 
 template <int NBW>
-static void launch_update_gram(rails_ctx *c, int ne, unsigned grid, double alpha, const double *X, int ldx, int k, const double *C, int r, double *Y, int ldy, int r2,
-                               int64_t m, int64_t ntiles)
+static void launch_update_gram(rails_ctx *c, int ne, unsigned grid, double alpha, const double *X, int ldx, int k, const double *C, int r, const double *Y, int ldy,
+                               double *Yo, int ldo, int r2, int64_t m, int64_t ntiles)
 {
     if (ne == 0)
-        RAILS_LAUNCH((k_update_gram<NBW, 0>), dim3(grid), dim3(256), 0, c->stream, alpha, X, ldx, k, C, r, Y, ldy, r2, m, ntiles, c->ws);
+        RAILS_LAUNCH((k_update_gram<NBW, 0>), dim3(grid), dim3(256), 0, c->stream, alpha, X, ldx, k, C, r, Y, ldy, Yo, ldo, r2, m, ntiles, c->ws);
     else
-        RAILS_LAUNCH((k_update_gram<NBW, 1>), dim3(grid), dim3(256), 0, c->stream, alpha, X, ldx, k, C, r, Y, ldy, r2, m, ntiles, c->ws);
+        RAILS_LAUNCH((k_update_gram<NBW, 1>), dim3(grid), dim3(256), 0, c->stream, alpha, X, ldx, k, C, r, Y, ldy, Yo, ldo, r2, m, ntiles, c->ws);
 }
 
 // Y[:, yc0:yc0+r] += alpha X[:, xc0:xc0+k] C (C on the host, k x r, leading dimension ldc), then slot <- X[:, xc0:xc0+k]' Y[:, yc0:yc0+r2]
 // (k x r2, leading dimension k, summed over the ranks, on its way to the slot's pinned mirror).  One pass over X where the shapes
 // allow (r <= 17, r2 <= 16, 32 <= k <= 512), the two separate kernels otherwise.
-extern "C" int rails_update_gram_deferred(rails_ctx *c, double alpha, const rails_panel *X, int xc0, int k, const double *C_host, int ldc, int r,
-                                          rails_panel *Y, int yc0, int r2, int slot)
+// The updated columns go to Yout[:, oc0:oc0+r] and the input Y stays as it was; Yout = Y with oc0 = yc0 is the update in place
+// (rails_update_gram_deferred).  The arithmetic does not know where the result goes: both forms give the same bits.  Where the two
+// separate kernels run, Y is copied to Yout first (rails_panel_copy's kernel) and they work on Yout.
+extern "C" int rails_update_gram_deferred_out(rails_ctx *c, double alpha, const rails_panel *X, int xc0, int k, const double *C_host, int ldc, int r,
+                                              const rails_panel *Y, int yc0, rails_panel *Yout, int oc0, int r2, int slot)
 {
     if (c) hipSetDevice(c->device);
     rails_slow_guard slow__(c, "rails_update_gram_deferred", k, r);
-    RAILS_REQUIRE(c && X && Y && C_host, "rails_update_gram_deferred: null argument");
+    RAILS_REQUIRE(c && X && Y && Yout && C_host, "rails_update_gram_deferred: null argument");
     RAILS_REQUIRE(k >= 1 && r >= 1 && r <= 256 && r2 >= 1 && r2 <= r && ldc >= k && xc0 >= 0 && yc0 >= 0 && xc0 + k <= X->cap && yc0 + r <= Y->cap && X->m == Y->m,
                   "rails_update_gram_deferred: bad shapes");
+    RAILS_REQUIRE(oc0 >= 0 && oc0 + r <= Yout->cap && Yout->m == X->m, "rails_update_gram_deferred: output window [%d,%d) outside capacity %d, or row mismatch", oc0,
+                  oc0 + r, Yout->cap);
     if (X->d == Y->d) RAILS_REQUIRE(xc0 + k <= yc0 || yc0 + r <= xc0, "rails_update_gram_deferred: overlapping windows of one panel");
+    if (X->d == Yout->d) RAILS_REQUIRE(xc0 + k <= oc0 || oc0 + r <= xc0, "rails_update_gram_deferred: overlapping windows of one panel");
+    if (Y->d == Yout->d) RAILS_REQUIRE(yc0 == oc0 || yc0 + r <= oc0 || oc0 + r <= yc0, "rails_update_gram_deferred: partially overlapping windows of one panel");
     const size_t n = (size_t)k * r2;
     RAILS_SLOT_CHECK(slot, n, "rails_update_gram_deferred");
     double *out = c->defer_dev + (size_t)slot * c->defer_slot;
@@ -879,7 +890,8 @@ extern "C" int rails_update_gram_deferred(rails_ctx *c, double alpha, const rail
         RAILS_TRY(rails_pinned_end_write(c));
         static const int fused_env = getenv("RAILS_FUSED_UPDATE_GRAM") ? atoi(getenv("RAILS_FUSED_UPDATE_GRAM")) : 1;
         const double *Xp = X->d + xc0;
-        double *Ypp = Y->d + yc0;
+        const double *Ypp = Y->d + yc0;
+        double *Yop = Yout->d + oc0;
         // (16-byte loads of four columns at a time: aligned rows, and the columns between k and k rounded up to 4 are Y's own)
         const int k4 = (k + 3) & ~3;
         const bool rows_ok = ((((uintptr_t)Xp) & 15) == 0 && (X->ld % 2) == 0) && (k4 == k || (X->d == Y->d && yc0 == xc0 + k && r >= k4 - k));
@@ -889,22 +901,29 @@ extern "C" int rails_update_gram_deferred(rails_ctx *c, double alpha, const rail
             const int ne = r > 16 ? r - 16 : 0;
             RAILS_TRY(rails_ws_reserve(c, (size_t)grid * n * sizeof(double)));
             if (k <= 256)
-                launch_update_gram<4>(c, ne, grid, alpha, Xp, X->ld, k, c->small, r, Ypp, Y->ld, r2, X->m, ntiles);
+                launch_update_gram<4>(c, ne, grid, alpha, Xp, X->ld, k, c->small, r, Ypp, Y->ld, Yop, Yout->ld, r2, X->m, ntiles);
             else if (k <= 384)
-                launch_update_gram<6>(c, ne, grid, alpha, Xp, X->ld, k, c->small, r, Ypp, Y->ld, r2, X->m, ntiles);
+                launch_update_gram<6>(c, ne, grid, alpha, Xp, X->ld, k, c->small, r, Ypp, Y->ld, Yop, Yout->ld, r2, X->m, ntiles);
             else
-                launch_update_gram<8>(c, ne, grid, alpha, Xp, X->ld, k, c->small, r, Ypp, Y->ld, r2, X->m, ntiles);
+                launch_update_gram<8>(c, ne, grid, alpha, Xp, X->ld, k, c->small, r, Ypp, Y->ld, Yop, Yout->ld, r2, X->m, ntiles);
             RAILS_LAUNCH(k_reduce_partials, dim3((unsigned)((n + 63) / 64)), dim3(1024), 0, c->stream, c->ws, (int64_t)grid, (int64_t)n, out);
             RAILS_HIP_CHECK(hipGetLastError());
             c->n_update_gram_fused++;
         } else {
-            RAILS_TRY(rails_panel_gemm_dev(c, alpha, Xp, X->ld, k, c->small, r, 1.0, Ypp, Y->ld, X->m));
-            RAILS_TRY(rails_gram_dev(c, Xp, X->ld, Ypp, Y->ld, X->m, k, r2, out));
+            if (Yop != Ypp) RAILS_TRY(rails_panel_copy(c, Y, yc0, r, Yout, oc0));
+            RAILS_TRY(rails_panel_gemm_dev(c, alpha, Xp, X->ld, k, c->small, r, 1.0, Yop, Yout->ld, X->m));
+            RAILS_TRY(rails_gram_dev(c, Xp, X->ld, Yop, Yout->ld, X->m, k, r2, out));
         }
     }
     RAILS_TRY(rails_allreduce_dev(c, out, n));
     RAILS_HIP_CHECK(hipMemcpyAsync(c->defer_pin + (size_t)slot * c->defer_slot, out, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     return RAILS_OK;
+}
+
+extern "C" int rails_update_gram_deferred(rails_ctx *c, double alpha, const rails_panel *X, int xc0, int k, const double *C_host, int ldc, int r,
+                                          rails_panel *Y, int yc0, int r2, int slot)
+{
+    return rails_update_gram_deferred_out(c, alpha, X, xc0, k, C_host, ldc, r, Y, yc0, Y, yc0, r2, slot);
 }
 
 // slot_out <- D^-1 R^-1 for the w x w Gram matrix in slot_in (see k_small_chol)

@@ -68,6 +68,7 @@ struct PanelHandle {
     rails_panel *p;
     bool own;
     PanelHandle(rails_ctx *c, int64_t m, int cap) : ctx(c), p(nullptr), own(true) { hip_ok(rails_panel_create(c, m, cap, &p), "rails_panel_create"); }
+    PanelHandle(rails_ctx *c, int64_t m, int cap, int ld) : ctx(c), p(nullptr), own(true) { hip_ok(rails_panel_create_ld(c, m, cap, ld, &p), "rails_panel_create_ld"); } // rows exactly ld apart
     PanelHandle(rails_ctx *c, rails_panel *borrowed) : ctx(c), p(borrowed), own(false) {}
     ~PanelHandle()
     {

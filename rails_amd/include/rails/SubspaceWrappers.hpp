@@ -100,6 +100,24 @@ public:
         std::vector<double> g0diag; // squared lengths of the block's columns before any projection
     } pending;
     enum { SLOT_C2 = 0, SLOT_G = 1, SLOT_M1 = 2, SLOT_G2 = 3, SLOT_M2 = 4, N_SLOTS = 5 };
+    // Where the block lives while the queued chain works on it.  In P's tail its w = 17 columns are 136 bytes per row at a row stride of
+    // P.capacity() doubles: every row touches two or three 128-byte lines, about 256 MB of lines for 136 MB of data at a million rows, and
+    // the chain sweeps them six times.  The chain therefore moves the block into a compact panel S of its own (rows of w rounded up to even
+    // doubles: 16-byte aligned, 144 MB, which the 256 MiB last-level cache can hold from one sweep to the next) with the first pass that
+    // writes it anyway, works there in place, and writes P's tail once, with the last scaling (what each pass gained: DESIGN.md section
+    // 3a).  Only addresses change: the kernels, their
+    // coefficients and every order of summation are those of the chain in the tail, and so are the bits of the result.  S is allocated
+    // when the first block is queued and kept; it grows only for a wider block.  RAILS_SUBSPACE_BLOCK_SCRATCH=0 keeps the chain in the tail.
+    bool block_scratch = !(getenv("RAILS_SUBSPACE_BLOCK_SCRATCH") && atoi(getenv("RAILS_SUBSPACE_BLOCK_SCRATCH")) == 0);
+    long n_scratch_blocks = 0;
+    std::shared_ptr<PanelHandle> S;
+    rails_panel *scratch_panel(int w)
+    {
+        if (S && S->p && rails_panel_capacity(S->p) >= w) return S->p;
+        const int ld = (w + 1) & ~1;
+        S = std::make_shared<PanelHandle>(ctx, m_local, ld, ld);
+        return S->p;
+    }
 
     SubspaceBasis(rails_ctx *c, int64_t ml, int64_t mg, int rows) : ctx(c), m_local(ml), m_global(mg), P(ml, std::max(rows, 16), c), row_cap(std::max(rows, 16))
     {
@@ -349,19 +367,35 @@ public:
         // the device's part: the first update, the second round on the leading w2 columns, Gram matrix of the block, its Cholesky
         // factor inverted, Q1 = X M1, the same once more (CholQR2)
         rails_panel *pp = P.panel();
+        // the block between its first and its last pass: columns [b0, b0 + w) of bp -- the scratch panel, or P's tail as before
+        rails_panel *bp = pp;
+        int b0 = dim;
+        if (block_scratch) {
+            bp = scratch_panel(w);
+            b0 = 0;
+            if (!bp) return fail("no scratch panel for the overlapped block orthogonalisation");
+        }
         bool ok = true;
+        // xp, x0: where the block is when its first Gram matrix is taken
+        rails_panel *xp = bp;
+        int x0 = b0;
         if (w2 > 0) {
-            // first update and second projection in one pass over P (rails_update_gram_deferred), then the second update from the slot
-            ok = ok && hip_ok(rails_update_gram_deferred(ctx, -1.0, pp, 0, dim, CG.data(), dw, w, pp, dim, w2, SLOT_C2), "rails_update_gram_deferred");
-            ok = ok && hip_ok(rails_panel_gemm_deferred(ctx, -1.0, pp, 0, dim, SLOT_C2, dim, w2, 1.0, pp, dim), "rails_panel_gemm_deferred");
-        } else
+            // first update and second projection in one pass over P (rails_update_gram_deferred_out: reads the tail, writes the block's
+            // place), then the second update from the slot
+            ok = ok && hip_ok(rails_update_gram_deferred_out(ctx, -1.0, pp, 0, dim, CG.data(), dw, w, pp, dim, bp, b0, w2, SLOT_C2), "rails_update_gram_deferred_out");
+            ok = ok && hip_ok(rails_panel_gemm_deferred(ctx, -1.0, pp, 0, dim, SLOT_C2, dim, w2, 1.0, bp, b0), "rails_panel_gemm_deferred");
+        } else {
+            // (no fused pass: the update stays in the tail, and the first scaling moves the block)
             ok = ok && hip_ok(rails_panel_gemm(ctx, -1.0, pp, 0, dim, CG.data(), dw, w, 1.0, pp, dim), "rails_panel_gemm");
-        ok = ok && hip_ok(rails_gram_deferred(ctx, pp, dim, w, pp, dim, w, SLOT_G), "rails_gram_deferred");
+            xp = pp;
+            x0 = dim;
+        }
+        ok = ok && hip_ok(rails_gram_deferred(ctx, xp, x0, w, xp, x0, w, SLOT_G), "rails_gram_deferred");
         ok = ok && hip_ok(rails_chol_inverse_deferred(ctx, SLOT_G, w, SLOT_M1), "rails_chol_inverse_deferred");
-        ok = ok && hip_ok(rails_panel_gemm_deferred(ctx, 1.0, pp, dim, w, SLOT_M1, w, w, 0.0, pp, dim), "rails_panel_gemm_deferred");
-        ok = ok && hip_ok(rails_gram_deferred(ctx, pp, dim, w, pp, dim, w, SLOT_G2), "rails_gram_deferred");
+        ok = ok && hip_ok(rails_panel_gemm_deferred(ctx, 1.0, xp, x0, w, SLOT_M1, w, w, 0.0, bp, b0), "rails_panel_gemm_deferred");
+        ok = ok && hip_ok(rails_gram_deferred(ctx, bp, b0, w, bp, b0, w, SLOT_G2), "rails_gram_deferred");
         ok = ok && hip_ok(rails_chol_inverse_deferred(ctx, SLOT_G2, w, SLOT_M2), "rails_chol_inverse_deferred");
-        ok = ok && hip_ok(rails_panel_gemm_deferred(ctx, 1.0, pp, dim, w, SLOT_M2, w, w, 0.0, pp, dim), "rails_panel_gemm_deferred");
+        ok = ok && hip_ok(rails_panel_gemm_deferred(ctx, 1.0, bp, b0, w, SLOT_M2, w, w, 0.0, pp, dim), "rails_panel_gemm_deferred"); // back into P's tail
         if (!ok) return fail("the overlapped block orthogonalisation could not be queued"); // false, with `failed` latched: the caller gives up
         // predicted coordinates along the new columns: X = Q Rfp
         pending.active = true;
@@ -375,6 +409,7 @@ public:
         }
         if (w2 > 0) n_second_round++;
         n_overlapped++;
+        if (block_scratch) n_scratch_blocks++;
         // test hook (tests/test_gpu_solver.py): the n-th overlapped block books a prediction that is off by 1 %, so that the read-back's
         // check has something to reject -- the failure has to be loud and end the run
         static const long spoil = getenv("RAILS_SUBSPACE_TEST_SPOIL_PREDICTION") ? atol(getenv("RAILS_SUBSPACE_TEST_SPOIL_PREDICTION")) : 0;
