@@ -341,6 +341,18 @@ int rails_deferred_fetch(rails_ctx *ctx, int slot, int64_t n, double *host_out);
 int rails_panel_gemm_wide(rails_ctx *ctx, double alpha, const rails_panel *X, int xc0, int k, const double *C_host, int ldc, int r,
                           double beta, rails_panel *Y, int yc0);
 
+/* Tile counts of the dense kernels fitted to the widths a solve runs at: rails_update_gram_deferred[_out] with five column blocks per
+ * wave for 256 < k <= 320, the wide-X Gram form with five tiles per wave instead of six where the same waves cover it (289 to 320 columns),
+ * rails_panel_gemm_wide with 13, 15 or 17 output tiles where that is the exact count, and without the second half of its last chunk
+ * of 32 where that lies past k.  All of it leaves out work on zero padding only: results are the same bits either way.  On by default;
+ * RAILS_DENSE_TILE_FIT=0 in the environment (read at the first use) or this process-wide setter (on = 0; it wins over the variable)
+ * restores the choices before the fit. */
+void rails_dense_set_tile_fit(int on);
+int rails_dense_tile_fit(void);
+/* Template parameter of the context's last launch of k_update_gram<NBW, .>, of the wide-X Gram form k_gram_cols[2]<TI, ., .> and of
+ * k_panel_gemm_wide<TR> (its last slice); 0 where there has been none.  Any of the three pointers may be NULL.  Read-only. */
+int rails_dense_last_tiles(const rails_ctx *ctx, int *update_gram_nbw, int *gram_cols_ti, int *gemm_wide_tr);
+
 /* Orthonormalise columns [k_old, k_old+w) of V against columns [0, k_old) and among themselves,
  * equivalent to the reference's column-wise CGS2 with pre/post normalisation
  * (src/StlWrapper.cpp:305-321): block CGS2 + CholQR2 on MFMA, falling back to the column-wise

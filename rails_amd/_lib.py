@@ -108,6 +108,9 @@ SIGNATURES = {
     "rails_gram": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _dp, C.c_int]),
     "rails_panel_gemm": (C.c_int, [_vp, C.c_double, _vp, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_double, _vp, C.c_int]),
     "rails_panel_gemm_wide": (C.c_int, [_vp, C.c_double, _vp, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_double, _vp, C.c_int]),
+    "rails_dense_set_tile_fit": (None, [C.c_int]),
+    "rails_dense_tile_fit": (C.c_int, []),
+    "rails_dense_last_tiles": (C.c_int, [_vp, _ip, _ip, _ip]),
     "rails_orthogonalize": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _ip]),
     "rails_orthogonalize_deflated": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _ip]),
     "rails_panel_colnorms2": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _dp]),

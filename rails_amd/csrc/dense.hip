@@ -33,6 +33,24 @@ namespace {
 typedef double v4f64 __attribute__((ext_vector_type(4)));
 typedef double v2f64 __attribute__((ext_vector_type(2)));
 
+// Tile counts fitted to the widths a solve runs at: k_update_gram<5, .>, k_gram_cols<5, 1, .>, the odd TR of
+// k_panel_gemm_wide and its skipped half chunk.  One process-wide switch for all of them: rails_dense_set_tile_fit, or
+// RAILS_DENSE_TILE_FIT=0 in the environment (read at the first use, unless the setter came first).  Off: the choices before the fit.
+// Either way the same bits come out: the fitted forms leave out work on zero padding and nothing else.
+std::atomic<int> g_tile_fit{-1}; // -1: not decided yet
+
+bool dense_tile_fit()
+{
+    int v = g_tile_fit.load(std::memory_order_relaxed);
+    if (v < 0) {
+        const char *e = getenv("RAILS_DENSE_TILE_FIT");
+        int undecided = -1;
+        g_tile_fit.compare_exchange_strong(undecided, (e ? atoi(e) : 1) ? 1 : 0); // (a setter that got in between wins)
+        v = g_tile_fit.load(std::memory_order_relaxed);
+    }
+    return v != 0;
+}
+
 __device__ __forceinline__ v4f64 mfma_f64(double a, double b, v4f64 c)
 {
     return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
@@ -212,7 +230,7 @@ __global__ void k_pack_ct(const double *__restrict__ C, int k, int r, int kpad, 
 
 template <int TR>
 __global__ __launch_bounds__(512) void k_panel_gemm_wide(double alpha, const double *__restrict__ X, int ldx, int k, const double *__restrict__ Ct /* packed, kpad x RL */,
-                                                         int r, double beta, double *__restrict__ Yp, int ldy, int64_t m, int vec_ok)
+                                                         int r, double beta, double *__restrict__ Yp, int ldy, int64_t m, int vec_ok, int skip_tail)
 {
     constexpr int KC = 32, RL = 16 * TR + 4, CHUNK_B = KC * RL * 8, PIECES = CHUNK_B / 1024; // (KC * RL * 8 is a multiple of 1024 for every TR)
     static_assert(CHUNK_B % 1024 == 0, "whole LDS-DMA pieces per chunk");
@@ -270,11 +288,15 @@ __global__ __launch_bounds__(512) void k_panel_gemm_wide(double alpha, const dou
 #pragma unroll
             for (int t = 0; t < TR; ++t) acc[t] = mfma_f64(xa[s], crow[16 * t], acc[t]);
         }
+        // (skip_tail: the second half of the last chunk is left out where it lies past k altogether -- sixteen k-steps of zeros times
+        // zeros.  The same for every wave of every block; the fetches above stay, so the loads keep their order.)
+        if (!skip_tail || ci * KC + 16 < k) {
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const double *crow = &cb[(16 + 4 * kk + s) * RL + li];
+            for (int s = 0; s < 4; ++s) {
+                const double *crow = &cb[(16 + 4 * kk + s) * RL + li];
 #pragma unroll
-            for (int t = 0; t < TR; ++t) acc[t] = mfma_f64(xb[s], crow[16 * t], acc[t]);
+                for (int t = 0; t < TR; ++t) acc[t] = mfma_f64(xb[s], crow[16 * t], acc[t]);
+            }
         }
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
@@ -310,7 +332,9 @@ int launch_pg_wide(rails_ctx *c, double alpha, const double *X, int ldx, int k, 
     RAILS_LAUNCH(k_pack_ct, dim3((unsigned)std::min<int64_t>(512, ((int64_t)kpad * RL + 255) / 256)), dim3(256), 0, c->stream, C, k, r, kpad, RL, ct);
     const size_t lds = (size_t)2 * 32 * RL * sizeof(double);
     RAILS_HIP_CHECK(hipFuncSetAttribute((const void *)k_panel_gemm_wide<TR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    RAILS_LAUNCH((k_panel_gemm_wide<TR>), dim3((unsigned)((m + 127) / 128)), dim3(512), lds, c->stream, alpha, X, ldx, k, ct, r, beta, Y, ldy, m, vec_ok);
+    RAILS_LAUNCH((k_panel_gemm_wide<TR>), dim3((unsigned)((m + 127) / 128)), dim3(512), lds, c->stream, alpha, X, ldx, k, ct, r, beta, Y, ldy, m, vec_ok,
+                 dense_tile_fit() ? 1 : 0);
+    c->last_gemm_wide_tr = TR;
     return RAILS_OK;
 }
 
@@ -329,7 +353,10 @@ void gram_slabs(int64_t m, int a, int b, int64_t *nslab_out, int64_t *rps_out)
 }
 
 // wide-X form: tiles of 16 X-columns per wave, the choice that leaves the fewest idle tile slots in blocks of four waves
-// (one_tile: Y is one MFMA column tile, b <= 16 or the 17th column on the vector unit)
+// (one_tile: Y is one MFMA column tile, b <= 16 or the 17th column on the vector unit).  With the tile fit a one-tile form of six
+// tiles per wave becomes one of five where five cover the columns with the same number of waves (19 and 20 tiles, 289 to 320
+// columns: 20 slots instead of 24).  Not where five need a wave more: at 17 and 18 tiles six tiles keep three waves busy, the fourth
+// leaves at once and costs nothing, and four waves of five measured 16 us slower (profiles/r11_tile_fit_kernels.md).
 int gram_cols_tiles(int ntiles, bool one_tile)
 {
     const int cand2[3] = {3, 4, 5}, cand1[3] = {4, 6, 8};
@@ -339,18 +366,22 @@ int gram_cols_tiles(int ntiles, bool one_tile)
         int ti = cand[q], strips = (ntiles + ti - 1) / ti, cost = (strips + 3) / 4 * 4 * ti;
         if (cost < best_cost) best = ti, best_cost = cost;
     }
+    if (one_tile && best == 6 && (ntiles + 4) / 5 == (ntiles + 5) / 6 && dense_tile_fit()) best = 5;
     return best;
 }
 
-// the nine instantiations of the wide-X form; K is k_gram_cols or k_gram_cols2, the variadic part its operand arguments
+// the eleven instantiations of the wide-X form; K is k_gram_cols or k_gram_cols2, the variadic part its operand arguments
 #define RAILS_GRAM_COLS_CASE(K, TI, TJ, NE, ...) RAILS_LAUNCH((K<TI, TJ, NE>), grid, dim3(256), 0, c->stream, __VA_ARGS__, Y, ldy, b, m, rps, c->ws)
 #define RAILS_GRAM_COLS(K, ...)                                                                                                            \
     do {                                                                                                                                   \
         const int ntiles = (a + 15) / 16, best = gram_cols_tiles(ntiles, b <= 16 || extra);                                                \
         const dim3 grid((unsigned)nslab, (unsigned)(((ntiles + best - 1) / best + 3) / 4));                                                \
+        c->last_gram_cols_ti = best;                                                                                                       \
         if (extra) {                                                                                                                       \
             if (best == 4)                                                                                                                 \
                 RAILS_GRAM_COLS_CASE(K, 4, 1, 1, __VA_ARGS__);                                                                             \
+            else if (best == 5)                                                                                                            \
+                RAILS_GRAM_COLS_CASE(K, 5, 1, 1, __VA_ARGS__);                                                                             \
             else if (best == 6)                                                                                                            \
                 RAILS_GRAM_COLS_CASE(K, 6, 1, 1, __VA_ARGS__);                                                                             \
             else                                                                                                                           \
@@ -358,6 +389,8 @@ int gram_cols_tiles(int ntiles, bool one_tile)
         } else if (b <= 16) {                                                                                                              \
             if (best == 4)                                                                                                                 \
                 RAILS_GRAM_COLS_CASE(K, 4, 1, 0, __VA_ARGS__);                                                                             \
+            else if (best == 5)                                                                                                            \
+                RAILS_GRAM_COLS_CASE(K, 5, 1, 0, __VA_ARGS__);                                                                             \
             else if (best == 6)                                                                                                            \
                 RAILS_GRAM_COLS_CASE(K, 6, 1, 0, __VA_ARGS__);                                                                             \
             else                                                                                                                           \
@@ -371,6 +404,19 @@ int gram_cols_tiles(int ntiles, bool one_tile)
     } while (0)
 
 } // namespace
+
+extern "C" void rails_dense_set_tile_fit(int on) { g_tile_fit.store(on ? 1 : 0); }
+
+extern "C" int rails_dense_tile_fit(void) { return dense_tile_fit() ? 1 : 0; }
+
+extern "C" int rails_dense_last_tiles(const rails_ctx *c, int *update_gram_nbw, int *gram_cols_ti, int *gemm_wide_tr)
+{
+    RAILS_REQUIRE(c, "rails_dense_last_tiles: null context");
+    if (update_gram_nbw) *update_gram_nbw = c->last_update_gram_nbw;
+    if (gram_cols_ti) *gram_cols_ti = c->last_gram_cols_ti;
+    if (gemm_wide_tr) *gemm_wide_tr = c->last_gemm_wide_tr;
+    return RAILS_OK;
+}
 
 int rails_gram_dev(rails_ctx *c, const double *X, int ldx, const double *Y, int ldy, int64_t m, int a, int b, double *C_dev)
 {
@@ -855,6 +901,7 @@ static void launch_update_gram(rails_ctx *c, int ne, unsigned grid, double alpha
         RAILS_LAUNCH((k_update_gram<NBW, 0>), dim3(grid), dim3(256), 0, c->stream, alpha, X, ldx, k, C, r, Y, ldy, Yo, ldo, r2, m, ntiles, c->ws);
     else
         RAILS_LAUNCH((k_update_gram<NBW, 1>), dim3(grid), dim3(256), 0, c->stream, alpha, X, ldx, k, C, r, Y, ldy, Yo, ldo, r2, m, ntiles, c->ws);
+    c->last_update_gram_nbw = NBW;
 }
 
 // Y[:, yc0:yc0+r] += alpha X[:, xc0:xc0+k] C (C on the host, k x r, leading dimension ldc), then slot <- X[:, xc0:xc0+k]' Y[:, yc0:yc0+r2]
@@ -902,6 +949,8 @@ extern "C" int rails_update_gram_deferred_out(rails_ctx *c, double alpha, const 
             RAILS_TRY(rails_ws_reserve(c, (size_t)grid * n * sizeof(double)));
             if (k <= 256)
                 launch_update_gram<4>(c, ne, grid, alpha, Xp, X->ld, k, c->small, r, Ypp, Y->ld, Yop, Yout->ld, r2, X->m, ntiles);
+            else if (k <= 320 && dense_tile_fit()) // (the waves' interleaved blocks of 16 columns: 20 of them instead of 24)
+                launch_update_gram<5>(c, ne, grid, alpha, Xp, X->ld, k, c->small, r, Ypp, Y->ld, Yop, Yout->ld, r2, X->m, ntiles);
             else if (k <= 384)
                 launch_update_gram<6>(c, ne, grid, alpha, Xp, X->ld, k, c->small, r, Ypp, Y->ld, Yop, Yout->ld, r2, X->m, ntiles);
             else
@@ -1111,10 +1160,16 @@ extern "C" int rails_panel_gemm_wide(rails_ctx *c, double alpha, const rails_pan
         RAILS_TRY(rails_ws_reserve(c, (size_t)nslices * ct_doubles * sizeof(double)));
         int slice = 0;
         for (int j0 = 0; j0 < r; j0 += width, ++slice) {
-            const int nc = std::min(width, r - j0), tr = (nc + 31) / 32 * 2;
+            // tiles of 16 output columns per wave: an even count, or with the tile fit the exact count where that is 13, 15 or 17
+            // (a rank of 257 to 272 after compress() is 17 tiles: as 18, one tile in eighteen of every k-step multiplied zeros)
+            const int nc = std::min(width, r - j0), exact = (nc + 15) / 16;
+            const int tr = (dense_tile_fit() && (exact == 13 || exact == 15 || exact == 17)) ? exact : (nc + 31) / 32 * 2;
             const double *Cj = c->small + (size_t)j0 * k;
             double *Yj = Y->d + yc0 + j0, *ct = c->ws + (size_t)slice * ct_doubles;
             switch (tr) {
+            case 13: RAILS_TRY((launch_pg_wide<13>(c, alpha, X->d + xc0, X->ld, k, Cj, nc, beta, Yj, Y->ld, X->m, vec_ok, ct))); break;
+            case 15: RAILS_TRY((launch_pg_wide<15>(c, alpha, X->d + xc0, X->ld, k, Cj, nc, beta, Yj, Y->ld, X->m, vec_ok, ct))); break;
+            case 17: RAILS_TRY((launch_pg_wide<17>(c, alpha, X->d + xc0, X->ld, k, Cj, nc, beta, Yj, Y->ld, X->m, vec_ok, ct))); break;
             case 2: case 4: case 6: RAILS_TRY((launch_pg_wide<6>(c, alpha, X->d + xc0, X->ld, k, Cj, nc, beta, Yj, Y->ld, X->m, vec_ok, ct))); break;
             case 8: RAILS_TRY((launch_pg_wide<8>(c, alpha, X->d + xc0, X->ld, k, Cj, nc, beta, Yj, Y->ld, X->m, vec_ok, ct))); break;
             case 10: RAILS_TRY((launch_pg_wide<10>(c, alpha, X->d + xc0, X->ld, k, Cj, nc, beta, Yj, Y->ld, X->m, vec_ok, ct))); break;

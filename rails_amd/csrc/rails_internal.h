@@ -94,6 +94,8 @@ struct rails_ctx {
     void *lz = nullptr; // rails_lanczos_state (lanczos.hip), released by rails_lanczos_release
     long n_orth_block = 0, n_orth_columnwise = 0, n_spmm_tiled = 0, n_spmm_planes = 0, n_spmm_overlapped = 0, n_spmm_sweep = 0, n_spmm_rowgather = 0, n_spmm_callback = 0, n_dev_alloc = 0, n_allreduce = 0, n_lanczos = 0, n_lanczos_start = 0, n_orth_repair = 0, n_update_gram_fused = 0, n_rowquad = 0;
     long n_orth_range = 0, n_orth_range_passes = 0, n_orth_range_syncs = 0; // rails_orthogonalize_range: calls, passes over a block of columns, host synchronisations
+    // template parameter of the last launch of k_update_gram<NBW, .>, k_gram_cols[2]<TI, ., .> and k_panel_gemm_wide<TR> (rails_dense_last_tiles); 0: none yet
+    int last_update_gram_nbw = 0, last_gram_cols_ti = 0, last_gemm_wide_tr = 0;
 };
 
 // the busy meter (see rails_ctx): RAILS_LAUNCH brackets a launch, rails_stream_sync reads what has been bracketed since the last one
