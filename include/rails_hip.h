@@ -219,6 +219,42 @@ int rails_lu_stats(const rails_lu *lu, int64_t *info, int cap);
  * (HipOperatorWrapper, rails_solver_create, rails_solver_set_inverse).  The caller keeps the rails_lu alive while the handle is used. */
 int rails_csr_create_lu(rails_ctx *ctx, rails_lu *lu, rails_csr **out);
 
+/* ---- iterative solve as a library object (rails_amd/csrc/itsolve.hip, iter_scalars.h) --------------------------------------------------
+ * The same operator A^-1 without a factorisation: the reference asks for no more than an approximate inverse (matlab/RAILSsolver.m:19-23,
+ * opts.Ainv: "This can be approximate"), and at the sizes where the fill of L and U rules a sparse LU out an iteration on the device is
+ * the only A^-1 there is.  A is any square operator handle rails_spmm accepts (a CSR matrix, a callback operator such as the Schur
+ * complement; a rectangular handle is refused); the caller keeps A and the rails_iter alive, as with rails_csr_create_lu.  method:
+ * RAILS_ITER_CG for a definite A of either sign, RAILS_ITER_BICGSTAB (right-preconditioned) for a general one.  The Jacobi preconditioner
+ * comes from diag_host (m entries, none zero); with diag_host = NULL from the CSR diagonal when A is a CSR matrix and every diagonal
+ * entry is stored and nonzero; otherwise there is none.  Every column is a system of its own (start value zero, tolerance relative to
+ * its own ||b||); all scalars stay on the device and the host reads one number back every `check_every` iterations.  No floating-point
+ * atomics: two solves of the same input give the same bits, whatever check_every is.  Single GPU only.
+ * Settings (rails_iter_set): "tolerance" 1e-10, "max_iterations" 1000, "jacobi" 1, "check_every" 8, "strict" 0.
+ * Outcomes: a zero right-hand-side column gives x = 0 after 0 iterations; a column that stops at max_iterations or breaks down (a
+ * vanishing denominator; CG: p'Ap of the wrong sign, the operator is not definite) keeps its last iterate and is flagged, and the call
+ * still returns RAILS_OK unless "strict" is set (RAILS_ENOCONV); a right-hand side that is not finite gives RAILS_EINVAL. */
+typedef struct rails_iter rails_iter;
+#define RAILS_ENOCONV -7 /* strict mode only: a column did not reach the tolerance */
+#define RAILS_ITER_CG 1
+#define RAILS_ITER_BICGSTAB 2
+int rails_iter_create(rails_ctx *ctx, rails_csr *A, int method, const double *diag_host, rails_iter **out);
+int rails_iter_set(rails_iter *it, const char *name, double value);
+/* Y[:, yc0:yc0+nc] = A^-1 X[:, xc0:xc0+nc] (trans != 0: A^-T; CG ignores it), out of place, any nc (groups of 32 columns); X is left
+ * unchanged and columns of Y outside the window are not touched.  The object owns its work panels and grows them only for a wider nc.
+ * Synchronises. */
+int rails_iter_solve(rails_ctx *ctx, rails_iter *it, int trans, const rails_panel *X, int xc0, int nc, rails_panel *Y, int yc0);
+/* Last solve: info[0] most iterations of a column, [1] inner products, [2] launches of the library's own passes, [3] columns that did not
+ * converge, [4] of those, broken down, [5] worst relative residual of the recurrence, [6] work-panel columns, [7] products with A;
+ * totals since creation: [8] solves, [9] columns, [10] iterations summed over columns, [11] flagged columns, [12] products.  Returns the
+ * number of entries written (at most cap), or a negative code. */
+int rails_iter_stats(const rails_iter *it, double *info, int cap);
+/* Per column of the last solve (any pointer may be NULL): iterations, relative residual of the recurrence, flags (2 converged, 4 stopped at
+ * max_iterations, 8 breakdown, 16 non-finite).  Returns the number of columns of the last solve; at most cap are written. */
+int rails_iter_columns(const rails_iter *it, int32_t *iterations, double *relres, int32_t *flags, int cap);
+/* An operator handle whose rails_spmm is rails_iter_solve: it goes wherever the LU handle goes (rails_solver_set_inverse, ...). */
+int rails_csr_create_iter(rails_ctx *ctx, rails_iter *it, rails_csr **out);
+void rails_iter_destroy(rails_iter *it);
+
 /* ---- sparse right-hand side (rails_amd/csrc/sprhs_host.cpp, sprhs.hip, lanczos.hip) ------------------------------------------------------
  * B of A X M' + M X A' + B B' = 0 as a sparse m x p matrix instead of a panel: the operator form of the reference's
  * MatrixOrMultiVectorWrapper (src/MatrixOrMultiVectorWrapper.hpp; src/main.cpp:67 reads B.mtx as a CrsMatrix and :98 hands it to the

@@ -6,6 +6,7 @@ templated Solver<Matrix, MultiVector, DenseMatrix>.  This Python package is the 
 mirror used by the tests and bench.py.  There is no CPU fallback anywhere in this package.
 """
 from ._lib import LIB_PATH, RailsError, load  # noqa: F401
+from .itsolve import IterativeInverse  # noqa: F401
 from .solution import Solution  # noqa: F401
 from .solver import Solver  # noqa: F401
 from .sparse_rhs import SparseRHS, resid_lanczos_sparse  # noqa: F401

@@ -91,6 +91,13 @@ SIGNATURES = {
     "rails_lu_solve": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int]),
     "rails_lu_stats": (C.c_int, [_vp, _i64p, C.c_int]),
     "rails_csr_create_lu": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
+    "rails_iter_create": (C.c_int, [_vp, _vp, C.c_int, _dp, C.POINTER(_vp)]),
+    "rails_iter_set": (C.c_int, [_vp, C.c_char_p, C.c_double]),
+    "rails_iter_solve": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int]),
+    "rails_iter_stats": (C.c_int, [_vp, _dp, C.c_int]),
+    "rails_iter_columns": (C.c_int, [_vp, _i32p, _dp, _i32p, C.c_int]),
+    "rails_csr_create_iter": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
+    "rails_iter_destroy": (None, [_vp]),
     "rails_csr_transpose_host": (C.c_int, [C.c_int64, C.c_int64, _i64p, _i32p, _dp, _i64p, _i32p, _dp]),
     "rails_csr_gram_norm2_host": (C.c_int, [C.c_int64, C.c_int64, _i64p, _i32p, _dp, _i64p, _i32p, _dp, _dp]),
     "rails_sprhs_create": (C.c_int, [_vp, C.c_int64, C.c_int, _i64p, _i32p, _dp, C.POINTER(_vp)]),

@@ -1,0 +1,671 @@
+// itsolve.hip -- A^-1 X (or A^-T X) by an iteration that stays on the device, as a library object: the approximate inverse the reference
+// allows for its inverse and extended Krylov projections (matlab/RAILSsolver.m:19-23, opts.Ainv: "This can be approximate") where a
+// sparse LU (splu.hip) is latency-bound or cannot be formed at all.  Conjugate gradients for a definite operator of either sign,
+// BiCGStab (right-preconditioned) for a general one, both with an optional Jacobi preconditioner.
+//
+// Every column is a system of its own with its own scalars (rails_iter_col, iter_scalars.h) in a device block the object owns: no block
+// method, no small matrix on the host.  The iteration runs on work panels of the object (ordinary panels, window at column 0, so the
+// SpMM kernels see the layout they are tested on and the passes below always load 16 bytes); X's window is copied in, the result copied
+// out.  Solves of more than RAILS_ITER_GROUP columns run in groups.  The host queues `check_every` iterations, reads one number back
+// through pinned memory (how many columns are still active) and stops when that is zero or max_iterations have been queued; a column
+// that has stopped gets zero coefficients from the scalar step, so what is queued after it leaves its x alone and the result does not
+// depend on check_every.
+//
+// Passes: thread (tx, ty) of a block owns the column pair 2 tx, 2 tx + 1 and every TY-th row of its block's slab (k_colnorms2's shape,
+// dense.hip), adds its rows in increasing order, the TY row classes meet in an LDS tree of fixed shape, the per-block partial sums go to
+// the context workspace, and the one-workgroup kernel k_iter_scalars sums them over the blocks in a fixed order (iter_reduce) and then
+// computes the scalars (iter_compute) -- two device functions, so that an all-reduce can sit between them in a row-partitioned form.
+// No floating-point atomics: two runs give the same bits.
+#include "rails_internal.h"
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "iter_scalars.h"
+
+namespace {
+
+constexpr int RAILS_ITER_GROUP = 32; // columns per group: the widest panel every SpMM kernel takes in one chunk
+
+typedef double it_v2 __attribute__((ext_vector_type(2)));
+
+struct PassGeom {
+    int ncw;     // columns of the group
+    int ld;      // row stride of every work panel
+    int tx_bits; // TX = 1 << tx_bits threads along the column pairs, TY = 256 / TX along the rows
+    int64_t m, rows_per_slab;
+};
+
+enum { STEP_CG_INIT = 0, STEP_CG_ALPHA, STEP_CG_BETA, STEP_BI_INIT, STEP_BI_ALPHA, STEP_BI_OMEGA, STEP_BI_END };
+
+__device__ __forceinline__ it_v2 ld2(const double *p) { return *reinterpret_cast<const it_v2 *>(p); }
+__device__ __forceinline__ void st2(double *p, it_v2 v, bool has1)
+{
+    if (has1)
+        *reinterpret_cast<it_v2 *>(p) = v;
+    else
+        p[0] = v.x; // the last column of an odd width: its neighbour is padding and stays as it is
+}
+// y + a x where a != 0, y itself where a == 0 (a stopped column: not even a non-finite x may reach y)
+__device__ __forceinline__ it_v2 axpy_sel(it_v2 a, it_v2 x, it_v2 y)
+{
+    it_v2 o;
+    o.x = a.x != 0.0 ? fma(a.x, x.x, y.x) : y.x;
+    o.y = a.y != 0.0 ? fma(a.y, x.y, y.y) : y.y;
+    return o;
+}
+
+// The shape every pass shares.  body(row, offset of the pair in a work panel, has1, acc) streams one row of one column pair and adds to
+// acc[0 .. NQ); the partial sums of block b land in partial[(b * NQ + q) * ncw + column].
+template <int NQ, class Body>
+__device__ __forceinline__ void iter_pass(const PassGeom &g, double *__restrict__ partial, Body body)
+{
+    __shared__ double sh[NQ > 0 ? NQ : 1][256][2];
+    const int TX = 1 << g.tx_bits, TY = 256 >> g.tx_bits;
+    const int tx = threadIdx.x & (TX - 1), ty = threadIdx.x >> g.tx_bits;
+    const int c = 2 * tx;
+    const bool has0 = c < g.ncw, has1 = c + 1 < g.ncw;
+    const int64_t r_begin = (int64_t)blockIdx.x * g.rows_per_slab;
+    const int64_t r_end = r_begin + g.rows_per_slab < g.m ? r_begin + g.rows_per_slab : g.m;
+    it_v2 acc[NQ > 0 ? NQ : 1];
+#pragma unroll
+    for (int q = 0; q < (NQ > 0 ? NQ : 1); ++q) acc[q] = (it_v2){0.0, 0.0};
+    if (has0) {
+#pragma unroll 4
+        for (int64_t r = r_begin + ty; r < r_end; r += TY) body(r, r * g.ld + c, has1, acc);
+    }
+    if (NQ == 0) return;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        sh[q][threadIdx.x][0] = acc[q].x;
+        sh[q][threadIdx.x][1] = acc[q].y;
+    }
+    __syncthreads();
+    for (int half = TY >> 1; half > 0; half >>= 1) { // row class ty += row class ty + half: a tree of fixed shape
+        if (ty < half) {
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                sh[q][threadIdx.x][0] += sh[q][threadIdx.x + (half << g.tx_bits)][0];
+                sh[q][threadIdx.x][1] += sh[q][threadIdx.x + (half << g.tx_bits)][1];
+            }
+        }
+        __syncthreads();
+    }
+    if (ty == 0 && has0) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            double *dst = partial + ((int64_t)blockIdx.x * NQ + q) * g.ncw + c;
+            dst[0] = sh[q][tx][0];
+            if (has1) dst[1] = sh[q][tx][1];
+        }
+    }
+}
+
+#define ITER_COEF(name, field)                                                                                                                 \
+    const int cc__##name = 2 * (threadIdx.x & ((1 << g.tx_bits) - 1));                                                                          \
+    const it_v2 name = {cc__##name < g.ncw ? cols[cc__##name].field : 0.0, cc__##name + 1 < g.ncw ? cols[cc__##name + 1].field : 0.0}
+
+// CG start (r = b is in R): z = D^-1 r, p = z, x = 0; partial sums of r.z and r.r
+template <bool JAC>
+__global__ __launch_bounds__(256) void k_cg_init(PassGeom g, const double *__restrict__ dinv, const double *__restrict__ R, double *__restrict__ Z,
+                                                 double *__restrict__ P, double *__restrict__ Xw, double *__restrict__ partial)
+{
+    iter_pass<2>(g, partial, [&](int64_t row, int64_t o, bool has1, it_v2 *acc) {
+        const it_v2 r = ld2(R + o);
+        it_v2 z = r;
+        if (JAC) {
+            z = r * dinv[row];
+            st2(Z + o, z, has1);
+        }
+        st2(P + o, z, has1);
+        st2(Xw + o, (it_v2){0.0, 0.0}, has1);
+        acc[0] += r * z;
+        acc[1] += r * r;
+    });
+}
+
+// BiCGStab start (r = b is in R): r^ = r, x = p = v = 0; partial sums of r.r twice (rho = r^.r = b.b)
+__global__ __launch_bounds__(256) void k_bi_init(PassGeom g, const double *__restrict__ R, double *__restrict__ RH, double *__restrict__ P,
+                                                 double *__restrict__ V, double *__restrict__ Xw, double *__restrict__ partial)
+{
+    iter_pass<2>(g, partial, [&](int64_t, int64_t o, bool has1, it_v2 *acc) {
+        const it_v2 r = ld2(R + o), zero = {0.0, 0.0};
+        st2(RH + o, r, has1);
+        st2(P + o, zero, has1);
+        st2(V + o, zero, has1);
+        st2(Xw + o, zero, has1);
+        acc[0] += r * r;
+        acc[1] += r * r;
+    });
+}
+
+// per-column inner products of one or two panel pairs: a1.b1 [, a2.b2]
+template <int NP>
+__global__ __launch_bounds__(256) void k_iter_dots(PassGeom g, const double *__restrict__ A1, const double *__restrict__ B1, const double *A2,
+                                                   const double *B2, double *__restrict__ partial)
+{
+    iter_pass<NP>(g, partial, [&](int64_t, int64_t o, bool, it_v2 *acc) {
+        acc[0] += ld2(A1 + o) * ld2(B1 + o);
+        if (NP == 2) acc[1] += ld2(A2 + o) * ld2(B2 + o);
+    });
+}
+
+// CG: x += alpha p, r -= alpha q, z = D^-1 r; partial sums of r.z and r.r
+template <bool JAC>
+__global__ __launch_bounds__(256) void k_cg_update(PassGeom g, const rails_iter_col *__restrict__ cols, const double *__restrict__ dinv,
+                                                   const double *__restrict__ P, const double *__restrict__ Q, double *__restrict__ Xw,
+                                                   double *__restrict__ R, double *__restrict__ Z, double *__restrict__ partial)
+{
+    ITER_COEF(alpha, alpha);
+    iter_pass<2>(g, partial, [&](int64_t row, int64_t o, bool has1, it_v2 *acc) {
+        const it_v2 x = axpy_sel(alpha, ld2(P + o), ld2(Xw + o));
+        const it_v2 r = axpy_sel(-alpha, ld2(Q + o), ld2(R + o));
+        st2(Xw + o, x, has1);
+        st2(R + o, r, has1);
+        it_v2 z = r;
+        if (JAC) {
+            z = r * dinv[row];
+            st2(Z + o, z, has1);
+        }
+        acc[0] += r * z;
+        acc[1] += r * r;
+    });
+}
+
+// CG: p = z + beta p (Z is R without the preconditioner)
+__global__ __launch_bounds__(256) void k_cg_dir(PassGeom g, const rails_iter_col *__restrict__ cols, const double *__restrict__ Z, double *__restrict__ P)
+{
+    ITER_COEF(beta, beta);
+    iter_pass<0>(g, nullptr, [&](int64_t, int64_t o, bool has1, it_v2 *) { st2(P + o, axpy_sel(beta, ld2(P + o), ld2(Z + o)), has1); });
+}
+
+// BiCGStab: p = r + beta (p - omega v), p^ = D^-1 p
+template <bool JAC>
+__global__ __launch_bounds__(256) void k_bi_dir(PassGeom g, const rails_iter_col *__restrict__ cols, const double *__restrict__ dinv,
+                                                const double *__restrict__ R, const double *__restrict__ V, double *__restrict__ P,
+                                                double *__restrict__ PH)
+{
+    ITER_COEF(beta, beta);
+    ITER_COEF(omega, omega);
+    iter_pass<0>(g, nullptr, [&](int64_t row, int64_t o, bool has1, it_v2 *) {
+        const it_v2 p = axpy_sel(beta, axpy_sel(-omega, ld2(V + o), ld2(P + o)), ld2(R + o));
+        st2(P + o, p, has1);
+        if (JAC) st2(PH + o, p * dinv[row], has1);
+    });
+}
+
+// BiCGStab: s = r - alpha v (kept in R), s^ = D^-1 s
+template <bool JAC>
+__global__ __launch_bounds__(256) void k_bi_s(PassGeom g, const rails_iter_col *__restrict__ cols, const double *__restrict__ dinv,
+                                              const double *__restrict__ V, double *__restrict__ R, double *__restrict__ SH)
+{
+    ITER_COEF(alpha, alpha);
+    iter_pass<0>(g, nullptr, [&](int64_t row, int64_t o, bool has1, it_v2 *) {
+        const it_v2 s = axpy_sel(-alpha, ld2(V + o), ld2(R + o));
+        st2(R + o, s, has1);
+        if (JAC) st2(SH + o, s * dinv[row], has1);
+    });
+}
+
+// BiCGStab: x += alpha p^ + omega s^, r = s - omega t; partial sums of r^.r and r.r.  Without the preconditioner PH is P and SH is R.
+__global__ __launch_bounds__(256) void k_bi_update(PassGeom g, const rails_iter_col *__restrict__ cols, const double *PH, const double *SH,
+                                                   const double *__restrict__ T, const double *__restrict__ RH, double *__restrict__ Xw, double *R,
+                                                   double *__restrict__ partial)
+{
+    ITER_COEF(alpha, alpha);
+    ITER_COEF(omega, omega);
+    iter_pass<2>(g, partial, [&](int64_t, int64_t o, bool has1, it_v2 *acc) {
+        const it_v2 x = axpy_sel(omega, ld2(SH + o), axpy_sel(alpha, ld2(PH + o), ld2(Xw + o)));
+        const it_v2 r = axpy_sel(-omega, ld2(T + o), ld2(R + o));
+        st2(Xw + o, x, has1);
+        st2(R + o, r, has1);
+        acc[0] += ld2(RH + o) * r;
+        acc[1] += r * r;
+    });
+}
+
+// sums[e] = sum over the blocks of partial[block][e], e < n <= 64, in a fixed order: 16 interleaved strands, then the strands 0..15
+__device__ __forceinline__ void iter_reduce(const double *__restrict__ partial, int64_t nslab, int n, double *sums)
+{
+    __shared__ double sh[16][64];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    double s = 0.0;
+    if (tx < n)
+        for (int64_t t = ty; t < nslab; t += 16) s += partial[t * n + tx];
+    sh[ty][tx] = s;
+    __syncthreads();
+    if (ty == 0) {
+        double r = 0.0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) r += sh[k][tx];
+        sums[tx] = tx < n ? r : 0.0;
+    }
+    __syncthreads();
+}
+
+// the scalar step of column j from the reduced sums (q0 = sums[j], q1 = sums[ncw + j])
+__device__ __forceinline__ void iter_compute(int step, rails_iter_col &c, double q0, double q1, double tol2, int maxit, double sign)
+{
+    switch (step) {
+    case STEP_CG_INIT: rails_iter_start(c, q1, q0, maxit); break;
+    case STEP_CG_ALPHA: rails_iter_cg_alpha(c, q0, sign); break;
+    case STEP_CG_BETA: rails_iter_cg_beta(c, q0, q1, tol2, maxit); break;
+    case STEP_BI_INIT: rails_iter_start(c, q1, q0, maxit); break;
+    case STEP_BI_ALPHA: rails_iter_bi_alpha(c, q0); break;
+    case STEP_BI_OMEGA: rails_iter_bi_omega(c, q0, q1); break;
+    default: rails_iter_bi_end(c, q0, q1, tol2, maxit); break;
+    }
+}
+
+// one workgroup: reduce, compute, count.  status[0] = active columns, status[1] = columns whose right-hand side is not finite (start only)
+__global__ __launch_bounds__(1024) void k_iter_scalars(int step, const double *__restrict__ partial, int64_t nslab, int ncw, int nq,
+                                                       rails_iter_col *cols, int32_t *status, double tol2, int maxit, double sign)
+{
+    __shared__ double sums[64];
+    iter_reduce(partial, nslab, nq * ncw, sums);
+    if ((int)threadIdx.x < ncw) {
+        rails_iter_col c = cols[threadIdx.x];
+        iter_compute(step, c, sums[threadIdx.x], nq == 2 ? sums[ncw + threadIdx.x] : 0.0, tol2, maxit, sign);
+        cols[threadIdx.x] = c;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && (step == STEP_CG_INIT || step == STEP_BI_INIT || step == STEP_CG_BETA || step == STEP_BI_END)) {
+        int active = 0, bad = 0;
+        for (int j = 0; j < ncw; ++j) {
+            active += (cols[j].flags & RAILS_ITER_ACTIVE) ? 1 : 0;
+            bad += (cols[j].flags & RAILS_ITER_NONFINITE) ? 1 : 0;
+        }
+        status[0] = active;
+        if (step == STEP_CG_INIT || step == STEP_BI_INIT) status[1] = bad;
+    }
+}
+
+enum { W_X = 0, W_R, W_P, W_Q, W_Z, W_RH, W_T, W_SH, W_COUNT }; // CG: x r p q [z]; BiCGStab: x r p v(=Q) [p^(=Z)] r^ t [s^]
+
+} // namespace
+
+struct rails_iter {
+    rails_ctx *ctx = nullptr;
+    rails_csr *A = nullptr;
+    int method = 0;
+    int64_t m = 0;
+    double *dinv = nullptr; // 1 / diagonal (null: no preconditioner available)
+    double defsign = 1.0;   // -1 when every diagonal entry is known and negative (CG without the preconditioner, iter_scalars.h)
+    double tol = 1e-10;
+    int maxit = 1000, jacobi = 1, check_every = 8, strict = 0;
+    rails_panel *w[W_COUNT] = {};
+    int work_cols = 0;
+    rails_iter_col *cols_dev = nullptr;
+    int cols_cap = 0;
+    int32_t *status_dev = nullptr;
+    void *pinned = nullptr;
+    size_t pinned_bytes = 0;
+    std::vector<rails_iter_col> last; // the columns of the last solve
+    // statistics: last solve, totals
+    long last_dots = 0, last_launches = 0, last_products = 0;
+    double tot_solves = 0, tot_iterations = 0, tot_flagged = 0, tot_products = 0, tot_columns = 0;
+};
+
+namespace {
+
+void release_work(rails_iter *it)
+{
+    for (rails_panel *&p : it->w) {
+        rails_panel_destroy(p);
+        p = nullptr;
+    }
+    it->work_cols = 0;
+}
+
+bool uses_panel(const rails_iter *it, int which)
+{
+    const bool jac = it->dinv != nullptr;
+    if (it->method == RAILS_ITER_CG) return which == W_X || which == W_R || which == W_P || which == W_Q || (which == W_Z && jac);
+    return which == W_X || which == W_R || which == W_P || which == W_Q || which == W_RH || which == W_T || ((which == W_Z || which == W_SH) && jac);
+}
+
+int grow_work(rails_ctx *c, rails_iter *it, int cols)
+{
+    if (cols <= it->work_cols) return RAILS_OK;
+    release_work(it);
+    for (int k = 0; k < W_COUNT; ++k)
+        if (uses_panel(it, k)) {
+            RAILS_TRY(rails_panel_create(c, it->m, cols, &it->w[k]));
+            RAILS_HIP_CHECK(hipMemsetAsync(it->w[k]->d, 0, (size_t)it->m * it->w[k]->ld * sizeof(double), c->stream));
+        }
+    it->work_cols = cols;
+    return RAILS_OK;
+}
+
+int grow_cols(rails_ctx *c, rails_iter *it, int nc)
+{
+    if (nc > it->cols_cap) {
+        RAILS_HIP_CHECK(hipStreamSynchronize(c->stream));
+        if (it->cols_dev) RAILS_HIP_CHECK(hipFree(it->cols_dev));
+        it->cols_dev = nullptr;
+        it->cols_cap = 0;
+        const int cap = (nc + 31) / 32 * 32;
+        RAILS_HIP_CHECK(hipMalloc((void **)&it->cols_dev, (size_t)cap * sizeof(rails_iter_col)));
+        it->cols_cap = cap;
+        c->n_dev_alloc++;
+    }
+    const size_t want = 64 + (size_t)it->cols_cap * sizeof(rails_iter_col);
+    if (want > it->pinned_bytes) {
+        RAILS_HIP_CHECK(hipStreamSynchronize(c->stream));
+        if (it->pinned) RAILS_HIP_CHECK(hipHostFree(it->pinned));
+        it->pinned = nullptr;
+        it->pinned_bytes = 0;
+        RAILS_HIP_CHECK(hipHostMalloc(&it->pinned, want, hipHostMallocDefault));
+        it->pinned_bytes = want;
+    }
+    return RAILS_OK;
+}
+
+struct Run {
+    rails_ctx *c;
+    rails_iter *it;
+    int trans;
+    PassGeom g;
+    int64_t nslab;
+    rails_iter_col *cols;
+    bool jac;
+    double tol2;
+
+    double *d(int k) const { return it->w[k]->d; }
+    int scalars(int step, int nq)
+    {
+        RAILS_LAUNCH(k_iter_scalars, dim3(1), dim3(1024), 0, c->stream, step, c->ws, nslab, g.ncw, nq, cols, it->status_dev, tol2, it->maxit,
+                     jac ? 1.0 : it->defsign);
+        it->last_launches++;
+        return RAILS_OK;
+    }
+    int product(int from, int to)
+    {
+        it->last_products++;
+        return rails_spmm(c, it->A, it->method == RAILS_ITER_CG ? 0 : trans, it->w[from], 0, g.ncw, it->w[to], 0); // CG: a symmetric operator
+    }
+    int dots(int np, int a1, int b1, int a2, int b2)
+    {
+        RAILS_TRY(rails_ws_reserve(c, (size_t)nslab * 2 * g.ncw * sizeof(double)));
+        if (np == 1)
+            RAILS_LAUNCH((k_iter_dots<1>), dim3((unsigned)nslab), dim3(256), 0, c->stream, g, d(a1), d(b1), d(a1), d(b1), c->ws);
+        else
+            RAILS_LAUNCH((k_iter_dots<2>), dim3((unsigned)nslab), dim3(256), 0, c->stream, g, d(a1), d(b1), d(a2), d(b2), c->ws);
+        it->last_launches++;
+        it->last_dots += np * g.ncw;
+        return RAILS_OK;
+    }
+#define ITER_PASS_LAUNCH(kernel_jac, kernel_plain, ...)                                                                                      \
+    do {                                                                                                                                     \
+        RAILS_TRY(rails_ws_reserve(c, (size_t)nslab * 2 * g.ncw * sizeof(double)));                                                          \
+        if (jac)                                                                                                                             \
+            RAILS_LAUNCH(kernel_jac, dim3((unsigned)nslab), dim3(256), 0, c->stream, __VA_ARGS__);                                          \
+        else                                                                                                                                 \
+            RAILS_LAUNCH(kernel_plain, dim3((unsigned)nslab), dim3(256), 0, c->stream, __VA_ARGS__);                                        \
+        it->last_launches++;                                                                                                                 \
+    } while (0)
+
+    int start()
+    {
+        if (it->method == RAILS_ITER_CG) {
+            ITER_PASS_LAUNCH((k_cg_init<true>), (k_cg_init<false>), g, it->dinv, d(W_R), jac ? d(W_Z) : nullptr, d(W_P), d(W_X), c->ws);
+            it->last_dots += 2 * g.ncw;
+            return scalars(STEP_CG_INIT, 2);
+        }
+        ITER_PASS_LAUNCH(k_bi_init, k_bi_init, g, d(W_R), d(W_RH), d(W_P), d(W_Q), d(W_X), c->ws);
+        it->last_dots += 2 * g.ncw;
+        return scalars(STEP_BI_INIT, 2);
+    }
+    int iteration()
+    {
+        if (it->method == RAILS_ITER_CG) {
+            const int z = jac ? W_Z : W_R;
+            RAILS_TRY(product(W_P, W_Q));
+            RAILS_TRY(dots(1, W_P, W_Q, W_P, W_Q));
+            RAILS_TRY(scalars(STEP_CG_ALPHA, 1));
+            ITER_PASS_LAUNCH((k_cg_update<true>), (k_cg_update<false>), g, cols, it->dinv, d(W_P), d(W_Q), d(W_X), d(W_R), jac ? d(W_Z) : nullptr, c->ws);
+            it->last_dots += 2 * g.ncw;
+            RAILS_TRY(scalars(STEP_CG_BETA, 2));
+            ITER_PASS_LAUNCH(k_cg_dir, k_cg_dir, g, cols, d(z), d(W_P));
+            return RAILS_OK;
+        }
+        const int ph = jac ? W_Z : W_P, sh = jac ? W_SH : W_R;
+        ITER_PASS_LAUNCH((k_bi_dir<true>), (k_bi_dir<false>), g, cols, it->dinv, d(W_R), d(W_Q), d(W_P), jac ? d(W_Z) : nullptr);
+        RAILS_TRY(product(ph, W_Q)); // v = A p^
+        RAILS_TRY(dots(1, W_RH, W_Q, W_RH, W_Q));
+        RAILS_TRY(scalars(STEP_BI_ALPHA, 1));
+        ITER_PASS_LAUNCH((k_bi_s<true>), (k_bi_s<false>), g, cols, it->dinv, d(W_Q), d(W_R), jac ? d(W_SH) : nullptr);
+        RAILS_TRY(product(sh, W_T)); // t = A s^
+        RAILS_TRY(dots(2, W_T, W_R, W_T, W_T));
+        RAILS_TRY(scalars(STEP_BI_OMEGA, 2));
+        ITER_PASS_LAUNCH(k_bi_update, k_bi_update, g, cols, d(ph), d(sh), d(W_T), d(W_RH), d(W_X), d(W_R), c->ws);
+        it->last_dots += 2 * g.ncw;
+        return scalars(STEP_BI_END, 2);
+    }
+#undef ITER_PASS_LAUNCH
+};
+
+} // namespace
+
+extern "C" void rails_iter_destroy(rails_iter *it)
+{
+    if (!it) return;
+    if (it->ctx) {
+        hipSetDevice(it->ctx->device);
+        hipStreamSynchronize(it->ctx->stream);
+    }
+    release_work(it);
+    hipFree(it->dinv);
+    hipFree(it->cols_dev);
+    hipFree(it->status_dev);
+    if (it->pinned) hipHostFree(it->pinned);
+    delete it;
+}
+
+extern "C" int rails_iter_create(rails_ctx *c, rails_csr *A, int method, const double *diag_host, rails_iter **out)
+{
+    if (c) hipSetDevice(c->device);
+    RAILS_REQUIRE(c && A && out, "rails_iter_create: null argument");
+    RAILS_REQUIRE(method == RAILS_ITER_CG || method == RAILS_ITER_BICGSTAB, "rails_iter_create: method %d is neither RAILS_ITER_CG nor RAILS_ITER_BICGSTAB", method);
+    RAILS_REQUIRE(c == A->ctx, "rails_iter_create: the operator belongs to another context");
+    RAILS_REQUIRE(c->nranks == 1 && !c->rccl, "rails_iter_create: single GPU only (the context has a partition or a communicator)");
+    RAILS_REQUIRE(!A->rect && !A->sprhs && A->ncols_ext == A->m, "rails_iter_create: the operator is rectangular (%lld x %lld)", (long long)A->m,
+                  (long long)rails_csr_cols(A));
+    RAILS_REQUIRE(A->m >= 1, "rails_iter_create: an operator without rows");
+    const int64_t m = A->m;
+    std::vector<double> dinv;
+    if (diag_host) {
+        dinv.assign(diag_host, diag_host + m);
+        for (int64_t i = 0; i < m; ++i)
+            RAILS_REQUIRE(dinv[i] != 0.0 && rails_iter_finite(dinv[i]), "rails_iter_create: diagonal entry %lld is %g", (long long)i, dinv[i]);
+    } else if (!A->apply_cb && !A->lu && !A->iter && (int64_t)A->h_rowptr.size() == m + 1 && (int64_t)A->h_val.size() == A->h_rowptr[m]) {
+        // the CSR diagonal, when every entry of it is stored and nonzero; otherwise no preconditioner
+        dinv.assign((size_t)m, 0.0);
+        bool ok = true;
+        for (int64_t i = 0; i < m && ok; ++i) {
+            bool found = false;
+            for (int64_t q = A->h_rowptr[i]; q < A->h_rowptr[i + 1]; ++q)
+                if (A->h_col[q] == i) {
+                    dinv[i] += A->h_val[q];
+                    found = true;
+                }
+            ok = found && dinv[i] != 0.0 && rails_iter_finite(dinv[i]);
+        }
+        if (!ok) dinv.clear();
+    }
+    rails_iter *it = new rails_iter;
+    it->ctx = c;
+    it->A = A;
+    it->method = method;
+    it->m = m;
+    bool negative = !dinv.empty();
+    for (double &v : dinv) {
+        negative = negative && v < 0.0;
+        v = 1.0 / v;
+    }
+    it->defsign = negative ? -1.0 : 1.0;
+    hipError_t e = hipMalloc((void **)&it->status_dev, 16 * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemset(it->status_dev, 0, 16 * sizeof(int32_t));
+    if (e == hipSuccess && !dinv.empty()) {
+        e = hipMalloc((void **)&it->dinv, (size_t)m * sizeof(double));
+        if (e == hipSuccess) e = hipMemcpy(it->dinv, dinv.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) {
+        rails_set_error("rails_iter_create: device allocation or upload failed: %s", hipGetErrorString(e));
+        rails_iter_destroy(it);
+        return RAILS_EHIP;
+    }
+    *out = it;
+    return RAILS_OK;
+}
+
+extern "C" int rails_iter_set(rails_iter *it, const char *name, double value)
+{
+    RAILS_REQUIRE(it && name, "rails_iter_set: null argument");
+    RAILS_REQUIRE(rails_iter_finite(value), "rails_iter_set: %s = %g", name, value);
+    const std::string n(name);
+    if (n == "tolerance") {
+        RAILS_REQUIRE(value >= 0.0, "rails_iter_set: tolerance %g", value);
+        it->tol = value;
+    } else if (n == "max_iterations") {
+        RAILS_REQUIRE(value >= 0.0 && value <= 1e9, "rails_iter_set: max_iterations %g", value);
+        it->maxit = (int)value;
+    } else if (n == "jacobi")
+        it->jacobi = value != 0.0;
+    else if (n == "check_every") {
+        RAILS_REQUIRE(value >= 1.0 && value <= 1e9, "rails_iter_set: check_every %g", value);
+        it->check_every = (int)value;
+    } else if (n == "strict")
+        it->strict = value != 0.0;
+    else {
+        rails_set_error("rails_iter_set: no setting named '%s' (tolerance, max_iterations, jacobi, check_every, strict)", name);
+        return RAILS_EINVAL;
+    }
+    return RAILS_OK;
+}
+
+extern "C" int rails_iter_solve(rails_ctx *c, rails_iter *it, int trans, const rails_panel *X, int xc0, int nc, rails_panel *Y, int yc0)
+{
+    if (c) hipSetDevice(c->device);
+    rails_slow_guard slow__(c, "rails_iter_solve", nc, it ? it->m : 0);
+    RAILS_REQUIRE(c && it && X && Y, "rails_iter_solve: null argument");
+    RAILS_REQUIRE(c == it->ctx, "rails_iter_solve: the object belongs to another context");
+    RAILS_REQUIRE(c->nranks == 1 && !c->rccl, "rails_iter_solve: single GPU only (the context has a partition or a communicator)");
+    RAILS_REQUIRE(X->m == it->m && Y->m == it->m, "rails_iter_solve: the operator has %lld rows, X %lld, Y %lld", (long long)it->m, (long long)X->m,
+                  (long long)Y->m);
+    RAILS_REQUIRE(xc0 >= 0 && nc >= 0 && xc0 + nc <= X->cap && yc0 >= 0 && yc0 + nc <= Y->cap, "rails_iter_solve: column windows outside the panels");
+    if (X->d == Y->d) RAILS_REQUIRE(xc0 + nc <= yc0 || yc0 + nc <= xc0, "rails_iter_solve: X and Y windows alias");
+    it->last_dots = it->last_launches = it->last_products = 0;
+    it->last.clear();
+    if (nc == 0) return RAILS_OK;
+    RAILS_TRY(grow_work(c, it, std::min(nc, RAILS_ITER_GROUP)));
+    RAILS_TRY(grow_cols(c, it, nc));
+    int32_t *status = (int32_t *)it->pinned;
+    Run run;
+    run.c = c;
+    run.it = it;
+    run.trans = trans ? 1 : 0;
+    run.jac = it->jacobi && it->dinv;
+    run.tol2 = it->tol * it->tol;
+    for (int g0 = 0; g0 < nc; g0 += RAILS_ITER_GROUP) {
+        const int w = std::min(RAILS_ITER_GROUP, nc - g0);
+        const int pairs = (w + 1) / 2;
+        int tx_bits = 0;
+        while ((1 << tx_bits) < pairs) ++tx_bits; // <= 4
+        const int TY = 256 >> tx_bits;
+        // slabs of at least 8 rows per thread, at most 1024 of them (k_colnorms2's rule)
+        int64_t nslab = std::max<int64_t>(1, std::min<int64_t>(1024, it->m / ((int64_t)TY * 8)));
+        const int64_t rps = (it->m + nslab - 1) / nslab;
+        nslab = (it->m + rps - 1) / rps;
+        run.g = PassGeom{w, it->w[W_X]->ld, tx_bits, it->m, rps};
+        run.nslab = nslab;
+        run.cols = it->cols_dev + g0;
+        RAILS_TRY(rails_panel_copy(c, X, xc0 + g0, w, it->w[W_R], 0));
+        RAILS_TRY(run.start());
+        for (int queued = 0, first = 1;; first = 0) {
+            const int n = std::max(0, std::min(it->check_every, it->maxit - queued));
+            for (int k = 0; k < n; ++k) RAILS_TRY(run.iteration());
+            queued += n;
+            RAILS_HIP_CHECK(hipGetLastError());
+            RAILS_HIP_CHECK(hipMemcpyAsync(status, it->status_dev, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+            RAILS_HIP_CHECK(rails_stream_sync(c));
+            if (first && status[1] > 0) {
+                rails_set_error("rails_iter_solve: %d column(s) of the right-hand side in columns [%d, %d) are not finite", (int)status[1], g0, g0 + w);
+                return RAILS_EINVAL;
+            }
+            if (status[0] == 0 || queued >= it->maxit) break;
+        }
+        RAILS_TRY(rails_panel_copy(c, it->w[W_X], 0, w, Y, yc0 + g0));
+    }
+    rails_iter_col *host_cols = (rails_iter_col *)((char *)it->pinned + 64);
+    RAILS_HIP_CHECK(hipMemcpyAsync(host_cols, it->cols_dev, (size_t)nc * sizeof(rails_iter_col), hipMemcpyDeviceToHost, c->stream));
+    RAILS_HIP_CHECK(rails_stream_sync(c));
+    it->last.assign(host_cols, host_cols + nc);
+    int flagged = 0;
+    for (const rails_iter_col &col : it->last) {
+        it->tot_iterations += col.iter;
+        flagged += (col.flags & RAILS_ITER_CONVERGED) ? 0 : 1;
+    }
+    it->tot_solves += 1;
+    it->tot_columns += nc;
+    it->tot_flagged += flagged;
+    it->tot_products += it->last_products;
+    if (flagged && it->strict) {
+        rails_set_error("rails_iter_solve: %d of %d columns did not reach the tolerance %g (strict)", flagged, nc, it->tol);
+        return RAILS_ENOCONV;
+    }
+    return RAILS_OK;
+}
+
+// info[0] most iterations of a column in the last solve, [1] inner products of the last solve (per column and quantity), [2] kernel
+// launches of the library's own passes in it, [3] its columns that did not converge (any flag but converged), [4] those of them that
+// broke down, [5] worst relative residual of the recurrence, [6] work-panel columns, [7] products with A in the last solve; totals since
+// creation: [8] solves, [9] columns, [10] iterations summed over the columns, [11] flagged columns, [12] products with A.
+extern "C" int rails_iter_stats(const rails_iter *it, double *info, int cap)
+{
+    RAILS_REQUIRE(it && info && cap >= 0, "rails_iter_stats: bad argument");
+    double most = 0, unconv = 0, broke = 0, worst = 0;
+    for (const rails_iter_col &c : it->last) {
+        most = std::max(most, (double)c.iter);
+        if (!(c.flags & RAILS_ITER_CONVERGED)) unconv += 1;
+        if (c.flags & RAILS_ITER_BREAKDOWN) broke += 1;
+        const double rel = c.bb > 0.0 ? std::sqrt(c.rr / c.bb) : 0.0;
+        if (!(rel <= worst)) worst = rel; // a NaN shows
+    }
+    const double v[13] = {most, (double)it->last_dots, (double)it->last_launches, unconv, broke, worst, (double)it->work_cols, (double)it->last_products,
+                          it->tot_solves, it->tot_columns, it->tot_iterations, it->tot_flagged, it->tot_products};
+    const int k = std::min(cap, 13);
+    for (int i = 0; i < k; ++i) info[i] = v[i];
+    return k;
+}
+
+// per column of the last solve: iterations, relative residual of the recurrence, flags (RAILS_ITER_* of iter_scalars.h: 2 converged,
+// 4 stopped at max_iterations, 8 breakdown, 16 non-finite).  Returns the number of columns of the last solve; at most cap are written.
+extern "C" int rails_iter_columns(const rails_iter *it, int32_t *iterations, double *relres, int32_t *flags, int cap)
+{
+    RAILS_REQUIRE(it && cap >= 0, "rails_iter_columns: bad argument");
+    const int n = (int)it->last.size();
+    for (int j = 0; j < std::min(n, cap); ++j) {
+        const rails_iter_col &c = it->last[j];
+        if (iterations) iterations[j] = c.iter;
+        if (relres) relres[j] = c.bb > 0.0 ? std::sqrt(c.rr / c.bb) : 0.0;
+        if (flags) flags[j] = c.flags;
+    }
+    return n;
+}
+
+extern "C" int rails_csr_create_iter(rails_ctx *c, rails_iter *it, rails_csr **out)
+{
+    RAILS_REQUIRE(c && it && out, "rails_csr_create_iter: null argument");
+    RAILS_REQUIRE(c == it->ctx, "rails_csr_create_iter: the object belongs to another context");
+    RAILS_REQUIRE(c->nranks == 1 && !c->rccl, "rails_csr_create_iter: single GPU only (the context has a partition or a communicator)");
+    rails_csr *A = new rails_csr();
+    A->ctx = c;
+    A->m = it->m;
+    A->ncols_ext = it->m;
+    A->iter = it;
+    A->last_kernel = it->method == RAILS_ITER_CG ? "iter_cg" : "iter_bicgstab";
+    *out = A;
+    return RAILS_OK;
+}

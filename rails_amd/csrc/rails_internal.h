@@ -179,6 +179,8 @@ struct rails_csr {
     rails_lu *lu = nullptr;
     // operator that applies a sparse right-hand side (rails_csr_create_sprhs, sprhs.hip): rails_spmm is rails_sprhs_apply; the caller owns the object
     rails_sprhs *sprhs = nullptr;
+    // operator that solves with A by iteration (rails_csr_create_iter, itsolve.hip): rails_spmm is rails_iter_solve; the caller owns the object
+    rails_iter *iter = nullptr;
 };
 
 // Sparse right-hand side B (m x p) and its transpose, both as rectangular CSR operators on the device (sprhs.hip), and the host-made plan

@@ -606,6 +606,7 @@ extern "C" int rails_csr_set_halo(rails_csr *A, int64_t n_send, const int64_t *s
     RAILS_REQUIRE(A, "null operator");
     RAILS_REQUIRE(!A->lu, "rails_csr_set_halo: an LU solve operator is single GPU only");
     RAILS_REQUIRE(!A->sprhs, "rails_csr_set_halo: a sparse right-hand side is single GPU only");
+    RAILS_REQUIRE(!A->iter, "rails_csr_set_halo: an iterative solve operator is single GPU only");
     RAILS_REQUIRE(n_send >= 0 && n_ghost >= 0 && A->m + n_ghost == A->ncols_ext,
                   "rails_csr_set_halo: m_local %lld + ghosts %lld != extended columns %lld", (long long)A->m, (long long)n_ghost,
                   (long long)A->ncols_ext);
@@ -680,7 +681,7 @@ extern "C" int rails_csr_prepare(rails_ctx *c, rails_csr *A, int trans, int nc, 
 {
     RAILS_REQUIRE(c && A && nc >= 1, "rails_csr_prepare: bad argument");
     if (kernel_ready) *kernel_ready = 0;
-    if (A->apply_cb || A->lu || A->sprhs) return RAILS_OK;
+    if (A->apply_cb || A->lu || A->sprhs || A->iter) return RAILS_OK;
     if (trans) {
         RAILS_TRY(build_transpose(A));
         A->AT->variant = A->variant;
@@ -712,6 +713,7 @@ extern "C" int rails_spmm(rails_ctx *c, rails_csr *A, int trans, const rails_pan
     if (X->d == Y->d) RAILS_REQUIRE(xc0 + nc <= yc0 || yc0 + nc <= xc0, "rails_spmm: X and Y windows alias");
     if (nc == 0 || A->m == 0) return RAILS_OK;
     if (A->lu) return rails_lu_solve(c, A->lu, trans, X, xc0, nc, Y, yc0);
+    if (A->iter) return rails_iter_solve(c, A->iter, trans, X, xc0, nc, Y, yc0);
     if (A->apply_cb) {
         int rc = A->apply_cb(A->apply_user, trans ? 1 : 0, X, xc0, nc, Y, yc0);
         if (rc != 0) {

@@ -552,6 +552,18 @@ public:
         if (A && rails_csr_sprhs(A)) n_cols_ = rails_csr_cols(A);
     }
 
+    // A^-1 by iteration on the device (rails_iter, include/rails_hip.h): products with this operator are the solves, so it goes
+    // wherever the LU handle goes (Solver::set_inverse).  The wrapper owns the operator handle it makes; the caller keeps the rails_iter
+    // and the operator it iterates on alive.  Single GPU.
+    HipOperatorWrapper(rails_ctx *ctx, rails_iter *it) : ctx_(ctx ? ctx : default_context()), transpose_(false), m_global_(-1)
+    {
+        rails_csr *A = nullptr;
+        if (it && hip_ok(rails_csr_create_iter(ctx_, it, &A), "rails_csr_create_iter")) {
+            h_ = std::make_shared<CsrHandle>(ctx_, A);
+            m_global_ = rails_csr_rows(A);
+        }
+    }
+
     // The right-hand side B as an operator, m x p (rails_sprhs: the sparse form the reference's driver uses, src/main.cpp:67,98, through
     // src/MatrixOrMultiVectorWrapper.hpp).  The wrapper owns the operator handle it makes; the caller keeps S alive.  Single GPU.
     HipOperatorWrapper(rails_ctx *ctx, rails_sprhs *S) : ctx_(ctx ? ctx : default_context()), transpose_(false), m_global_(S ? rails_sprhs_rows(S) : -1)

@@ -1,0 +1,121 @@
+"""Iterative solves on the device as a library object (include/rails_hip.h: rails_iter_*, rails_amd/csrc/itsolve.hip): the approximate A^-1
+the reference allows for its inverse and extended Krylov projections (opts.Ainv of matlab/RAILSsolver.m:19-23, "This can be approximate")
+where a sparse LU is latency-bound or cannot be formed.  Conjugate gradients for a definite matrix, BiCGStab for a general one, Jacobi
+preconditioning; every column is a system of its own and all scalars stay on the device."""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import check
+from .wrappers import HipMultiVectorWrapper, HipOperatorWrapper, _Handle
+
+_dp, _i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+
+METHODS = {"cg": 1, "bicgstab": 2}
+FLAGS = {"active": 1, "converged": 2, "max_iterations": 4, "breakdown": 8, "nonfinite": 16}
+ENOCONV = -7
+
+
+class IterativeInverse:
+    """A^-1 by iteration.
+
+    A: a scipy sparse matrix, a (rowptr, col, val) CSR triple of a square matrix, or an operator wrapper (HipOperatorWrapper: a CSR
+    operator, a callback operator such as SchurOperator.op).  method: "cg", "bicgstab" or "auto" -- conjugate gradients when a matrix
+    equals its transpose, BiCGStab otherwise; for an operator wrapper the caller names the method.  diag: the diagonal for the Jacobi
+    preconditioner when A is an operator that is not a CSR matrix (None: the CSR diagonal where there is one).  `.op` is an operator handle
+    (HipOperatorWrapper) whose products are the solves: it goes wherever an operator goes (Solver.set_inverse, rails_spmm)."""
+
+    def __init__(self, ctx, A, method="auto", tol=1e-10, maxit=1000, jacobi=True, strict=False, diag=None, check_every=None):
+        self.ctx = ctx
+        self._owned = None
+        if isinstance(A, HipOperatorWrapper):
+            if method == "auto":
+                raise ValueError("IterativeInverse: name the method ('cg' or 'bicgstab') for an operator wrapper")
+            if A.trans:
+                raise ValueError("IterativeInverse: pass the operator itself and solve with trans=True")
+            self.A = A
+        else:
+            import scipy.sparse as sp
+
+            if isinstance(A, tuple):
+                rowptr, col, val = A
+                n = len(rowptr) - 1
+                A = sp.csr_matrix((val, col, rowptr), shape=(n, n))
+            A = sp.csr_matrix(A)
+            if A.shape[0] != A.shape[1]:
+                raise ValueError("IterativeInverse: A is %d x %d" % A.shape)
+            A.sort_indices()
+            if method == "auto":
+                method = "cg" if (A != A.T).nnz == 0 else "bicgstab"
+            self.A = self._owned = HipOperatorWrapper(ctx, A.indptr, A.indices, A.data)
+        if method not in METHODS:
+            raise ValueError("IterativeInverse: no method %r (cg, bicgstab, auto)" % (method,))
+        self.method = method
+        self.m = self.n = int(self.A.M())
+        d = None if diag is None else np.ascontiguousarray(diag, dtype=np.float64)
+        if d is not None and d.size != self.m:
+            raise ValueError("IterativeInverse: the diagonal has %d entries, the operator %d rows" % (d.size, self.m))
+        h = C.c_void_p()
+        check(ctx.lib.rails_iter_create(ctx.h, self.A.h.h, METHODS[method], d.ctypes.data_as(_dp) if d is not None else None, C.byref(h)), "rails_iter_create")
+        self.h = h
+        self.set("tolerance", tol)
+        self.set("max_iterations", maxit)
+        self.set("jacobi", 1 if jacobi else 0)
+        self.set("strict", 1 if strict else 0)
+        if check_every is not None:
+            self.set("check_every", check_every)
+        oh = C.c_void_p()
+        check(ctx.lib.rails_csr_create_iter(ctx.h, h, C.byref(oh)), "rails_csr_create_iter")
+        self.op = HipOperatorWrapper(ctx, None, None, None, _handle=_Handle(ctx, oh))
+        self.op.h._iter = self  # the solve object (and the operator it iterates on) outlives every copy of the handle
+
+    def set(self, name, value):
+        """"tolerance", "max_iterations", "jacobi", "check_every", "strict" (rails_iter_set)"""
+        check(self.ctx.lib.rails_iter_set(self.h, name.encode(), float(value)), "rails_iter_set")
+
+    def solve(self, X, Y=None, trans=False):
+        """Y = A^-1 X (trans: A^-T X; CG ignores it) for a HipMultiVectorWrapper X of m rows (a new one when Y is None); X is left
+        unchanged.  Columns that did not converge are flagged (columns()); with strict=True they raise."""
+        if Y is None:
+            Y = HipMultiVectorWrapper(self.ctx, self.m, X.n)
+        assert Y.n == X.n
+        check(self.ctx.lib.rails_iter_solve(self.ctx.h, self.h, 1 if trans else 0, X.panel.h, X.c0, X.n, Y.panel.h, Y.c0), "rails_iter_solve")
+        return Y
+
+    def solve_host(self, X, trans=False):
+        """the same on a host array (m x nc): upload, solve, download"""
+        X = np.asarray(X, dtype=np.float64)
+        X2 = X.reshape(X.shape[0], -1)
+        return self.solve(HipMultiVectorWrapper(self.ctx, data=X2), trans=trans).to_host().reshape(X.shape)
+
+    def stats(self):
+        """the last solve and the totals since creation (rails_iter_stats)"""
+        info = (C.c_double * 13)()
+        k = self.ctx.lib.rails_iter_stats(self.h, info, 13)
+        names = ("max_iterations_of_a_column", "inner_products", "launches", "unconverged_columns", "breakdown_columns", "worst_relative_residual",
+                 "workspace_columns", "products", "total_solves", "total_columns", "total_iterations", "total_flagged_columns", "total_products")
+        out = {names[i]: info[i] for i in range(max(k, 0))}
+        return {n: (v if n == "worst_relative_residual" else int(v)) for n, v in out.items()}
+
+    def columns(self):
+        """per column of the last solve: (iterations, relative residual of the recurrence, flags -- FLAGS)"""
+        n = self.ctx.lib.rails_iter_columns(self.h, None, None, None, 0)
+        it, rel, fl = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1)), np.zeros(max(n, 1), dtype=np.int32)
+        self.ctx.lib.rails_iter_columns(self.h, it.ctypes.data_as(_i32p), rel.ctypes.data_as(_dp), fl.ctypes.data_as(_i32p), n)
+        return it[:n], rel[:n], fl[:n]
+
+    def close(self):
+        if self.h:
+            if self.ctx.h:
+                self.op.h._iter = None
+                self.ctx.lib.rails_csr_destroy(self.op.h.h)
+                self.op.h.h = None
+                self.ctx.lib.rails_iter_destroy(self.h)
+            self.h = None
+            self._owned = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -2,6 +2,7 @@
 
     python -m rails_amd.main [params.xml] [--dir DIR] [--A A.mtx] [--B B.mtx] [--M M.mtx] [--V V.mtx] [--T T.mtx]
                                [--eigs K] [--variance FILE] [--sparse-B] [--warm-start V.mtx | --start-space S.mtx] [--restart-upon-start]
+                               [--inverse {lu,cg,bicgstab,iterative}] [--inverse-tol T]
     python -m torch.distributed.run --nproc-per-node N -m rails_amd.main ...      (one rank per GPU, rows partitioned)
 
 File names, formats and the parameter file follow the reference's driver (src/main.cpp:57-68,111,123-126): `A.mtx`, `B.mtx`
@@ -14,6 +15,11 @@ definite.
 `--sparse-B` keeps B sparse, as the reference's driver does (src/main.cpp:67 reads B.mtx as a CrsMatrix, :98 hands the operator to the
 solver): B.mtx is read as CSR and goes to the solver as a rails_amd.SparseRHS (one rank, direct back end); after a Schur reduction it
 keeps the rows of the Schur complement.
+
+`--inverse` chooses the A^-1 of a "Projection method" above 1 (opts.Ainv, matlab/RAILSsolver.m:19-23): `lu` (the default) a sparse LU
+factorised on the host and applied on the device, `cg` / `bicgstab` an iteration on the device to the relative tolerance `--inverse-tol`
+(rails_amd.IterativeInverse; the reference allows an approximate inverse), `iterative` conjugate gradients when A equals its transpose and
+BiCGStab otherwise.  A Schur-complement problem keeps the inverse of its Schur operator.
 
 `--eigs K` and `--variance FILE` are the second half of the reference's driver (src/main.cpp:140-170) on the solution object
 (rails_amd.Solution): the K eigenvalues of largest modulus of the covariance X, each next to its share of the trace, written to
@@ -57,6 +63,9 @@ def main(argv=None):
     ap.add_argument("--direct", action="store_true", help="direct back end (device panels for V, AV) instead of the default coordinate-space back end")
     ap.add_argument("--projected-lanczos", action="store_true", help="direct back end with the coefficient-space residual Lanczos (M = I only)")
     ap.add_argument("--sparse-B", action="store_true", help="keep B sparse (B.mtx in coordinate format): a device CSR operator instead of a dense panel; one rank")
+    ap.add_argument("--inverse", choices=("lu", "cg", "bicgstab", "iterative"), default="lu", help="the A^-1 of a 'Projection method' above 1: a sparse LU (default), "
+                                                                                                   "or an iteration on the device (iterative: CG for a symmetric A, BiCGStab otherwise)")
+    ap.add_argument("--inverse-tol", type=float, default=1e-10, metavar="T", help="relative tolerance of an iterative inverse (per column)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args(argv)
@@ -199,16 +208,22 @@ def main(argv=None):
     inverse = None
     if method > 1:
         if world > 1:
-            raise SystemExit("'Projection method' %g: the sparse LU inverse runs on one rank" % method)
+            raise SystemExit("'Projection method' %g: the %s inverse runs on one rank" % (method, "sparse LU" if args.inverse == "lu" else "iterative"))
         t0 = time.time()
         if schur is not None:
             inverse = schur.inverse()
             what = "Sinv, a sparse LU of the full matrix restricted to the %d Schur rows (matlab/RAILSschur.m:60-64)" % schur.m2
-        else:
+        elif args.inverse == "lu":
             inverse = rails_amd.SparseLU(ctx, (rowptr, col.astype(np.int32), val))
             what = "a sparse LU of A"
+        else:
+            inverse = rails_amd.IterativeInverse(ctx, (rowptr, col.astype(np.int32), val), method="auto" if args.inverse == "iterative" else args.inverse,
+                                                 tol=args.inverse_tol)
         solver.set_inverse(inverse)
-        _log(rank, "Projection method %g: A^-1 is %s; nnz(L+U) %d, factorised in %.2f s" % (method, what, inverse.nnz, time.time() - t0))
+        if isinstance(inverse, rails_amd.IterativeInverse):
+            _log(rank, "Projection method %g: A^-1 is an iterative solve on the device, method %s, Jacobi, tolerance %g" % (method, inverse.method, args.inverse_tol))
+        else:
+            _log(rank, "Projection method %g: A^-1 is %s; nnz(L+U) %d, factorised in %.2f s" % (method, what, inverse.nnz, time.time() - t0))
 
     if S0 is not None:
         if S0.shape[0] != m:
@@ -224,6 +239,10 @@ def main(argv=None):
     if schur is not None:
         _log(rank, "Amount of matrix-vector products after the solve: %d" % schur.applies)
     _log(rank, "solve returned %d after %d iterations in %.3f s: V is %d x %d, relative residual %.3e" % (code, solver.trips(), dt, m, solver.k, rel))
+    if isinstance(inverse, rails_amd.IterativeInverse):
+        st = inverse.stats()
+        _log(rank, "iterative inverse (%s): %d solves of %d columns, %d inner iterations in all, %d flagged columns" % (
+            inverse.method, st["total_solves"], st["total_columns"], st["total_iterations"], st["total_flagged_columns"]))
     if Nsp is not None:
         _log(rank, "nullspace: %d of %d columns kept" % (solver.nullspace_rank, Nsp.shape[1]))
     if S0 is not None:
