@@ -470,7 +470,7 @@ extern "C" int rails_iter_create(rails_ctx *c, rails_csr *A, int method, const d
     RAILS_REQUIRE(method == RAILS_ITER_CG || method == RAILS_ITER_BICGSTAB, "rails_iter_create: method %d is neither RAILS_ITER_CG nor RAILS_ITER_BICGSTAB", method);
     RAILS_REQUIRE(c == A->ctx, "rails_iter_create: the operator belongs to another context");
     RAILS_REQUIRE(c->nranks == 1 && !c->rccl, "rails_iter_create: single GPU only (the context has a partition or a communicator)");
-    RAILS_REQUIRE(!A->rect && !A->sprhs && A->ncols_ext == A->m, "rails_iter_create: the operator is rectangular (%lld x %lld)", (long long)A->m,
+    RAILS_REQUIRE(!A->rect && A->kind != rails_csr::SPRHS && A->ncols_ext == A->m, "rails_iter_create: the operator is rectangular (%lld x %lld)", (long long)A->m,
                   (long long)rails_csr_cols(A));
     RAILS_REQUIRE(A->m >= 1, "rails_iter_create: an operator without rows");
     const int64_t m = A->m;
@@ -479,7 +479,7 @@ extern "C" int rails_iter_create(rails_ctx *c, rails_csr *A, int method, const d
         dinv.assign(diag_host, diag_host + m);
         for (int64_t i = 0; i < m; ++i)
             RAILS_REQUIRE(dinv[i] != 0.0 && rails_iter_finite(dinv[i]), "rails_iter_create: diagonal entry %lld is %g", (long long)i, dinv[i]);
-    } else if (!A->apply_cb && !A->lu && !A->iter && (int64_t)A->h_rowptr.size() == m + 1 && (int64_t)A->h_val.size() == A->h_rowptr[m]) {
+    } else if (A->kind == rails_csr::STORED && (int64_t)A->h_rowptr.size() == m + 1 && (int64_t)A->h_val.size() == A->h_rowptr[m]) {
         // the CSR diagonal, when every entry of it is stored and nonzero; otherwise no preconditioner
         dinv.assign((size_t)m, 0.0);
         bool ok = true;
@@ -664,7 +664,8 @@ extern "C" int rails_csr_create_iter(rails_ctx *c, rails_iter *it, rails_csr **o
     A->ctx = c;
     A->m = it->m;
     A->ncols_ext = it->m;
-    A->iter = it;
+    A->kind = rails_csr::ITER;
+    A->delegate = it;
     A->last_kernel = it->method == RAILS_ITER_CG ? "iter_cg" : "iter_bicgstab";
     *out = A;
     return RAILS_OK;

@@ -172,15 +172,16 @@ struct rails_csr {
     int variant = 0;  // rails_csr_set_variant: the kernel rails_spmm is to take (0: its own choice)
     int is_grid = -1; // structured-grid stencil? (-1: not looked at yet; rails_csr_is_grid, spmm.hip)
     const char *last_kernel = "";
-    // operator given by its action (rails_csr_create_callback): rails_spmm hands the panels over
-    rails_apply_fn apply_cb = nullptr;
-    void *apply_user = nullptr;
-    // operator that solves with a sparse LU (rails_csr_create_lu, splu.hip): rails_spmm is rails_lu_solve; the caller owns the object
-    rails_lu *lu = nullptr;
-    // operator that applies a sparse right-hand side (rails_csr_create_sprhs, sprhs.hip): rails_spmm is rails_sprhs_apply; the caller owns the object
-    rails_sprhs *sprhs = nullptr;
-    // operator that solves with A by iteration (rails_csr_create_iter, itsolve.hip): rails_spmm is rails_iter_solve; the caller owns the object
-    rails_iter *iter = nullptr;
+    // What rails_spmm does with the operator: multiplies by the stored matrix, or hands the panels to a delegate -- the action given to
+    // rails_csr_create_callback (apply_fn with `delegate` as its user pointer), a sparse LU (rails_csr_create_lu, splu.hip: rails_lu_solve),
+    // a sparse right-hand side (rails_csr_create_sprhs, sprhs.hip: rails_sprhs_apply) or an iterative solve (rails_csr_create_iter,
+    // itsolve.hip: rails_iter_solve).  The caller owns the delegate object.
+    enum Kind { STORED, CALLBACK, LU, SPRHS, ITER } kind = STORED;
+    void *delegate = nullptr;
+    rails_apply_fn apply_fn = nullptr;
+    rails_lu *lu() const { return kind == LU ? static_cast<rails_lu *>(delegate) : nullptr; }
+    rails_sprhs *sprhs() const { return kind == SPRHS ? static_cast<rails_sprhs *>(delegate) : nullptr; }
+    rails_iter *iter() const { return kind == ITER ? static_cast<rails_iter *>(delegate) : nullptr; }
 };
 
 // Sparse right-hand side B (m x p) and its transpose, both as rectangular CSR operators on the device (sprhs.hip), and the host-made plan
@@ -266,12 +267,16 @@ int rails_rccl_halo(rails_ctx *c, const rails_csr *A, const double *send_buf, do
 void rails_rccl_release(rails_ctx *c);
 
 // ---- kernels / launchers across translation units ----
+// spmm.hip: the facts op_choice.h decides on, for a product of nc columns between windows of that alignment
+struct OpFacts;
+OpFacts rails_op_facts(const rails_ctx *c, const rails_csr *A, int nc, bool x_vec2, bool y_vec2);
 // spmm_sweep.hip: the sweep kernel for banded patterns; *done tells whether it computed the product
 int rails_spmm_sweep(rails_ctx *c, rails_csr *A, const double *X, int ldx, const double *Xg, int ldg, double *Y, int ldy, int nc, bool aligned,
                      bool force, bool *done);
 int rails_sweep_prepare(rails_ctx *c, rails_csr *A, int nc, bool *fits); // the schedule for nc columns, now
 void rails_sweep_release(rails_csr *A);
-// the interior rows of a row-partitioned operator as a sweep of their own (on stream st, beside the halo exchange)
+// the interior rows of a row-partitioned operator as a sweep of their own (on stream st, beside the halo exchange); aligned: X and Y rows
+// 16-byte aligned
 int rails_spmm_sweep_interior(rails_ctx *c, rails_csr *A, const double *X, int ldx, double *Y, int ldy, int nc, bool aligned, hipStream_t st, bool *done);
 int rails_sweep_prepare_interior(rails_ctx *c, rails_csr *A, int nc, bool *fits);
 // spmm_planes.hip: the plane-sweep kernel for structured-grid stencils; *done tells whether it computed the product

@@ -391,7 +391,8 @@ extern "C" int rails_csr_create_lu(rails_ctx *c, rails_lu *lu, rails_csr **out)
     A->ctx = c;
     A->m = lu->m_sub;
     A->ncols_ext = lu->m_sub;
-    A->lu = lu;
+    A->kind = rails_csr::LU;
+    A->delegate = lu;
     A->last_kernel = "lu";
     *out = A;
     return RAILS_OK;

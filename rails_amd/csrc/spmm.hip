@@ -8,7 +8,9 @@
 // contiguous row segment X[j, c0:c0+nc] -- a single 1 KiB wave-wide dwordx4 load at nc = 128.
 //
 // In this file: the operator object (create, destroy, halo set-up, transpose), the row kernels with their launchers, and the dispatcher
-// rails_spmm with the halo-overlapped order of a row-partitioned product.
+// rails_spmm in stages: check_windows, apply_delegate, exchange_halo / overlapped_product for a row-partitioned operator, local_product.
+// Which whole-operator kernel (sweep, planes, LDS-staged) a product tries before the row kernels, whether a row-partitioned product
+// overlaps its exchange, and what rails_csr_prepare builds ahead are decided in one place, op_choice.h.
 // Kernel 1 (row-gather): LPR lanes own one row; (col,val) of the row are group-uniform
 // (scalar loads when LPR == 64), U = 8 X-row loads are kept in flight per lane.  1b / 1c: its chunked and lean forms, see there.
 // Which of the three computes a product is decided in one place, row_choice.h.
@@ -17,6 +19,7 @@
 // column chunk and re-used by all rows of the block.
 // The sweep kernel for banded patterns is in spmm_sweep.hip, the plane-sweep kernel for grid stencils in spmm_planes.hip.
 #include "rails_internal.h"
+#include "op_choice.h"
 #include "row_choice.h"
 #include "tile_plan.h"
 
@@ -402,16 +405,24 @@ int dispatch_rg(rails_ctx *c, const rails_csr *A, int lpr, const double *X, int 
 // panels: (col, val) of a 64-row block staged in LDS instead of per-lane vector-memory loads -- kernel 1c where every X row is within
 // 32-bit byte offsets (0.24 vs 0.45 ms at 16 columns, 0.44 vs 0.71 ms at 32, banded pattern), kernel 1b otherwise
 // (RAILS_SPMM_NARROW_CC=0 disables both).
+struct NarrowEnv {
+    bool cc, fast;
+};
+const NarrowEnv &narrow_env() // (read once)
+{
+    static const NarrowEnv e = {spmm_env("RAILS_SPMM_NARROW_CC", 1) != 0, spmm_env("RAILS_SPMM_NARROW_FAST", 1) != 0};
+    return e;
+}
+
 RowFacts row_facts(const rails_csr *A, int nc, bool x_vec2, bool y_vec2, bool vec2, const double *X, int ldx, const double *Xg, int ldg, int span_ghost)
 {
-    static const int narrow_cc = spmm_env("RAILS_SPMM_NARROW_CC", 1), narrow_fast = spmm_env("RAILS_SPMM_NARROW_FAST", 1),
-                     chunk_env = spmm_env("RAILS_SPMM_CHUNK", 0);
+    static const int chunk_env = spmm_env("RAILS_SPMM_CHUNK", 0);
     RowFacts f;
     f.variant = A->variant; f.max_row_nnz = A->max_row_nnz; f.m = A->m; f.ncols_ext = A->ncols_ext; f.n_ghost = A->n_ghost; f.rect = A->rect;
     f.nc = nc; f.x_vec2 = x_vec2; f.y_vec2 = y_vec2; f.vec2 = vec2; f.ldx = ldx; f.ldg = ldg;
     f.xg_is_tail = Xg == X + (int64_t)A->m * ldx;
     f.span_ghost = span_ghost;
-    f.narrow_cc = narrow_cc != 0; f.narrow_fast = narrow_fast != 0; f.chunk_env = chunk_env;
+    f.narrow_cc = narrow_env().cc; f.narrow_fast = narrow_env().fast; f.chunk_env = chunk_env;
     return f;
 }
 
@@ -535,8 +546,9 @@ extern "C" int rails_csr_create_callback(rails_ctx *c, int64_t m_local, rails_ap
     A->ctx = c;
     A->m = m_local;
     A->ncols_ext = m_local;
-    A->apply_cb = fn;
-    A->apply_user = user;
+    A->kind = rails_csr::CALLBACK;
+    A->apply_fn = fn;
+    A->delegate = user;
     A->last_kernel = "callback";
     *out = A;
     return RAILS_OK;
@@ -604,9 +616,8 @@ extern "C" int rails_csr_set_halo(rails_csr *A, int64_t n_send, const int64_t *s
                                   void *user)
 {
     RAILS_REQUIRE(A, "null operator");
-    RAILS_REQUIRE(!A->lu, "rails_csr_set_halo: an LU solve operator is single GPU only");
-    RAILS_REQUIRE(!A->sprhs, "rails_csr_set_halo: a sparse right-hand side is single GPU only");
-    RAILS_REQUIRE(!A->iter, "rails_csr_set_halo: an iterative solve operator is single GPU only");
+    static const char *const single_gpu_only[] = {nullptr, nullptr, "an LU solve operator", "a sparse right-hand side", "an iterative solve operator"}; // by rails_csr::Kind
+    RAILS_REQUIRE(!single_gpu_only[A->kind], "rails_csr_set_halo: %s is single GPU only", single_gpu_only[A->kind]);
     RAILS_REQUIRE(n_send >= 0 && n_ghost >= 0 && A->m + n_ghost == A->ncols_ext,
                   "rails_csr_set_halo: m_local %lld + ghosts %lld != extended columns %lld", (long long)A->m, (long long)n_ghost,
                   (long long)A->ncols_ext);
@@ -661,68 +672,233 @@ static bool rails_csr_is_grid(rails_csr *A)
     return A->is_grid == 1;
 }
 
-// The sweep kernel as the automatic choice, from what is known without building its schedule: 64 to 256 columns in chunks of 16 that
-// divide the 32 workgroups of an XCD; the window of columns of a row fits (phases - 1) blocks of 2816 rows (the planner decides
-// exactly); every XCD's part holds a few blocks per phase; an X row is staged by at most 8 workgroups per row of the part (phases x
-// (1 + window / rows of a part): the launcher's own bound); and the pattern is not a structured-grid stencil -- few nonzeros per row
-// leave the sweep at its floor of one LDS-DMA latency per step and the LDS-staged box kernel is faster (7-point Laplacian 50 x 50 x
-// 400 at 128 columns: 0.65 ms against 0.82).
-static bool sweep_worthwhile(rails_csr *A, int nc)
+// The facts op_choice.h decides on.  RAILS_SPMM_HALO_OVERLAP and RAILS_SPMM_PLANES are read per product (the tests switch the first inside
+// one process), the other switches once.
+OpFacts rails_op_facts(const rails_ctx *c, const rails_csr *A, int nc, bool x_vec2, bool y_vec2)
 {
-    if (!(nc >= 64 && nc <= 256 && nc % 16 == 0 && 32 % (nc / 16) == 0 && A->n_ghost == 0 && A->window_rows > 0)) return false;
-    const int64_t phases = 32 / (nc / 16), part_rows = A->m / 8;
-    if (!(A->window_rows + 256 <= (phases - 1) * 2816 && A->m >= 8 * phases * 2816 &&
-          (double)phases * (double)(part_rows + A->window_rows + 1024) <= 8.0 * (double)part_rows))
-        return false;
-    return !rails_csr_is_grid(A);
+    OpFacts f;
+    f.variant = A->variant; f.max_row_nnz = A->max_row_nnz; f.m = A->m; f.ncols_ext = A->ncols_ext; f.n_ghost = A->n_ghost; f.rect = A->rect;
+    f.window_rows = A->window_rows; f.window_rows_int = A->window_rows_int; f.int_lo = A->int_lo; f.int_hi = A->int_hi;
+    f.nc = nc; f.x_vec2 = x_vec2; f.y_vec2 = y_vec2;
+    f.num_cu = c->num_cu;
+    f.planes = spmm_env("RAILS_SPMM_PLANES", 1) != 0; f.halo_overlap = spmm_env("RAILS_SPMM_HALO_OVERLAP", 1) != 0;
+    f.narrow_cc = narrow_env().cc; f.narrow_fast = narrow_env().fast;
+    return f;
 }
 
 extern "C" int rails_csr_prepare(rails_ctx *c, rails_csr *A, int trans, int nc, int *kernel_ready)
 {
     RAILS_REQUIRE(c && A && nc >= 1, "rails_csr_prepare: bad argument");
     if (kernel_ready) *kernel_ready = 0;
-    if (A->apply_cb || A->lu || A->sprhs || A->iter) return RAILS_OK;
+    if (A->kind != rails_csr::STORED) return RAILS_OK;
     if (trans) {
         RAILS_TRY(build_transpose(A));
         A->AT->variant = A->variant;
         return rails_csr_prepare(c, A->AT, 0, nc, kernel_ready);
     }
-    if (A->variant == 7 || (A->variant == 0 && sweep_worthwhile(A, nc))) {
-        bool fits = false;
-        RAILS_TRY(rails_sweep_prepare(c, A, nc, &fits));
-        if (kernel_ready) *kernel_ready = fits ? 1 : 0;
-    } else if (A->variant == 0 && A->n_ghost > 0 && !rails_csr_is_grid(A)) { // row-partitioned: the schedule of the interior rows
-        bool fits = false;
-        RAILS_TRY(rails_sweep_prepare_interior(c, A, nc, &fits));
-        if (kernel_ready) *kernel_ready = fits ? 1 : 0;
+    // what the products of that width would take, between aligned windows
+    bool fits = false;
+    switch (rails_prepare_choice(rails_op_facts(c, A, nc, true, true), [&] { return rails_csr_is_grid(A); })) {
+    case PrepareChoice::SWEEP: RAILS_TRY(rails_sweep_prepare(c, A, nc, &fits)); break;
+    case PrepareChoice::SWEEP_INTERIOR: RAILS_TRY(rails_sweep_prepare_interior(c, A, nc, &fits)); break; // row-partitioned: the schedule of the interior rows
+    case PrepareChoice::NONE: break;
     }
+    if (kernel_ready) *kernel_ready = fits ? 1 : 0;
     return RAILS_OK;
 }
 
-extern "C" int rails_spmm(rails_ctx *c, rails_csr *A, int trans, const rails_panel *X, int xc0, int nc, rails_panel *Y, int yc0)
+namespace {
+
+// One product's operands: the windows of X and Y, and where the columns beyond the operator's rows come from.
+struct Product {
+    const rails_panel *X;
+    rails_panel *Y;
+    int xc0, yc0, nc;
+    const double *Xp; // X->d + xc0
+    double *Yp;       // Y->d + yc0
+    const double *Xg; // ghost rows, leading dimension ldg
+    int ldg;
+};
+
+int check_windows(const rails_csr *A, int trans, const rails_panel *X, int xc0, int nc, const rails_panel *Y, int yc0)
 {
-    if (c) hipSetDevice(c->device); // allocations and launches go to the context's device whatever the caller's current device is
-    rails_slow_guard slow__(c, "rails_spmm", nc, A ? A->m : 0);
-    RAILS_REQUIRE(c && A && X && Y, "rails_spmm: null argument");
-    if (A->sprhs) return rails_sprhs_apply(c, A->sprhs, trans, X, xc0, nc, Y, yc0); // m x p: it checks the shapes of either direction itself
     RAILS_REQUIRE(xc0 >= 0 && nc >= 0 && xc0 + nc <= X->cap, "rails_spmm: X columns [%d,%d) outside capacity %d", xc0, xc0 + nc, X->cap);
     RAILS_REQUIRE(yc0 >= 0 && yc0 + nc <= Y->cap, "rails_spmm: Y columns [%d,%d) outside capacity %d", yc0, yc0 + nc, Y->cap);
     RAILS_REQUIRE(X->m == (A->rect ? A->ncols_ext : A->m) && Y->m == A->m, "rails_spmm: operator is %lld x %lld, X has %lld rows, Y %lld", (long long)A->m,
                   (long long)(A->rect ? A->ncols_ext : A->m), (long long)X->m, (long long)Y->m);
     RAILS_REQUIRE(!(A->rect && trans), "rails_spmm: a rectangular operator has no transposed apply (create the transposed matrix)");
     if (X->d == Y->d) RAILS_REQUIRE(xc0 + nc <= yc0 || yc0 + nc <= xc0, "rails_spmm: X and Y windows alias");
-    if (nc == 0 || A->m == 0) return RAILS_OK;
-    if (A->lu) return rails_lu_solve(c, A->lu, trans, X, xc0, nc, Y, yc0);
-    if (A->iter) return rails_iter_solve(c, A->iter, trans, X, xc0, nc, Y, yc0);
-    if (A->apply_cb) {
-        int rc = A->apply_cb(A->apply_user, trans ? 1 : 0, X, xc0, nc, Y, yc0);
+    return RAILS_OK;
+}
+
+// An operator that is not a stored matrix: the panels go to its delegate.
+int apply_delegate(rails_ctx *c, rails_csr *A, int trans, const rails_panel *X, int xc0, int nc, rails_panel *Y, int yc0)
+{
+    switch (A->kind) {
+    case rails_csr::SPRHS: return rails_sprhs_apply(c, A->sprhs(), trans, X, xc0, nc, Y, yc0);
+    case rails_csr::LU: return rails_lu_solve(c, A->lu(), trans, X, xc0, nc, Y, yc0);
+    case rails_csr::ITER: return rails_iter_solve(c, A->iter(), trans, X, xc0, nc, Y, yc0);
+    default: break;
+    }
+    int rc = A->apply_fn(A->delegate, trans ? 1 : 0, X, xc0, nc, Y, yc0);
+    if (rc != 0) {
+        rails_set_error("rails_spmm: the operator callback failed with code %d", rc);
+        return RAILS_ECOMM;
+    }
+    c->n_spmm_callback++;
+    return RAILS_OK;
+}
+
+// a device buffer of the operator that only grows (the stream may still read the old one)
+int grow_buffer(rails_ctx *c, double **buf, size_t *cap, size_t bytes)
+{
+    if (bytes <= *cap) return RAILS_OK;
+    RAILS_HIP_CHECK(rails_stream_sync(c));
+    if (*buf) RAILS_HIP_CHECK(hipFree(*buf));
+    *buf = nullptr;
+    RAILS_HIP_CHECK(hipMalloc((void **)buf, bytes));
+    *cap = bytes;
+    return RAILS_OK;
+}
+
+// Packs the rows the neighbours need and exchanges: afterwards (in stream order) A->ext holds the ghost rows, nc columns wide.
+int exchange_halo(rails_ctx *c, rails_csr *A, const double *Xp, int ldx, int nc)
+{
+    if (A->n_send) {
+        int64_t total = A->n_send * nc;
+        int grid = (int)std::min<int64_t>((total + 255) / 256, (int64_t)c->num_cu * 8);
+        RAILS_LAUNCH(k_pack_rows, dim3(grid), dim3(256), 0, c->stream, A->send_rows, A->n_send, Xp, ldx, nc, A->send_buf);
+    }
+    if (A->halo) {
+        int rc = A->halo(A->halo_user, A->send_buf, A->ext, nc, (void *)c->stream);
         if (rc != 0) {
-            rails_set_error("rails_spmm: the operator callback failed with code %d", rc);
+            rails_set_error("rails_spmm: halo hook failed with code %d", rc);
             return RAILS_ECOMM;
         }
-        c->n_spmm_callback++;
         return RAILS_OK;
     }
+    RAILS_REQUIRE(c->rccl, "rails_spmm: ghost rows but neither a halo hook nor an RCCL communicator");
+    return rails_rccl_halo(c, A, A->send_buf, A->ext, nc);
+}
+
+// From the fork on, the second stream may be writing Y: whichever way the product is left, the first stream waits for it, so that the
+// stream the caller synchronises covers every write (an error return must not leave the interior product in flight on panels the
+// caller is then free to release).  The normal exit has recorded and waited itself and calls joined().
+struct JoinGuard {
+    rails_ctx *c;
+    bool armed = true;
+    explicit JoinGuard(rails_ctx *ctx) : c(ctx) {}
+    void joined() { armed = false; }
+    ~JoinGuard()
+    {
+        if (!armed) return;
+        (void)hipEventRecord(c->ev_join, c->stream2); // (already on the way out with an error, or with one to come from the next call)
+        (void)hipStreamWaitEvent(c->stream, c->ev_join, 0);
+    }
+};
+
+// The row-partitioned product in the overlapped order: the interior rows' product runs on the context's second stream while the ghost rows
+// are packed, exchanged and waited for on the first; the boundary rows follow the exchange, and the first stream then waits for the
+// interior.  Row by row the same kernels as the serial order (`RAILS_SPMM_HALO_OVERLAP=0`): the result is bitwise the same.
+int overlapped_product(rails_ctx *c, rails_csr *A, const OpOrder &interior, const Product &p, bool x_vec2, bool y_vec2)
+{
+    const rails_panel *X = p.X, *Y = p.Y;
+    const int nc = p.nc;
+    RAILS_TRY(rails_ctx_second_stream(c));
+    RAILS_HIP_CHECK(hipEventRecord(c->ev_fork, c->stream));
+    JoinGuard join(c);
+    RAILS_HIP_CHECK(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
+    bool planes_done = false, sweep_done = false;
+    for (int i = 0; i < interior.n && !planes_done && !sweep_done; ++i) {
+        if (interior.step[i].kernel == OpStep::PLANES)
+            RAILS_TRY(rails_spmm_planes_interior(c, A, p.Xp, X->ld, p.Yp, Y->ld, nc, x_vec2, c->stream2, &planes_done));
+        else if (interior.step[i].kernel == OpStep::SWEEP)
+            RAILS_TRY(rails_spmm_sweep_interior(c, A, p.Xp, X->ld, p.Yp, Y->ld, nc, x_vec2 && y_vec2, c->stream2, &sweep_done));
+    }
+    if (!planes_done && !sweep_done) {
+        const RowSpan in = {A->int_lo, A->int_hi - A->int_lo, c->stream2};
+        RAILS_TRY(spmm_span(c, A, rails_row_choice(row_facts(A, nc, x_vec2, y_vec2, false, p.Xp, X->ld, p.Xp, X->ld, 0)), p.Xp, X->ld, p.Xp, X->ld, p.Yp, Y->ld, nc, in));
+    }
+    RAILS_HIP_CHECK(hipEventRecord(c->ev_join, c->stream2));
+    c->n_spmm_overlapped++;
+    RAILS_TRY(exchange_halo(c, A, p.Xp, X->ld, nc));
+    const RowSpan lo = {0, A->int_lo, nullptr}, hi = {A->int_hi, A->m - A->int_hi, nullptr};
+    // (ghost rows are packed with ld = nc: even, 16-byte aligned rows when nc is even)
+    const RowChoice ch = rails_row_choice(row_facts(A, nc, x_vec2, y_vec2, false, p.Xp, X->ld, A->ext, nc, 1));
+    RAILS_TRY(spmm_span(c, A, ch, p.Xp, X->ld, A->ext, nc, p.Yp, Y->ld, nc, lo));
+    RAILS_TRY(spmm_span(c, A, ch, p.Xp, X->ld, A->ext, nc, p.Yp, Y->ld, nc, hi));
+    RAILS_HIP_CHECK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
+    join.joined();
+    // what ran: the kernel of the boundary rows (the chunked one counts as row-gather beside another kernel's name), and of the
+    // interior rows where that is another one
+    static const char *const overlapped[3][3] = {
+        {"k_spmm_rowgather (halo overlapped)", "k_spmm_rowgather_cc (halo overlapped)", "k_spmm_narrow (halo overlapped)"},
+        {"k_spmm_rowgather + k_spmm_planes (halo overlapped)", "k_spmm_rowgather + k_spmm_planes (halo overlapped)", "k_spmm_narrow + k_spmm_planes (halo overlapped)"},
+        {"k_spmm_rowgather + k_spmm_sweep (halo overlapped)", "k_spmm_rowgather + k_spmm_sweep (halo overlapped)", "k_spmm_rowgather + k_spmm_sweep (halo overlapped)"}};
+    const RowChoice::Kind boundary = (lo.nrows > 0 || hi.nrows > 0) ? ch.kind : RowChoice::PLAIN;
+    A->last_kernel = overlapped[sweep_done ? 2 : planes_last_interior(A) ? 1 : 0][boundary];
+    c->n_spmm_rowgather++;
+    RAILS_HIP_CHECK(hipGetLastError());
+    return RAILS_OK;
+}
+
+// All rows on the context's stream: the whole-operator kernels in the order of rails_op_order, then the row kernel of rails_row_choice.
+int local_product(rails_ctx *c, rails_csr *A, const OpOrder &order, const Product &p)
+{
+    const rails_panel *X = p.X, *Y = p.Y;
+    const int xc0 = p.xc0, yc0 = p.yc0, nc = p.nc, ldg = p.ldg;
+    const bool vec2 = ((xc0 | yc0) & 1) == 0 && (ldg % 2 == 0);
+    for (int i = 0; i < order.n; ++i) {
+        const bool forced = order.step[i].forced;
+        bool done = false;
+        switch (order.step[i].kernel) {
+        case OpStep::SWEEP: { // banded patterns at panel width (spmm_sweep.hip; forced, it fails itself instead of declining)
+            const bool al = vec2 && X->ld % 2 == 0 && Y->ld % 2 == 0;
+            RAILS_TRY(rails_spmm_sweep(c, A, p.Xp, X->ld, p.Xg, ldg, p.Yp, Y->ld, nc, al, forced, &done));
+            break;
+        }
+        case OpStep::PLANES: { // structured-grid stencils (complete 7- / 27-point patterns) at every even width (spmm_planes.hip) -- the plan
+                               // is one pass over the matrix on the device (a product's worth of time), made by the first product that asks
+            const bool al = (xc0 & 1) == 0 && X->ld % 2 == 0; // (16-byte aligned X rows for the LDS-DMA; Y's window may sit on an odd column)
+            RAILS_TRY(rails_spmm_planes(c, A, p.Xp, X->ld, p.Yp, Y->ld, nc, al, true, &done));
+            if (done) c->n_spmm_planes++;
+            RAILS_REQUIRE(done || !forced, "rails_spmm: plane-sweep kernel requested but not applicable to this operator/shape");
+            break;
+        }
+        case OpStep::TILED:
+            RAILS_TRY(rails_spmm_tiled(c, A, p.Xp, X->ld, p.Xg, ldg, p.Yp, Y->ld, nc, vec2, X->ld - xc0, &done));
+            if (done) c->n_spmm_tiled++;
+            RAILS_REQUIRE(done || !forced, "rails_spmm: LDS-staged kernel requested but not applicable to this operator/shape");
+            break;
+        }
+        if (done) {
+            RAILS_HIP_CHECK(hipGetLastError());
+            return RAILS_OK;
+        }
+    }
+    // (the gathers need 16-byte aligned X rows; a Y window on an odd column -- A*W written behind an odd number of basis columns --
+    // only changes the form of the stores)
+    const bool x_vec2 = (xc0 & 1) == 0 && (X->ld % 2 == 0) && (ldg % 2 == 0);
+    const bool y_vec2 = (yc0 & 1) == 0 && (Y->ld % 2 == 0);
+    const RowChoice ch = rails_row_choice(row_facts(A, nc, x_vec2, y_vec2, vec2, p.Xp, X->ld, p.Xg, ldg, -1));
+    RAILS_TRY(launch_rows(c, A, ch, p.Xp, X->ld, p.Xg, ldg, p.Yp, Y->ld, nc));
+    A->last_kernel = ROW_KERNEL[ch.kind];
+    c->n_spmm_rowgather++;
+    RAILS_HIP_CHECK(hipGetLastError());
+    return RAILS_OK;
+}
+
+} // namespace
+
+extern "C" int rails_spmm(rails_ctx *c, rails_csr *A, int trans, const rails_panel *X, int xc0, int nc, rails_panel *Y, int yc0)
+{
+    if (c) hipSetDevice(c->device); // allocations and launches go to the context's device whatever the caller's current device is
+    rails_slow_guard slow__(c, "rails_spmm", nc, A ? A->m : 0);
+    RAILS_REQUIRE(c && A && X && Y, "rails_spmm: null argument");
+    if (A->kind == rails_csr::SPRHS) return apply_delegate(c, A, trans, X, xc0, nc, Y, yc0); // m x p: it checks the shapes of either direction itself
+    RAILS_TRY(check_windows(A, trans, X, xc0, nc, Y, yc0));
+    if (nc == 0 || A->m == 0) return RAILS_OK;
+    if (A->kind != rails_csr::STORED) return apply_delegate(c, A, trans, X, xc0, nc, Y, yc0);
     if (trans) {
         RAILS_TRY(build_transpose(A));
         A->AT->variant = A->variant;
@@ -730,127 +906,21 @@ extern "C" int rails_spmm(rails_ctx *c, rails_csr *A, int trans, const rails_pan
         A->last_kernel = A->AT->last_kernel;
         return rc;
     }
-    const double *Xp = X->d + xc0;
-    double *Yp = Y->d + yc0;
     // columns beyond the operator's rows come from the ghost buffer; for a rectangular operator (more columns than rows, all of them
     // local) that buffer is the rest of X itself
-    const double *Xg = A->rect ? Xp + (size_t)std::min(A->m, A->ncols_ext) * X->ld : Xp;
-    int ldg = X->ld;
+    Product p = {X, Y, xc0, yc0, nc, X->d + xc0, Y->d + yc0, nullptr, X->ld};
+    p.Xg = A->rect ? p.Xp + (size_t)std::min(A->m, A->ncols_ext) * X->ld : p.Xp;
+    const bool x_vec2 = (xc0 & 1) == 0 && (X->ld % 2 == 0) && (nc % 2 == 0), y_vec2 = (yc0 & 1) == 0 && (Y->ld % 2 == 0);
+    const OpFacts facts = rails_op_facts(c, A, nc, x_vec2, y_vec2);
     if (A->n_ghost > 0 || A->n_send > 0) {
         // pack the rows the neighbours need, exchange, gather from [local | ghost]
-        size_t sbytes = (size_t)(A->n_send ? A->n_send : 1) * nc * sizeof(double);
-        size_t gbytes = (size_t)(A->n_ghost ? A->n_ghost : 1) * nc * sizeof(double);
-        if (sbytes > A->send_cap) {
-            RAILS_HIP_CHECK(rails_stream_sync(c));
-            if (A->send_buf) RAILS_HIP_CHECK(hipFree(A->send_buf));
-            A->send_buf = nullptr;
-            RAILS_HIP_CHECK(hipMalloc((void **)&A->send_buf, sbytes));
-            A->send_cap = sbytes;
-        }
-        if (gbytes > A->ext_cap) {
-            RAILS_HIP_CHECK(rails_stream_sync(c));
-            if (A->ext) RAILS_HIP_CHECK(hipFree(A->ext));
-            A->ext = nullptr;
-            RAILS_HIP_CHECK(hipMalloc((void **)&A->ext, gbytes));
-            A->ext_cap = gbytes;
-        }
-        // Overlap: the interior rows' product runs on the context's second stream while the ghost rows are packed, exchanged and
-        // waited for on the first; the boundary rows follow the exchange, and the first stream then waits for the interior.  Row by
-        // row the same kernels as the serial order below (`RAILS_SPMM_HALO_OVERLAP=0`): the result is bitwise the same.
-        const int overlap_env = spmm_env("RAILS_SPMM_HALO_OVERLAP", 1); // (read per product: the tests switch it inside one process)
-        const bool x_vec2o = (xc0 & 1) == 0 && (X->ld % 2 == 0) && (nc % 2 == 0), y_vec2o = (yc0 & 1) == 0 && (Y->ld % 2 == 0);
-        bool interior_sweep = false;
-        const bool overlap = overlap_env && A->n_ghost > 0 && !A->rect && (A->variant == 0 || A->variant == 1 || A->variant == 3) &&
-                             A->int_hi - A->int_lo >= A->m / 2 && A->int_hi - A->int_lo >= 1024;
-        if (overlap) {
-            RAILS_TRY(rails_ctx_second_stream(c));
-            RAILS_HIP_CHECK(hipEventRecord(c->ev_fork, c->stream));
-            RAILS_HIP_CHECK(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-            const RowSpan in = {A->int_lo, A->int_hi - A->int_lo, c->stream2};
-            bool planes_done = false, sweep_done = false;
-            RAILS_TRY(rails_spmm_planes_interior(c, A, Xp, X->ld, Yp, Y->ld, nc, x_vec2o, c->stream2, &planes_done));
-            if (!planes_done) RAILS_TRY(rails_spmm_sweep_interior(c, A, Xp, X->ld, Yp, Y->ld, nc, x_vec2o && y_vec2o, c->stream2, &sweep_done));
-            interior_sweep = sweep_done;
-            if (!planes_done && !sweep_done)
-                RAILS_TRY(spmm_span(c, A, rails_row_choice(row_facts(A, nc, x_vec2o, y_vec2o, false, Xp, X->ld, Xp, X->ld, 0)), Xp, X->ld, Xp, X->ld, Yp, Y->ld, nc, in));
-            RAILS_HIP_CHECK(hipEventRecord(c->ev_join, c->stream2));
-            c->n_spmm_overlapped++;
-        }
-        if (A->n_send) {
-            int64_t total = A->n_send * nc;
-            int grid = (int)std::min<int64_t>((total + 255) / 256, (int64_t)c->num_cu * 8);
-            RAILS_LAUNCH(k_pack_rows, dim3(grid), dim3(256), 0, c->stream, A->send_rows, A->n_send, Xp, X->ld, nc, A->send_buf);
-        }
-        if (A->halo) {
-            int rc = A->halo(A->halo_user, A->send_buf, A->ext, nc, (void *)c->stream);
-            if (rc != 0) {
-                rails_set_error("rails_spmm: halo hook failed with code %d", rc);
-                return RAILS_ECOMM;
-            }
-        } else {
-            RAILS_REQUIRE(c->rccl, "rails_spmm: ghost rows but neither a halo hook nor an RCCL communicator");
-            RAILS_TRY(rails_rccl_halo(c, A, A->send_buf, A->ext, nc));
-        }
-        if (overlap) {
-            const RowSpan lo = {0, A->int_lo, nullptr}, hi = {A->int_hi, A->m - A->int_hi, nullptr};
-            // (ghost rows are packed with ld = nc: even, 16-byte aligned rows when nc is even)
-            const RowChoice ch = rails_row_choice(row_facts(A, nc, x_vec2o, y_vec2o, false, Xp, X->ld, A->ext, nc, 1));
-            RAILS_TRY(spmm_span(c, A, ch, Xp, X->ld, A->ext, nc, Yp, Y->ld, nc, lo));
-            RAILS_TRY(spmm_span(c, A, ch, Xp, X->ld, A->ext, nc, Yp, Y->ld, nc, hi));
-            RAILS_HIP_CHECK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
-            // what ran: the kernel of the boundary rows (the chunked one counts as row-gather beside another kernel's name), and of the
-            // interior rows where that is another one
-            static const char *const overlapped[3][3] = {
-                {"k_spmm_rowgather (halo overlapped)", "k_spmm_rowgather_cc (halo overlapped)", "k_spmm_narrow (halo overlapped)"},
-                {"k_spmm_rowgather + k_spmm_planes (halo overlapped)", "k_spmm_rowgather + k_spmm_planes (halo overlapped)", "k_spmm_narrow + k_spmm_planes (halo overlapped)"},
-                {"k_spmm_rowgather + k_spmm_sweep (halo overlapped)", "k_spmm_rowgather + k_spmm_sweep (halo overlapped)", "k_spmm_rowgather + k_spmm_sweep (halo overlapped)"}};
-            const RowChoice::Kind boundary = (lo.nrows > 0 || hi.nrows > 0) ? ch.kind : RowChoice::PLAIN;
-            A->last_kernel = overlapped[interior_sweep ? 2 : planes_last_interior(A) ? 1 : 0][boundary];
-            c->n_spmm_rowgather++;
-            RAILS_HIP_CHECK(hipGetLastError());
-            return RAILS_OK;
-        }
-        Xg = A->ext;
-        ldg = nc;
+        RAILS_TRY(grow_buffer(c, &A->send_buf, &A->send_cap, (size_t)(A->n_send ? A->n_send : 1) * nc * sizeof(double)));
+        RAILS_TRY(grow_buffer(c, &A->ext, &A->ext_cap, (size_t)(A->n_ghost ? A->n_ghost : 1) * nc * sizeof(double)));
+        const HaloOrder halo = rails_halo_order(facts);
+        if (halo.overlap) return overlapped_product(c, A, halo.interior, p, x_vec2, y_vec2);
+        RAILS_TRY(exchange_halo(c, A, p.Xp, X->ld, nc));
+        p.Xg = A->ext;
+        p.ldg = nc;
     }
-    bool done = false;
-    const bool vec2 = ((xc0 | yc0) & 1) == 0 && (ldg % 2 == 0);
-    // banded patterns at panel width: the sweep kernel (spmm_sweep.hip), asked for or worthwhile
-    const bool sweep_auto = A->variant == 0 && sweep_worthwhile(A, nc);
-    if (A->variant == 7 || sweep_auto) {
-        const bool al = ((xc0 | yc0) & 1) == 0 && X->ld % 2 == 0 && Y->ld % 2 == 0 && ldg % 2 == 0;
-        RAILS_TRY(rails_spmm_sweep(c, A, Xp, X->ld, Xg, ldg, Yp, Y->ld, nc, al, A->variant == 7, &done));
-        if (done) return RAILS_OK;
-    }
-    // structured-grid stencils (complete 7- / 27-point patterns): the plane-sweep kernel (spmm_planes.hip) at every even width
-    // -- its plan is one pass over the matrix on the device (a product's worth of time), made by the first product that asks
-    if (A->variant == 9 || (A->variant == 0 && nc >= 2 && A->n_ghost == 0 && !A->rect && spmm_env("RAILS_SPMM_PLANES", 1) && rails_csr_is_grid(A))) {
-        const bool al = (xc0 & 1) == 0 && X->ld % 2 == 0; // (16-byte aligned X rows for the LDS-DMA; Y's window may sit on an odd column)
-        RAILS_TRY(rails_spmm_planes(c, A, Xp, X->ld, Yp, Y->ld, nc, al, true, &done));
-        if (done) {
-            c->n_spmm_planes++;
-            return RAILS_OK;
-        }
-        RAILS_REQUIRE(A->variant != 9, "rails_spmm: plane-sweep kernel requested but not applicable to this operator/shape");
-    }
-    // at Expand size <= 16 the lean row kernel (1c) beats the LDS-staged box kernel on the stencils too (27-point: 0.206 against 0.256 ms,
-    // 7-point: 0.097 against 0.130): in automatic mode the box kernel is for wider panels
-    static const int narrow_first = spmm_env("RAILS_SPMM_NARROW_CC", 1) && spmm_env("RAILS_SPMM_NARROW_FAST", 1);
-    const bool leave_to_narrow = A->variant == 0 && narrow_first && nc > 8 && nc <= 16 && A->max_row_nnz <= 64 && A->ncols_ext < (1 << 24);
-    if ((A->variant == 0 && !leave_to_narrow) || A->variant == 2 || A->variant == 6)
-        RAILS_TRY(rails_spmm_tiled(c, A, Xp, X->ld, Xg, ldg, Yp, Y->ld, nc, vec2, X->ld - xc0, &done));
-    if (done) c->n_spmm_tiled++;
-    if (!done) {
-        RAILS_REQUIRE(A->variant != 2 && A->variant != 6, "rails_spmm: LDS-staged kernel requested but not applicable to this operator/shape");
-        // (the gathers need 16-byte aligned X rows; a Y window on an odd column -- A*W written behind an odd number of basis columns --
-        // only changes the form of the stores)
-        const bool x_vec2 = (xc0 & 1) == 0 && (X->ld % 2 == 0) && (ldg % 2 == 0);
-        const bool y_vec2 = (yc0 & 1) == 0 && (Y->ld % 2 == 0);
-        const RowChoice ch = rails_row_choice(row_facts(A, nc, x_vec2, y_vec2, vec2, Xp, X->ld, Xg, ldg, -1));
-        RAILS_TRY(launch_rows(c, A, ch, Xp, X->ld, Xg, ldg, Yp, Y->ld, nc));
-        A->last_kernel = ROW_KERNEL[ch.kind];
-        c->n_spmm_rowgather++;
-    }
-    RAILS_HIP_CHECK(hipGetLastError());
-    return RAILS_OK;
+    return local_product(c, A, rails_op_order(facts, [&] { return rails_csr_is_grid(A); }), p);
 }

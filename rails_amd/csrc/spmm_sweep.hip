@@ -21,6 +21,7 @@
 // Every row's nonzeros are consumed in ascending column order with one fused multiply-add each, exactly like the
 // row-gather kernel: the two kernels give bit-identical results.
 #include "rails_internal.h"
+#include "op_choice.h"
 #include "sweep_plan.h"
 
 #include <map>
@@ -256,8 +257,15 @@ void rails_sweep_release(rails_csr *A)
     A->sweep = nullptr;
 }
 
-// the geometry the kernel is instantiated for
-static constexpr int SWEEP_W = 8, SWEEP_G = 22;
+// the geometry the kernel is instantiated for (op_choice.h: the automatic choice reckons with its row block)
+static constexpr int SWEEP_W = RAILS_SWEEP_WAVES, SWEEP_G = RAILS_SWEEP_GROUPS;
+
+// products of a width an operator is asked for in automatic mode before it builds that width's schedule
+static int sweep_after()
+{
+    static const int after = getenv("RAILS_SWEEP_AFTER") ? atoi(getenv("RAILS_SWEEP_AFTER")) : 16;
+    return after;
+}
 
 // The schedule of A for n_chunks column chunks, built (host, a second per million rows) and copied to the device when missing.
 static int ensure_plan(rails_ctx *c, rails_csr *A, int n_chunks, DevPlan **out, bool interior = false)
@@ -276,10 +284,7 @@ static int ensure_plan(rails_ctx *c, rails_csr *A, int n_chunks, DevPlan **out, 
         prm.nseg = NSEG;
         prm.parts = 8;
         prm.phases = 32 / n_chunks;
-        if (getenv("RAILS_SWEEP_LEVEL")) prm.level = atoi(getenv("RAILS_SWEEP_LEVEL")); // experiments: 0 = no levelling of the waves
-        if (getenv("RAILS_SWEEP_MIN_FILL")) prm.level_min_fill = atoi(getenv("RAILS_SWEEP_MIN_FILL"));
-        if (getenv("RAILS_SWEEP_SLACK")) prm.level_slack = atoi(getenv("RAILS_SWEEP_SLACK"));
-        if (getenv("RAILS_SWEEP_ENTRY_TRIPS")) prm.entry_trips = atoi(getenv("RAILS_SWEEP_ENTRY_TRIPS")) == 4 ? 4 : 2; // 4: entries of whole units (k_spmm_sweep)
+        rails_sweep_params_from_env(prm, true, true);
         if (getenv("RAILS_SWEEP_ABLATE") && atoi(getenv("RAILS_SWEEP_ABLATE"))) prm.entry_trips = 4;                  // (the experiment builds take those)
         bool built = rails_sweep_plan_build(prm, plan_rows, plan_cols, plan_rowptr, A->h_col.data(), A->h_val.data(), d->host);
         if (!built && prm.entry_trips == 2) { // heavy rows: twice the entries do not fit a step's record; whole units may
@@ -322,7 +327,7 @@ int rails_sweep_prepare(rails_ctx *c, rails_csr *A, int nc, bool *fits)
     if (!sweep_shape_ok(c, A, nc, true)) return RAILS_OK;
     DevPlan *d = nullptr;
     RAILS_TRY(ensure_plan(c, A, nc / 16, &d));
-    *fits = d->ok && d->host.efficiency >= 0.4 && d->host.staged_rows_per_row <= 8.0;
+    *fits = rails_sweep_plan_fits(d->ok, d->host.efficiency, d->host.staged_rows_per_row);
     return RAILS_OK;
 }
 
@@ -341,8 +346,7 @@ int rails_spmm_sweep(rails_ctx *c, rails_csr *A, const double *X, int ldx, const
     }
     if (!A->sweep) A->sweep = new rails_sweep_cache();
     if (!force && !A->sweep->by_chunks.count(n_chunks)) {
-        static const int after = getenv("RAILS_SWEEP_AFTER") ? atoi(getenv("RAILS_SWEEP_AFTER")) : 16;
-        if (++A->sweep->asked[n_chunks] < after) return RAILS_OK;
+        if (++A->sweep->asked[n_chunks] < sweep_after()) return RAILS_OK;
     }
     DevPlan *d = nullptr;
     RAILS_TRY(ensure_plan(c, A, n_chunks, &d));
@@ -350,9 +354,7 @@ int rails_spmm_sweep(rails_ctx *c, rails_csr *A, const double *X, int ldx, const
         RAILS_REQUIRE(!force, "rails_spmm: the sweep kernel does not fit this operator: %s", d->host.why.c_str());
         return RAILS_OK;
     }
-    // worth it only where the lock-step trips are reasonably full (the units run early to level the waves count as trips: 0.52 on the
-    // banded-random pattern) and a row block re-uses what it stages
-    if (!force && (d->host.efficiency < 0.4 || d->host.staged_rows_per_row > 8.0)) return RAILS_OK;
+    if (!force && !rails_sweep_plan_fits(true, d->host.efficiency, d->host.staged_rows_per_row)) return RAILS_OK;
     SweepArgs a;
     a.ldx = ldx;
     a.ldg = ldg;
@@ -407,39 +409,31 @@ int rails_spmm_sweep(rails_ctx *c, rails_csr *A, const double *X, int ldx, const
 }
 
 // The interior rows of a row-partitioned operator (rails_csr_set_halo: rows [int_lo, int_hi) reference local X rows only) as a sweep of
-// their own, on stream st while the ghost rows travel (rails_spmm).  prepare_only: build the schedule if the shape qualifies.
-static bool sweep_interior_shape_ok(const rails_ctx *c, const rails_csr *A, int nc, bool aligned)
-{
-    const int n_chunks = nc / 16;
-    if (!(aligned && nc % 16 == 0 && nc >= 64 && n_chunks <= 32 && 32 % n_chunks == 0 && c->num_cu >= 256 && A->n_ghost > 0 && !A->rect && A->m < 0x7fffffffLL)) return false;
-    const int64_t phases = 32 / n_chunks, rows = A->int_hi - A->int_lo, part_rows = rows / 8;
-    return A->window_rows_int > 0 && A->window_rows_int + 256 <= (phases - 1) * 2816 && rows >= 8 * phases * 2816 &&
-           (double)phases * (double)(part_rows + A->window_rows_int + 1024) <= 8.0 * (double)part_rows;
-}
+// their own, on stream st while the ghost rows travel (rails_spmm, where rails_halo_order says so).  Which shapes qualify:
+// rails_sweep_interior_shape_ok (op_choice.h).
 
 int rails_sweep_prepare_interior(rails_ctx *c, rails_csr *A, int nc, bool *fits)
 {
     *fits = false;
-    if (!sweep_interior_shape_ok(c, A, nc, true)) return RAILS_OK;
+    if (!rails_sweep_interior_shape_ok(rails_op_facts(c, A, nc, true, true))) return RAILS_OK;
     DevPlan *d = nullptr;
     RAILS_TRY(ensure_plan(c, A, nc / 16, &d, true));
-    *fits = d->ok && d->host.efficiency >= 0.4 && d->host.staged_rows_per_row <= 8.0;
+    *fits = rails_sweep_plan_fits(d->ok, d->host.efficiency, d->host.staged_rows_per_row);
     return RAILS_OK;
 }
 
 int rails_spmm_sweep_interior(rails_ctx *c, rails_csr *A, const double *X, int ldx, double *Y, int ldy, int nc, bool aligned, hipStream_t st, bool *done)
 {
     *done = false;
-    if (A->variant != 0 || !sweep_interior_shape_ok(c, A, nc, aligned)) return RAILS_OK;
+    if (!rails_sweep_interior_shape_ok(rails_op_facts(c, A, nc, aligned, aligned))) return RAILS_OK;
     const int n_chunks = nc / 16;
     if (!A->sweep) A->sweep = new rails_sweep_cache();
     if (!A->sweep->interior.count(n_chunks)) {
-        static const int after = getenv("RAILS_SWEEP_AFTER") ? atoi(getenv("RAILS_SWEEP_AFTER")) : 16;
-        if (++A->sweep->asked_interior[n_chunks] < after) return RAILS_OK;
+        if (++A->sweep->asked_interior[n_chunks] < sweep_after()) return RAILS_OK;
     }
     DevPlan *d = nullptr;
     RAILS_TRY(ensure_plan(c, A, n_chunks, &d, true));
-    if (!d->ok || d->host.efficiency < 0.4 || d->host.staged_rows_per_row > 8.0) return RAILS_OK;
+    if (!rails_sweep_plan_fits(d->ok, d->host.efficiency, d->host.staged_rows_per_row)) return RAILS_OK;
     SweepArgs a;
     a.ldx = ldx;
     a.ldg = ldx;

@@ -123,7 +123,8 @@ extern "C" int rails_csr_create_sprhs(rails_ctx *c, rails_sprhs *S, rails_csr **
     A->m = S->m;
     A->ncols_ext = S->p;
     A->nnz = S->nnz;
-    A->sprhs = S;
+    A->kind = rails_csr::SPRHS;
+    A->delegate = S;
     A->last_kernel = "sprhs";
     *out = A;
     return RAILS_OK;
@@ -132,7 +133,7 @@ extern "C" int rails_csr_create_sprhs(rails_ctx *c, rails_sprhs *S, rails_csr **
 extern "C" int64_t rails_csr_cols(const rails_csr *A)
 {
     if (!A) return -1;
-    return (A->rect || A->sprhs) ? A->ncols_ext : A->m;
+    return (A->rect || A->kind == rails_csr::SPRHS) ? A->ncols_ext : A->m;
 }
 
-extern "C" rails_sprhs *rails_csr_sprhs(const rails_csr *A) { return A ? A->sprhs : nullptr; }
+extern "C" rails_sprhs *rails_csr_sprhs(const rails_csr *A) { return A ? A->sprhs() : nullptr; }

@@ -539,6 +539,23 @@ bool rails_sweep_plan_build(const rails_sweep_params &prm, int64_t m, int64_t nc
     return true;
 }
 
+// (experiments, DESIGN.md 4a: RAILS_SWEEP_LEVEL = 0 takes the levelling of the waves out)
+void rails_sweep_params_from_env(rails_sweep_params &prm, bool levelling, bool entry_trips)
+{
+    auto env = [](const char *name, int &v) {
+        const char *e = getenv(name);
+        if (e) v = atoi(e);
+        return e != nullptr;
+    };
+    if (levelling) {
+        env("RAILS_SWEEP_LEVEL", prm.level);
+        env("RAILS_SWEEP_MIN_FILL", prm.level_min_fill);
+        env("RAILS_SWEEP_SLACK", prm.level_slack);
+    }
+    int trips = 0;
+    if (entry_trips && env("RAILS_SWEEP_ENTRY_TRIPS", trips)) prm.entry_trips = trips == 4 ? 4 : 2;
+}
+
 // ---- C ABI (include/rails_hip.h): host-side access to the schedule for tests and diagnostics ----
 #include "rails_hip.h"
 
@@ -561,11 +578,8 @@ extern "C" int rails_sweep_plan_create(int64_t m, int64_t ncols, const int64_t *
         prm.phases = params[5];
         prm.ahead = params[6];
         if (params[7] == 2 || params[7] == 4) prm.entry_trips = params[7];
-        if (getenv("RAILS_SWEEP_LEVEL")) prm.level = atoi(getenv("RAILS_SWEEP_LEVEL")); // experiments: 0 = no levelling of the waves
-        if (getenv("RAILS_SWEEP_MIN_FILL")) prm.level_min_fill = atoi(getenv("RAILS_SWEEP_MIN_FILL"));
-        if (getenv("RAILS_SWEEP_SLACK")) prm.level_slack = atoi(getenv("RAILS_SWEEP_SLACK"));
     }
-    if ((!params || params[7] == 0) && getenv("RAILS_SWEEP_ENTRY_TRIPS")) prm.entry_trips = atoi(getenv("RAILS_SWEEP_ENTRY_TRIPS")) == 4 ? 4 : 2;
+    rails_sweep_params_from_env(prm, params != nullptr, !params || params[7] == 0);
     rails_sweep_plan *pl = new rails_sweep_plan();
     if (!rails_sweep_plan_build(prm, m, ncols, rowptr, col, val, *pl)) {
         rails_set_error("rails_sweep_plan_create: pattern does not fit the sweep scheme: %s", pl->why.c_str());

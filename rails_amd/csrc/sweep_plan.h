@@ -78,6 +78,10 @@ struct rails_sweep_plan {
     std::string why;                         // reason when not feasible
 };
 
+// The planner's switches from the environment, read in this one place (sweep_plan.cpp names them): level, level_min_fill and level_slack
+// where `levelling`; entry_trips (4: entries of whole units, anything else: 2) where `entry_trips`.
+void rails_sweep_params_from_env(rails_sweep_params &prm, bool levelling, bool entry_trips);
+
 // Builds the plan; returns false (plan.why says why) when the pattern does not fit the scheme with these parameters:
 // a block's rows still need X rows that have not arrived when the rows of the next block of the same workgroup lose theirs.
 bool rails_sweep_plan_build(const rails_sweep_params &prm, int64_t m, int64_t ncols, const int64_t *rowptr, const int32_t *col,

@@ -321,3 +321,76 @@ def test_interior_rows_of_a_banded_block_take_the_sweep_kernel(monkeypatch):
     for k, i in enumerate(rows):
         ref[k] = val[rp[i]:rp[i + 1]] @ X[col[rp[i]:rp[i + 1]]]
     assert np.abs(Yo[rows] - ref).max() <= 4e-14 * np.sqrt(27) * np.abs(ref).max()
+
+
+def test_failing_halo_hook_joins_the_interior_product_and_the_context_goes_on(monkeypatch):
+    """A halo hook that reports failure makes rails_spmm return after the interior rows' product was started on the second stream: the
+    product raises, the context's stream then covers that product too (rails_spmm joins on every exit of the overlapped order), and the
+    same context goes on to compute the overlapped product bit for bit as the serial one.  One context plays the middle rank of three;
+    its hook takes the ghost rows from the global X held here."""
+    import torch
+
+    import rails_amd
+    from rails_amd import partition
+    from rails_amd import problems as P
+    from rails_amd._lib import RailsError
+    from rails_amd.partition import wrap_buffer
+    from rails_amd.wrappers import HipMultiVectorWrapper as MV
+
+    nranks, rank, m = 3, 1, 3 * 4096
+    A = P.banded_random(m, 27, 64, seed=4)
+    Xh = np.random.default_rng(11).uniform(-1, 1, (m, 16))
+    starts = partition.row_ranges(m, nranks)
+    blocks = [P.csr_rows(A, int(starts[q]), int(starts[q + 1])) for q in range(nranks)]
+
+    def requests(q):  # what rank q asks of every rank: its ghost rows by owner (HaloPlan's own first step)
+        colg = np.asarray(blocks[q][1], dtype=np.int64)
+        ghosts = np.unique(colg[(colg < starts[q]) | (colg >= starts[q + 1])])
+        owner = np.searchsorted(starts, ghosts, side="right") - 1
+        return [ghosts[owner == d] for d in range(nranks)]
+
+    rowptr, colg, val = blocks[rank]
+    plan = partition.HaloPlan(starts, rank, colg, lambda mine: [requests(q) for q in range(nranks)])
+    r0, r1 = int(starts[rank]), int(starts[rank + 1])
+    # the interior rows as rails_csr_set_halo finds them: ghost rows on both sides, at least 1024 rows and half the block in between
+    has_ghost = np.logical_or.reduceat(plan.col_local >= plan.m_local, rowptr[:-1])
+    lo_rows, hi_rows = np.flatnonzero(has_ghost[:2048]), np.flatnonzero(has_ghost[2048:])
+    assert lo_rows.size and hi_rows.size and plan.recv_counts[0] > 0 and plan.recv_counts[2] > 0
+    assert (2048 + hi_rows.min()) - (lo_rows.max() + 1) >= 2048
+
+    monkeypatch.setenv("RAILS_SPMM_HALO_OVERLAP", "1")
+    ctx = rails_amd.Context(device=0, seed=5)
+    op = rails_amd.HipOperatorWrapper(ctx, rowptr, plan.col_local, val, ncols_ext=plan.m_local + plan.n_ghost)
+    hook_result = [1]
+
+    def hook(send_ptr, recv_ptr, ncols, stream):
+        if hook_result[0]:
+            return hook_result[0]
+        ctx.sync()
+        ghosts = np.ascontiguousarray(Xh[plan.ghost_globals, :ncols]).ravel()
+        wrap_buffer(recv_ptr, plan.n_ghost * ncols, True).copy_(torch.from_numpy(ghosts))
+        torch.cuda.synchronize()
+        return 0
+
+    op.set_halo(plan, hook)
+    X16, X6 = MV(ctx, data=Xh[r0:r1]), MV(ctx, data=Xh[r0:r1, :6])
+    with pytest.raises(RailsError, match="halo hook"):
+        op.apply(X16)
+    ctx.sync()
+    assert ctx.stats()["spmm_halo_overlapped"] == 1  # the failure came after the fork: the interior product had been started
+    hook_result[0] = 0
+    Y16, Y6 = op.apply(X16), op.apply(X6)
+    k16 = op.last_kernel()
+    Y6h, k6 = Y6.to_host(), op.last_kernel()
+    Y16h = Y16.to_host()
+    assert "halo overlapped" in k16 and "halo overlapped" in k6
+    assert ctx.stats()["spmm_halo_overlapped"] - 1 == 2
+    monkeypatch.setenv("RAILS_SPMM_HALO_OVERLAP", "0")
+    op.set_variant(1)
+    S16, S6 = op.apply(X16).to_host(), op.apply(X6).to_host()
+    assert "halo overlapped" not in op.last_kernel() and ctx.stats()["spmm_halo_overlapped"] == 3
+    assert np.array_equal(Y16h, S16), np.abs(Y16h - S16).max()
+    assert np.array_equal(Y6h, S6), np.abs(Y6h - S6).max()
+    ref = np.add.reduceat(np.asarray(val)[:, None] * Xh[np.asarray(colg)], rowptr[:-1])
+    assert np.abs(Y16h - ref).max() <= 4e-14 * np.sqrt(27) * np.abs(ref).max()
+    ctx.close()
