@@ -229,7 +229,17 @@ int rails_csr_create_lu(rails_ctx *ctx, rails_lu *lu, rails_csr **out);
  * entry is stored and nonzero; otherwise there is none.  Every column is a system of its own (start value zero, tolerance relative to
  * its own ||b||); all scalars stay on the device and the host reads one number back every `check_every` iterations.  No floating-point
  * atomics: two solves of the same input give the same bits, whatever check_every is.  Single GPU only.
- * Settings (rails_iter_set): "tolerance" 1e-10, "max_iterations" 1000, "jacobi" 1, "check_every" 8, "strict" 0.
+ * Settings (rails_iter_set): "tolerance" 1e-10, "max_iterations" 1000, "jacobi" 1, "check_every" 8, "strict" 0, and those of the polynomial
+ * preconditioner below: "poly_degree" 0, "poly_ratio" 10, "eig_max" 0, "poly_fused" 1.
+ * Chebyshev polynomial preconditioner (CG only; rails_amd/csrc/cheb_coef.h): with "poly_degree" K in 1 .. 64 the
+ * solve preconditions with z = p_K(G A) G r, K products with A in a row without an inner product, a scalar kernel or a read-back between
+ * them; G is the Jacobi diagonal's inverse when Jacobi is in effect and otherwise +-I, the sign of the operator's diagonal.  The
+ * polynomial is fitted to [hi / "poly_ratio", hi]; hi is a Gershgorin bound on the spectrum of G A taken at create time from the CSR
+ * arrays a stored operator keeps on the host, or "eig_max" when that is above 0 (an operator without host arrays -- a callback, an LU
+ * handle -- needs it).  For a stored CSR operator without ghost rows, of fewer than 2^24 rows and with work panels below 4 GiB each
+ * product is fused with its recurrence update in one kernel ("poly_fused" 0: never).  Degree 0, the default, is the solve without any
+ * of this, bit for bit.  RAILS_EINVAL: a degree above 0 on a BiCGStab object, a degree outside 0 .. 64, a ratio of at most 1, and a
+ * solve with a degree above 0 and no bound.
  * Outcomes: a zero right-hand-side column gives x = 0 after 0 iterations; a column that stops at max_iterations or breaks down (a
  * vanishing denominator; CG: p'Ap of the wrong sign, the operator is not definite) keeps its last iterate and is flagged, and the call
  * still returns RAILS_OK unless "strict" is set (RAILS_ENOCONV); a right-hand side that is not finite gives RAILS_EINVAL. */
@@ -243,10 +253,16 @@ int rails_iter_set(rails_iter *it, const char *name, double value);
  * unchanged and columns of Y outside the window are not touched.  The object owns its work panels and grows them only for a wider nc.
  * Synchronises. */
 int rails_iter_solve(rails_ctx *ctx, rails_iter *it, int trans, const rails_panel *X, int xc0, int nc, rails_panel *Y, int yc0);
+/* Y[:, yc0:yc0+nc] = p_K(G A) G X[:, xc0:xc0+nc]: the preconditioner of the solve on its own, a fixed linear approximate inverse (K = 0:
+ * G X).  Same window rules and groups of 32 columns as rails_iter_solve.  Queues its work and does not synchronise; the counters [1], [2],
+ * [7], [13] and [14] of rails_iter_stats then count this call. */
+int rails_iter_precondition(rails_ctx *ctx, rails_iter *it, const rails_panel *X, int xc0, int nc, rails_panel *Y, int yc0);
 /* Last solve: info[0] most iterations of a column, [1] inner products, [2] launches of the library's own passes, [3] columns that did not
  * converge, [4] of those, broken down, [5] worst relative residual of the recurrence, [6] work-panel columns, [7] products with A;
- * totals since creation: [8] solves, [9] columns, [10] iterations summed over columns, [11] flagged columns, [12] products.  Returns the
- * number of entries written (at most cap), or a negative code. */
+ * totals since creation: [8] solves, [9] columns, [10] iterations summed over columns, [11] flagged columns, [12] products; the polynomial
+ * preconditioner: [13] its applications in the last solve, [14] launches of the fused step kernel, [15] hi and [16] lo of the interval in
+ * use (0 with degree 0).  [7] counts every product with A, those inside fused steps included.  Returns the number of entries written (at
+ * most cap: a caller that passes 13 sees what it always saw), or a negative code. */
 int rails_iter_stats(const rails_iter *it, double *info, int cap);
 /* Per column of the last solve (any pointer may be NULL): iterations, relative residual of the recurrence, flags (2 converged, 4 stopped at
  * max_iterations, 8 breakdown, 16 non-finite).  Returns the number of columns of the last solve; at most cap are written. */

@@ -1,7 +1,9 @@
 // itsolve.hip -- A^-1 X (or A^-T X) by an iteration that stays on the device, as a library object: the approximate inverse the reference
 // allows for its inverse and extended Krylov projections (matlab/RAILSsolver.m:19-23, opts.Ainv: "This can be approximate") where a
 // sparse LU (splu.hip) is latency-bound or cannot be formed at all.  Conjugate gradients for a definite operator of either sign,
-// BiCGStab (right-preconditioned) for a general one, both with an optional Jacobi preconditioner.
+// BiCGStab (right-preconditioned) for a general one, both with an optional Jacobi preconditioner; conjugate gradients also with a
+// Chebyshev polynomial in the Jacobi-scaled operator ("poly_degree", cheb_coef.h), whose steps -- a product and its
+// recurrence update -- are one kernel each for a stored CSR operator (k_cheb_step_csr).
 //
 // Every column is a system of its own with its own scalars (rails_iter_col, iter_scalars.h) in a device block the object owns: no block
 // method, no small matrix on the host.  The iteration runs on work panels of the object (ordinary panels, window at column 0, so the
@@ -22,11 +24,14 @@
 #include <cmath>
 #include <vector>
 
+#include "cheb_coef.h"
 #include "iter_scalars.h"
 
 namespace {
 
 constexpr int RAILS_ITER_GROUP = 32; // columns per group: the widest panel every SpMM kernel takes in one chunk
+// default of "poly_ratio" (hi / lo): the smallest worst case of products relative to plain CG over the table of DESIGN.md section 15
+constexpr double RAILS_ITER_POLY_RATIO = 10.0;
 
 typedef double it_v2 __attribute__((ext_vector_type(2)));
 
@@ -225,6 +230,135 @@ __global__ __launch_bounds__(256) void k_bi_update(PassGeom g, const rails_iter_
     });
 }
 
+// ---- the Chebyshev polynomial preconditioner z = p_K(G A) G r (cheb_coef.h): G is the Jacobi diagonal's inverse (gvec) or the scalar gs
+// = +-1; the coefficients are the same for every column and come as kernel arguments ----
+
+__device__ __forceinline__ double cheb_g(const double *__restrict__ gvec, double gs, int64_t row) { return gvec ? gvec[row] : gs; }
+
+// d = z = (g r) / theta
+__global__ __launch_bounds__(256) void k_cheb_init(PassGeom g, const double *__restrict__ gvec, double gs, double theta, const double *__restrict__ R,
+                                                   double *__restrict__ D, double *__restrict__ Z)
+{
+    iter_pass<0>(g, nullptr, [&](int64_t row, int64_t o, bool has1, it_v2 *) {
+        const it_v2 d = (ld2(R + o) * cheb_g(gvec, gs, row)) / theta;
+        st2(D + o, d, has1);
+        st2(Z + o, d, has1);
+    });
+}
+
+// the unfused step, after Q = A z: d = a d + b g (r - q), z += d
+__global__ __launch_bounds__(256) void k_cheb_pass(PassGeom g, const double *__restrict__ gvec, double gs, double a, double b, const double *__restrict__ Q,
+                                                   const double *__restrict__ R, double *__restrict__ D, double *__restrict__ Z)
+{
+    iter_pass<0>(g, nullptr, [&](int64_t row, int64_t o, bool has1, it_v2 *) {
+        const it_v2 res = (ld2(R + o) - ld2(Q + o)) * cheb_g(gvec, gs, row);
+        const it_v2 d = ld2(D + o) * a + res * b;
+        st2(D + o, d, has1);
+        st2(Z + o, ld2(Z + o) + d, has1);
+    });
+}
+
+// The fused step for a stored CSR operator: t = (A Zin)_row by k_spmm_narrow's row gather (spmm.hip: LPR lanes own a row and two adjacent
+// columns each, 64 rows per block, the block's (col, val) run staged in LDS, 32-bit byte offsets; one entry at a time for a block whose run
+// is longer than the LDS buffer and for the lane of an odd last column), then in the same thread d = a d + b g (r - t) in place and
+// Zout = Zin + d.  Zin and Zout are different panels: every block reads rows of Zin that other blocks own.  All panels are work panels of
+// the object: window at column 0, one row stride, rows 16-byte aligned.  No atomics, no inner products.
+template <int RPG, int LPR>
+__global__ __launch_bounds__(256) void k_cheb_step_csr(int64_t m, const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+                                                       const double *__restrict__ val, const double *__restrict__ Zin, int ld, int nc, int64_t blocks_per_xcd,
+                                                       const double *__restrict__ gvec, double gs, double a, double b, const double *__restrict__ R,
+                                                       double *__restrict__ D, double *__restrict__ Zout)
+{
+    constexpr int GROUPS = 256 / LPR, ROWS = GROUPS * RPG, CAP = 2048;
+    __shared__ double s_val[CAP];
+    __shared__ int32_t s_col[CAP];
+    const int g = threadIdx.x / LPR;
+    const int l = threadIdx.x % LPR;
+    const int64_t lb = (int64_t)(blockIdx.x & 7) * blocks_per_xcd + (blockIdx.x >> 3);
+    const int64_t r0 = lb * ROWS;
+    if (r0 >= m) return;
+    const int64_t r1 = (r0 + ROWS < m) ? r0 + ROWS : m;
+    const int64_t nz0 = rowptr[r0], nz1 = rowptr[r1];
+    const bool staged = (nz1 - nz0) <= CAP; // block-uniform
+    if (staged) {
+        for (int q = threadIdx.x; q < (int)(nz1 - nz0); q += 256) {
+            s_col[q] = col[nz0 + q];
+            s_val[q] = val[nz0 + q];
+        }
+        __syncthreads();
+    }
+    const int cb = l * 2;
+    if (cb >= nc) return;
+    const bool full = (cb + 2 <= nc);
+    const uint32_t cb8 = (uint32_t)cb * 8u, ld8 = (uint32_t)ld * 8u;
+    const char *Zb = reinterpret_cast<const char *>(Zin);
+    auto zrow = [&](uint32_t c) -> const char * { return Zb + (__umul24(c, ld8) + cb8); };
+    for (int rr = 0; rr < RPG; ++rr) {
+        const int64_t row = r0 + (int64_t)rr * GROUPS + g; // the rows in flight are consecutive
+        if (row >= m) break;
+        it_v2 acc = (it_v2){0.0, 0.0};
+        if (staged && full) {
+            int i = (int)(rowptr[row] - nz0);
+            const int i1 = (int)(rowptr[row + 1] - nz0);
+            for (; i + 8 <= i1; i += 8) {
+                it_v2 x[8];
+                double av[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    x[u] = *reinterpret_cast<const it_v2 *>(zrow((uint32_t)s_col[i + u]));
+                    av[u] = s_val[i + u];
+                }
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    acc.x = __builtin_fma(av[u], x[u].x, acc.x);
+                    acc.y = __builtin_fma(av[u], x[u].y, acc.y);
+                }
+            }
+            for (; i < i1; i += 4) { // the last one to seven: groups of four, the slots past the end repeat the last entry with a zero
+                it_v2 x[4];
+                double av[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int q = i + u < i1 ? i + u : i1 - 1;
+                    x[u] = *reinterpret_cast<const it_v2 *>(zrow((uint32_t)s_col[q]));
+                    av[u] = i + u < i1 ? s_val[q] : 0.0;
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    acc.x = __builtin_fma(av[u], x[u].x, acc.x);
+                    acc.y = __builtin_fma(av[u], x[u].y, acc.y);
+                }
+            }
+        } else {
+            for (int64_t p = rowptr[row]; p < rowptr[row + 1]; ++p) {
+                const double av = val[p];
+                const double *src = reinterpret_cast<const double *>(zrow((uint32_t)col[p]));
+                acc.x = __builtin_fma(av, src[0], acc.x);
+                if (full) acc.y = __builtin_fma(av, src[1], acc.y);
+            }
+        }
+        // the epilogue on this thread's own two entries of the row (the pad column beside an odd last column is read, never written)
+        const int64_t o = row * ld + cb;
+        const it_v2 res = (ld2(R + o) - acc) * cheb_g(gvec, gs, row);
+        const it_v2 d = ld2(D + o) * a + res * b;
+        st2(D + o, d, full);
+        st2(Zout + o, ld2(Zin + o) + d, full);
+    }
+}
+
+// CG with the polynomial, start (r = b in R, z = p(A) r in Z): p = z, x = 0; partial sums of r.z and r.r
+__global__ __launch_bounds__(256) void k_cg_init_poly(PassGeom g, const double *__restrict__ R, const double *__restrict__ Z, double *__restrict__ P,
+                                                      double *__restrict__ Xw, double *__restrict__ partial)
+{
+    iter_pass<2>(g, partial, [&](int64_t, int64_t o, bool has1, it_v2 *acc) {
+        const it_v2 r = ld2(R + o), z = ld2(Z + o);
+        st2(P + o, z, has1);
+        st2(Xw + o, (it_v2){0.0, 0.0}, has1);
+        acc[0] += r * z;
+        acc[1] += r * r;
+    });
+}
+
 // sums[e] = sum over the blocks of partial[block][e], e < n <= 64, in a fixed order: 16 interleaved strands, then the strands 0..15
 __device__ __forceinline__ void iter_reduce(const double *__restrict__ partial, int64_t nslab, int n, double *sums)
 {
@@ -281,7 +415,8 @@ __global__ __launch_bounds__(1024) void k_iter_scalars(int step, const double *_
     }
 }
 
-enum { W_X = 0, W_R, W_P, W_Q, W_Z, W_RH, W_T, W_SH, W_COUNT }; // CG: x r p q [z]; BiCGStab: x r p v(=Q) [p^(=Z)] r^ t [s^]
+// CG: x r p q [z]; BiCGStab: x r p v(=Q) [p^(=Z)] r^ t [s^]; the polynomial: z, its direction d, the second z of the fused step's ping-pong
+enum { W_X = 0, W_R, W_P, W_Q, W_Z, W_RH, W_T, W_SH, W_D, W_Z2, W_COUNT };
 
 } // namespace
 
@@ -304,6 +439,11 @@ struct rails_iter {
     std::vector<rails_iter_col> last; // the columns of the last solve
     // statistics: last solve, totals
     long last_dots = 0, last_launches = 0, last_products = 0;
+    // the Chebyshev polynomial preconditioner (cheb_coef.h): degree 0 is off
+    int poly_degree = 0, poly_fused = 1;
+    double poly_ratio = RAILS_ITER_POLY_RATIO, eig_max = 0.0;
+    double hi_jacobi = 0.0, hi_plain = 0.0; // Gershgorin bounds on D^-1 A and on +-A from the host CSR arrays (0: none)
+    long last_poly = 0, last_fused = 0;
     double tot_solves = 0, tot_iterations = 0, tot_flagged = 0, tot_products = 0, tot_columns = 0;
 };
 
@@ -321,16 +461,23 @@ void release_work(rails_iter *it)
 bool uses_panel(const rails_iter *it, int which)
 {
     const bool jac = it->dinv != nullptr;
+    if (which == W_D || which == W_Z2) return it->poly_degree > 0;
+    if (which == W_Z && it->poly_degree > 0) return true;
     if (it->method == RAILS_ITER_CG) return which == W_X || which == W_R || which == W_P || which == W_Q || (which == W_Z && jac);
     return which == W_X || which == W_R || which == W_P || which == W_Q || which == W_RH || which == W_T || ((which == W_Z || which == W_SH) && jac);
 }
 
-int grow_work(rails_ctx *c, rails_iter *it, int cols)
+// `also`: panels (bits 1 << W_...) wanted beside those the method uses (rails_iter_precondition)
+int grow_work(rails_ctx *c, rails_iter *it, int cols, unsigned also = 0)
 {
-    if (cols <= it->work_cols) return RAILS_OK;
+    bool missing = false; // a setting made after the last solve may ask for a panel that is not there yet
+    for (int k = 0; k < W_COUNT; ++k) missing = missing || ((uses_panel(it, k) || (also >> k & 1)) && !it->w[k]);
+    if (cols <= it->work_cols && !missing) return RAILS_OK;
+    cols = std::max(cols, it->work_cols);
+    for (int k = 0; k < W_COUNT; ++k) also |= it->w[k] ? 1u << k : 0u;
     release_work(it);
     for (int k = 0; k < W_COUNT; ++k)
-        if (uses_panel(it, k)) {
+        if (uses_panel(it, k) || (also >> k & 1)) {
             RAILS_TRY(rails_panel_create(c, it->m, cols, &it->w[k]));
             RAILS_HIP_CHECK(hipMemsetAsync(it->w[k]->d, 0, (size_t)it->m * it->w[k]->ld * sizeof(double), c->stream));
         }
@@ -371,12 +518,17 @@ struct Run {
     rails_iter_col *cols;
     bool jac;
     double tol2;
+    // the polynomial: degree (0: off), theta and the coefficient pairs, whether its steps run on the fused kernel
+    int K = 0;
+    bool fused = false;
+    double theta = 1.0, ca[RAILS_CHEB_MAX_DEGREE], cb[RAILS_CHEB_MAX_DEGREE];
 
     double *d(int k) const { return it->w[k]->d; }
     int scalars(int step, int nq)
     {
+        // (with the polynomial r.z carries the sign of the operator itself, as with Jacobi)
         RAILS_LAUNCH(k_iter_scalars, dim3(1), dim3(1024), 0, c->stream, step, c->ws, nslab, g.ncw, nq, cols, it->status_dev, tol2, it->maxit,
-                     jac ? 1.0 : it->defsign);
+                     (jac || K > 0) ? 1.0 : it->defsign);
         it->last_launches++;
         return RAILS_OK;
     }
@@ -406,8 +558,50 @@ struct Run {
         it->last_launches++;                                                                                                                 \
     } while (0)
 
+    // W_Z = p_K(G A) G W_R (K = 0: G W_R).  The fused steps read one z panel and write the other, and start in the one that makes the
+    // last of them write W_Z; the unfused ones work in W_Z with A z in W_Q.
+    int polynomial()
+    {
+        const double *gvec = jac ? it->dinv : nullptr;
+        const double gs = it->defsign;
+        const dim3 grid((unsigned)nslab), block(256);
+        int zin = (fused && (K & 1)) ? W_Z2 : W_Z;
+        RAILS_LAUNCH(k_cheb_init, grid, block, 0, c->stream, g, gvec, gs, theta, d(W_R), d(W_D), d(zin));
+        it->last_launches++;
+        it->last_poly++;
+        const rails_csr *A = it->A;
+        const int64_t bpx = ((it->m + 63) / 64 + 7) / 8;
+        for (int k = 0; k < K; ++k) {
+            if (!fused) {
+                RAILS_TRY(product(W_Z, W_Q));
+                RAILS_LAUNCH(k_cheb_pass, grid, block, 0, c->stream, g, gvec, gs, ca[k], cb[k], d(W_Q), d(W_R), d(W_D), d(W_Z));
+                it->last_launches++;
+                continue;
+            }
+            const int zout = zin == W_Z ? W_Z2 : W_Z;
+            if (g.ncw <= 16)
+                RAILS_LAUNCH((k_cheb_step_csr<2, 8>), dim3((unsigned)(bpx * 8)), block, 0, c->stream, it->m, A->rowptr, A->col, A->val, d(zin), g.ld, g.ncw, bpx,
+                             gvec, gs, ca[k], cb[k], d(W_R), d(W_D), d(zout));
+            else
+                RAILS_LAUNCH((k_cheb_step_csr<4, 16>), dim3((unsigned)(bpx * 8)), block, 0, c->stream, it->m, A->rowptr, A->col, A->val, d(zin), g.ld, g.ncw, bpx,
+                             gvec, gs, ca[k], cb[k], d(W_R), d(W_D), d(zout));
+            it->last_launches++;
+            it->last_products++;
+            it->last_fused++;
+            zin = zout;
+        }
+        return RAILS_OK;
+    }
     int start()
     {
+        if (it->method == RAILS_ITER_CG && K > 0) {
+            RAILS_TRY(polynomial());
+            RAILS_TRY(rails_ws_reserve(c, (size_t)nslab * 2 * g.ncw * sizeof(double)));
+            RAILS_LAUNCH(k_cg_init_poly, dim3((unsigned)nslab), dim3(256), 0, c->stream, g, d(W_R), d(W_Z), d(W_P), d(W_X), c->ws);
+            it->last_launches++;
+            it->last_dots += 2 * g.ncw;
+            return scalars(STEP_CG_INIT, 2);
+        }
         if (it->method == RAILS_ITER_CG) {
             ITER_PASS_LAUNCH((k_cg_init<true>), (k_cg_init<false>), g, it->dinv, d(W_R), jac ? d(W_Z) : nullptr, d(W_P), d(W_X), c->ws);
             it->last_dots += 2 * g.ncw;
@@ -419,6 +613,21 @@ struct Run {
     }
     int iteration()
     {
+        if (it->method == RAILS_ITER_CG && K > 0) {
+            // the update without its own z (its partial sums are overwritten below), the polynomial, then r.z and r.r in the layout
+            // the scalar step reads; K products in a row without an inner product, a scalar kernel or a read-back between them
+            RAILS_TRY(product(W_P, W_Q));
+            RAILS_TRY(dots(1, W_P, W_Q, W_P, W_Q));
+            RAILS_TRY(scalars(STEP_CG_ALPHA, 1));
+            RAILS_LAUNCH((k_cg_update<false>), dim3((unsigned)nslab), dim3(256), 0, c->stream, g, cols, it->dinv, d(W_P), d(W_Q), d(W_X), d(W_R), nullptr, c->ws);
+            it->last_launches++;
+            RAILS_TRY(polynomial());
+            RAILS_TRY(dots(2, W_R, W_Z, W_R, W_R));
+            RAILS_TRY(scalars(STEP_CG_BETA, 2));
+            RAILS_LAUNCH(k_cg_dir, dim3((unsigned)nslab), dim3(256), 0, c->stream, g, cols, d(W_Z), d(W_P));
+            it->last_launches++;
+            return RAILS_OK;
+        }
         if (it->method == RAILS_ITER_CG) {
             const int z = jac ? W_Z : W_R;
             RAILS_TRY(product(W_P, W_Q));
@@ -445,6 +654,47 @@ struct Run {
     }
 #undef ITER_PASS_LAUNCH
 };
+
+// the upper end of the polynomial's interval: "eig_max", else the Gershgorin bound that goes with the preconditioner in effect (0: none)
+double poly_hi(const rails_iter *it)
+{
+    if (it->eig_max > 0.0) return it->eig_max;
+    return (it->jacobi && it->dinv) ? it->hi_jacobi : it->hi_plain;
+}
+
+// degree, interval and coefficients of a run; the work panels must be there (the fused kernel's rule looks at their row stride)
+int poly_setup(Run &run, const char *who)
+{
+    rails_iter *it = run.it;
+    run.K = it->poly_degree;
+    run.fused = false;
+    run.theta = 1.0;
+    if (run.K == 0) return RAILS_OK;
+    const double hi = poly_hi(it);
+    RAILS_REQUIRE(hi > 0.0 && rails_iter_finite(hi),
+                  "%s: poly_degree %d needs an upper bound on the spectrum: the operator keeps no CSR arrays on the host to take one from, set \"eig_max\"", who, run.K);
+    RAILS_REQUIRE(rails_cheb_coef(hi / it->poly_ratio, hi, run.K, &run.theta, run.ca, run.cb), "%s: no polynomial of degree %d on [%g, %g]", who, run.K,
+                  hi / it->poly_ratio, hi);
+    const rails_csr *A = it->A;
+    run.fused = it->poly_fused && rails_cheb_fused_eligible(A->kind == rails_csr::STORED && !A->rect && A->rowptr && A->col && A->val, A->n_ghost, it->m, it->w[W_Z]->ld);
+    return RAILS_OK;
+}
+
+// the passes' geometry for a group of w columns
+void set_group(Run &run, int w)
+{
+    const rails_iter *it = run.it;
+    const int pairs = (w + 1) / 2;
+    int tx_bits = 0;
+    while ((1 << tx_bits) < pairs) ++tx_bits; // <= 4
+    const int TY = 256 >> tx_bits;
+    // slabs of at least 8 rows per thread, at most 1024 of them (k_colnorms2's rule)
+    int64_t nslab = std::max<int64_t>(1, std::min<int64_t>(1024, it->m / ((int64_t)TY * 8)));
+    const int64_t rps = (it->m + nslab - 1) / nslab;
+    nslab = (it->m + rps - 1) / rps;
+    run.g = PassGeom{w, it->w[W_R]->ld, tx_bits, it->m, rps};
+    run.nslab = nslab;
+}
 
 } // namespace
 
@@ -505,6 +755,11 @@ extern "C" int rails_iter_create(rails_ctx *c, rails_csr *A, int method, const d
         v = 1.0 / v;
     }
     it->defsign = negative ? -1.0 : 1.0;
+    if (A->kind == rails_csr::STORED && (int64_t)A->h_rowptr.size() == m + 1 && (int64_t)A->h_val.size() == A->h_rowptr[m]) {
+        // the polynomial preconditioner's upper bounds (two numbers; used only with "poly_degree" above 0)
+        it->hi_plain = rails_cheb_gershgorin(m, A->h_rowptr.data(), A->h_val.data(), nullptr);
+        if (!dinv.empty()) it->hi_jacobi = rails_cheb_gershgorin(m, A->h_rowptr.data(), A->h_val.data(), dinv.data());
+    }
     hipError_t e = hipMalloc((void **)&it->status_dev, 16 * sizeof(int32_t));
     if (e == hipSuccess) e = hipMemset(it->status_dev, 0, 16 * sizeof(int32_t));
     if (e == hipSuccess && !dinv.empty()) {
@@ -538,8 +793,22 @@ extern "C" int rails_iter_set(rails_iter *it, const char *name, double value)
         it->check_every = (int)value;
     } else if (n == "strict")
         it->strict = value != 0.0;
+    else if (n == "poly_degree") {
+        RAILS_REQUIRE(value >= 0.0 && value <= RAILS_CHEB_MAX_DEGREE && value == std::floor(value), "rails_iter_set: poly_degree %g is not a whole number in 0 .. %d", value,
+                      RAILS_CHEB_MAX_DEGREE);
+        RAILS_REQUIRE(value == 0.0 || it->method == RAILS_ITER_CG,
+                      "rails_iter_set: poly_degree %g on a BiCGStab object: the polynomial preconditioner is for conjugate gradients (a real spectrum)", value);
+        it->poly_degree = (int)value;
+    } else if (n == "poly_ratio") {
+        RAILS_REQUIRE(value > 1.0, "rails_iter_set: poly_ratio %g is not above 1", value);
+        it->poly_ratio = value;
+    } else if (n == "eig_max") {
+        RAILS_REQUIRE(value >= 0.0, "rails_iter_set: eig_max %g", value);
+        it->eig_max = value;
+    } else if (n == "poly_fused")
+        it->poly_fused = value != 0.0;
     else {
-        rails_set_error("rails_iter_set: no setting named '%s' (tolerance, max_iterations, jacobi, check_every, strict)", name);
+        rails_set_error("rails_iter_set: no setting named '%s' (tolerance, max_iterations, jacobi, check_every, strict, poly_degree, poly_ratio, eig_max, poly_fused)", name);
         return RAILS_EINVAL;
     }
     return RAILS_OK;
@@ -556,7 +825,7 @@ extern "C" int rails_iter_solve(rails_ctx *c, rails_iter *it, int trans, const r
                   (long long)Y->m);
     RAILS_REQUIRE(xc0 >= 0 && nc >= 0 && xc0 + nc <= X->cap && yc0 >= 0 && yc0 + nc <= Y->cap, "rails_iter_solve: column windows outside the panels");
     if (X->d == Y->d) RAILS_REQUIRE(xc0 + nc <= yc0 || yc0 + nc <= xc0, "rails_iter_solve: X and Y windows alias");
-    it->last_dots = it->last_launches = it->last_products = 0;
+    it->last_dots = it->last_launches = it->last_products = it->last_poly = it->last_fused = 0;
     it->last.clear();
     if (nc == 0) return RAILS_OK;
     RAILS_TRY(grow_work(c, it, std::min(nc, RAILS_ITER_GROUP)));
@@ -568,18 +837,10 @@ extern "C" int rails_iter_solve(rails_ctx *c, rails_iter *it, int trans, const r
     run.trans = trans ? 1 : 0;
     run.jac = it->jacobi && it->dinv;
     run.tol2 = it->tol * it->tol;
+    RAILS_TRY(poly_setup(run, "rails_iter_solve"));
     for (int g0 = 0; g0 < nc; g0 += RAILS_ITER_GROUP) {
         const int w = std::min(RAILS_ITER_GROUP, nc - g0);
-        const int pairs = (w + 1) / 2;
-        int tx_bits = 0;
-        while ((1 << tx_bits) < pairs) ++tx_bits; // <= 4
-        const int TY = 256 >> tx_bits;
-        // slabs of at least 8 rows per thread, at most 1024 of them (k_colnorms2's rule)
-        int64_t nslab = std::max<int64_t>(1, std::min<int64_t>(1024, it->m / ((int64_t)TY * 8)));
-        const int64_t rps = (it->m + nslab - 1) / nslab;
-        nslab = (it->m + rps - 1) / rps;
-        run.g = PassGeom{w, it->w[W_X]->ld, tx_bits, it->m, rps};
-        run.nslab = nslab;
+        set_group(run, w);
         run.cols = it->cols_dev + g0;
         RAILS_TRY(rails_panel_copy(c, X, xc0 + g0, w, it->w[W_R], 0));
         RAILS_TRY(run.start());
@@ -618,10 +879,47 @@ extern "C" int rails_iter_solve(rails_ctx *c, rails_iter *it, int trans, const r
     return RAILS_OK;
 }
 
+// Y = p_K(G A) G X, the preconditioner the CG solve applies to its residual, on its own: a fixed linear approximate inverse.  K = 0: G X.
+extern "C" int rails_iter_precondition(rails_ctx *c, rails_iter *it, const rails_panel *X, int xc0, int nc, rails_panel *Y, int yc0)
+{
+    if (c) hipSetDevice(c->device);
+    RAILS_REQUIRE(c && it && X && Y, "rails_iter_precondition: null argument");
+    RAILS_REQUIRE(c == it->ctx, "rails_iter_precondition: the object belongs to another context");
+    RAILS_REQUIRE(c->nranks == 1 && !c->rccl, "rails_iter_precondition: single GPU only (the context has a partition or a communicator)");
+    RAILS_REQUIRE(X->m == it->m && Y->m == it->m, "rails_iter_precondition: the operator has %lld rows, X %lld, Y %lld", (long long)it->m, (long long)X->m,
+                  (long long)Y->m);
+    RAILS_REQUIRE(xc0 >= 0 && nc >= 0 && xc0 + nc <= X->cap && yc0 >= 0 && yc0 + nc <= Y->cap, "rails_iter_precondition: column windows outside the panels");
+    if (X->d == Y->d) RAILS_REQUIRE(xc0 + nc <= yc0 || yc0 + nc <= xc0, "rails_iter_precondition: X and Y windows alias");
+    it->last_dots = it->last_launches = it->last_products = it->last_poly = it->last_fused = 0; // the counters count this call
+    if (nc == 0) return RAILS_OK;
+    unsigned want = 1u << W_R | 1u << W_Z | 1u << W_D;
+    if (it->poly_degree > 0) want |= 1u << W_Z2 | 1u << W_Q;
+    RAILS_TRY(grow_work(c, it, std::min(nc, RAILS_ITER_GROUP), want));
+    Run run;
+    run.c = c;
+    run.it = it;
+    run.trans = 0;
+    run.jac = it->jacobi && it->dinv;
+    run.tol2 = 0.0;
+    run.cols = nullptr;
+    RAILS_TRY(poly_setup(run, "rails_iter_precondition"));
+    for (int g0 = 0; g0 < nc; g0 += RAILS_ITER_GROUP) {
+        const int w = std::min(RAILS_ITER_GROUP, nc - g0);
+        set_group(run, w);
+        RAILS_TRY(rails_panel_copy(c, X, xc0 + g0, w, it->w[W_R], 0));
+        RAILS_TRY(run.polynomial());
+        RAILS_TRY(rails_panel_copy(c, it->w[W_Z], 0, w, Y, yc0 + g0));
+    }
+    RAILS_HIP_CHECK(hipGetLastError());
+    return RAILS_OK;
+}
+
 // info[0] most iterations of a column in the last solve, [1] inner products of the last solve (per column and quantity), [2] kernel
 // launches of the library's own passes in it, [3] its columns that did not converge (any flag but converged), [4] those of them that
 // broke down, [5] worst relative residual of the recurrence, [6] work-panel columns, [7] products with A in the last solve; totals since
-// creation: [8] solves, [9] columns, [10] iterations summed over the columns, [11] flagged columns, [12] products with A.
+// creation: [8] solves, [9] columns, [10] iterations summed over the columns, [11] flagged columns, [12] products with A; the polynomial
+// preconditioner: [13] its applications in the last solve, [14] launches of the fused step kernel in it, [15] hi and [16] lo of the
+// interval in use (0 with degree 0).  [7] counts every product, those inside the fused step included.
 extern "C" int rails_iter_stats(const rails_iter *it, double *info, int cap)
 {
     RAILS_REQUIRE(it && info && cap >= 0, "rails_iter_stats: bad argument");
@@ -633,9 +931,11 @@ extern "C" int rails_iter_stats(const rails_iter *it, double *info, int cap)
         const double rel = c.bb > 0.0 ? std::sqrt(c.rr / c.bb) : 0.0;
         if (!(rel <= worst)) worst = rel; // a NaN shows
     }
-    const double v[13] = {most, (double)it->last_dots, (double)it->last_launches, unconv, broke, worst, (double)it->work_cols, (double)it->last_products,
-                          it->tot_solves, it->tot_columns, it->tot_iterations, it->tot_flagged, it->tot_products};
-    const int k = std::min(cap, 13);
+    const double hi = it->poly_degree > 0 ? poly_hi(it) : 0.0;
+    const double v[17] = {most, (double)it->last_dots, (double)it->last_launches, unconv, broke, worst, (double)it->work_cols, (double)it->last_products,
+                          it->tot_solves, it->tot_columns, it->tot_iterations, it->tot_flagged, it->tot_products,
+                          (double)it->last_poly, (double)it->last_fused, hi, hi / it->poly_ratio};
+    const int k = std::min(cap, 17);
     for (int i = 0; i < k; ++i) info[i] = v[i];
     return k;
 }

@@ -1,7 +1,8 @@
 """Iterative solves on the device as a library object (include/rails_hip.h: rails_iter_*, rails_amd/csrc/itsolve.hip): the approximate A^-1
 the reference allows for its inverse and extended Krylov projections (opts.Ainv of matlab/RAILSsolver.m:19-23, "This can be approximate")
 where a sparse LU is latency-bound or cannot be formed.  Conjugate gradients for a definite matrix, BiCGStab for a general one, Jacobi
-preconditioning; every column is a system of its own and all scalars stay on the device."""
+preconditioning, for conjugate gradients also a Chebyshev polynomial in the Jacobi-scaled matrix; every column is a system of its own and
+all scalars stay on the device."""
 import ctypes as C
 
 import numpy as np
@@ -23,9 +24,13 @@ class IterativeInverse:
     operator, a callback operator such as SchurOperator.op).  method: "cg", "bicgstab" or "auto" -- conjugate gradients when a matrix
     equals its transpose, BiCGStab otherwise; for an operator wrapper the caller names the method.  diag: the diagonal for the Jacobi
     preconditioner when A is an operator that is not a CSR matrix (None: the CSR diagonal where there is one).  `.op` is an operator handle
-    (HipOperatorWrapper) whose products are the solves: it goes wherever an operator goes (Solver.set_inverse, rails_spmm)."""
+    (HipOperatorWrapper) whose products are the solves: it goes wherever an operator goes (Solver.set_inverse, rails_spmm).
+    poly_degree K > 0 (conjugate gradients only): precondition with the Chebyshev polynomial z = p_K(G A) G r, K products per application
+    and no inner product between them, fitted to [hi / poly_ratio, hi]; hi is eig_max, or (None) a Gershgorin bound from the CSR arrays --
+    an operator that is not a CSR matrix needs eig_max.  poly_ratio None: the library's default."""
 
-    def __init__(self, ctx, A, method="auto", tol=1e-10, maxit=1000, jacobi=True, strict=False, diag=None, check_every=None):
+    def __init__(self, ctx, A, method="auto", tol=1e-10, maxit=1000, jacobi=True, strict=False, diag=None, check_every=None, poly_degree=0,
+                 poly_ratio=None, eig_max=None):
         self.ctx = ctx
         self._owned = None
         if isinstance(A, HipOperatorWrapper):
@@ -64,13 +69,21 @@ class IterativeInverse:
         self.set("strict", 1 if strict else 0)
         if check_every is not None:
             self.set("check_every", check_every)
+        if poly_ratio is not None:
+            self.set("poly_ratio", poly_ratio)
+        if eig_max is not None:
+            self.set("eig_max", eig_max)
+        if poly_degree:
+            self.set("poly_degree", poly_degree)
         oh = C.c_void_p()
         check(ctx.lib.rails_csr_create_iter(ctx.h, h, C.byref(oh)), "rails_csr_create_iter")
         self.op = HipOperatorWrapper(ctx, None, None, None, _handle=_Handle(ctx, oh))
         self.op.h._iter = self  # the solve object (and the operator it iterates on) outlives every copy of the handle
 
     def set(self, name, value):
-        """"tolerance", "max_iterations", "jacobi", "check_every", "strict" (rails_iter_set)"""
+        """"tolerance", "max_iterations", "jacobi", "check_every", "strict"; the polynomial preconditioner: "poly_degree" (0 .. 64, 0 is
+        off; conjugate gradients only), "poly_ratio" (hi / lo of its interval, above 1), "eig_max" (hi; 0: the Gershgorin bound),
+        "poly_fused" (0: never the fused step kernel) (rails_iter_set)"""
         check(self.ctx.lib.rails_iter_set(self.h, name.encode(), float(value)), "rails_iter_set")
 
     def solve(self, X, Y=None, trans=False):
@@ -82,6 +95,15 @@ class IterativeInverse:
         check(self.ctx.lib.rails_iter_solve(self.ctx.h, self.h, 1 if trans else 0, X.panel.h, X.c0, X.n, Y.panel.h, Y.c0), "rails_iter_solve")
         return Y
 
+    def precondition(self, X, Y=None):
+        """Y = p_K(G A) G X, the preconditioner of the solve on its own (K = poly_degree; 0: G X), for a HipMultiVectorWrapper X of m rows
+        (a new Y when None).  Queues its work and does not synchronise."""
+        if Y is None:
+            Y = HipMultiVectorWrapper(self.ctx, self.m, X.n)
+        assert Y.n == X.n
+        check(self.ctx.lib.rails_iter_precondition(self.ctx.h, self.h, X.panel.h, X.c0, X.n, Y.panel.h, Y.c0), "rails_iter_precondition")
+        return Y
+
     def solve_host(self, X, trans=False):
         """the same on a host array (m x nc): upload, solve, download"""
         X = np.asarray(X, dtype=np.float64)
@@ -90,12 +112,13 @@ class IterativeInverse:
 
     def stats(self):
         """the last solve and the totals since creation (rails_iter_stats)"""
-        info = (C.c_double * 13)()
-        k = self.ctx.lib.rails_iter_stats(self.h, info, 13)
+        info = (C.c_double * 17)()
+        k = self.ctx.lib.rails_iter_stats(self.h, info, 17)
         names = ("max_iterations_of_a_column", "inner_products", "launches", "unconverged_columns", "breakdown_columns", "worst_relative_residual",
-                 "workspace_columns", "products", "total_solves", "total_columns", "total_iterations", "total_flagged_columns", "total_products")
+                 "workspace_columns", "products", "total_solves", "total_columns", "total_iterations", "total_flagged_columns", "total_products",
+                 "poly_applications", "fused_launches", "eig_hi", "eig_lo")
         out = {names[i]: info[i] for i in range(max(k, 0))}
-        return {n: (v if n == "worst_relative_residual" else int(v)) for n, v in out.items()}
+        return {n: (v if n in ("worst_relative_residual", "eig_hi", "eig_lo") else int(v)) for n, v in out.items()}
 
     def columns(self):
         """per column of the last solve: (iterations, relative residual of the recurrence, flags -- FLAGS)"""

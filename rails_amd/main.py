@@ -2,7 +2,7 @@
 
     python -m rails_amd.main [params.xml] [--dir DIR] [--A A.mtx] [--B B.mtx] [--M M.mtx] [--V V.mtx] [--T T.mtx]
                                [--eigs K] [--variance FILE] [--sparse-B] [--warm-start V.mtx | --start-space S.mtx] [--restart-upon-start]
-                               [--inverse {lu,cg,bicgstab,iterative}] [--inverse-tol T]
+                               [--inverse {lu,cg,bicgstab,iterative}] [--inverse-tol T] [--inverse-poly K]
     python -m torch.distributed.run --nproc-per-node N -m rails_amd.main ...      (one rank per GPU, rows partitioned)
 
 File names, formats and the parameter file follow the reference's driver (src/main.cpp:57-68,111,123-126): `A.mtx`, `B.mtx`
@@ -19,7 +19,9 @@ keeps the rows of the Schur complement.
 `--inverse` chooses the A^-1 of a "Projection method" above 1 (opts.Ainv, matlab/RAILSsolver.m:19-23): `lu` (the default) a sparse LU
 factorised on the host and applied on the device, `cg` / `bicgstab` an iteration on the device to the relative tolerance `--inverse-tol`
 (rails_amd.IterativeInverse; the reference allows an approximate inverse), `iterative` conjugate gradients when A equals its transpose and
-BiCGStab otherwise.  A Schur-complement problem keeps the inverse of its Schur operator.
+BiCGStab otherwise.  `--inverse-poly K` preconditions the conjugate gradients with a Chebyshev polynomial of degree K (K products in a
+row without an inner product between them; 0, the default, is off); with an inverse that resolves to BiCGStab the driver refuses it.  A
+Schur-complement problem keeps the inverse of its Schur operator.
 
 `--eigs K` and `--variance FILE` are the second half of the reference's driver (src/main.cpp:140-170) on the solution object
 (rails_amd.Solution): the K eigenvalues of largest modulus of the covariance X, each next to its share of the trace, written to
@@ -66,6 +68,8 @@ def main(argv=None):
     ap.add_argument("--inverse", choices=("lu", "cg", "bicgstab", "iterative"), default="lu", help="the A^-1 of a 'Projection method' above 1: a sparse LU (default), "
                                                                                                    "or an iteration on the device (iterative: CG for a symmetric A, BiCGStab otherwise)")
     ap.add_argument("--inverse-tol", type=float, default=1e-10, metavar="T", help="relative tolerance of an iterative inverse (per column)")
+    ap.add_argument("--inverse-poly", type=int, default=0, metavar="K", help="degree of the Chebyshev polynomial preconditioner of a conjugate-gradients inverse "
+                                                                            "(K products per application; 0: off)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args(argv)
@@ -219,9 +223,16 @@ def main(argv=None):
         else:
             inverse = rails_amd.IterativeInverse(ctx, (rowptr, col.astype(np.int32), val), method="auto" if args.inverse == "iterative" else args.inverse,
                                                  tol=args.inverse_tol)
+            if args.inverse_poly and inverse.method != "cg":
+                raise SystemExit("--inverse-poly %d: the polynomial preconditioner is for conjugate gradients, and the inverse chosen is %s" % (
+                    args.inverse_poly, inverse.method))
+            if args.inverse_poly:
+                inverse.set("poly_degree", args.inverse_poly)
         solver.set_inverse(inverse)
         if isinstance(inverse, rails_amd.IterativeInverse):
             _log(rank, "Projection method %g: A^-1 is an iterative solve on the device, method %s, Jacobi, tolerance %g" % (method, inverse.method, args.inverse_tol))
+            if args.inverse_poly:
+                _log(rank, "its preconditioner: a Chebyshev polynomial of degree %d in the Jacobi-scaled matrix" % args.inverse_poly)
         else:
             _log(rank, "Projection method %g: A^-1 is %s; nnz(L+U) %d, factorised in %.2f s" % (method, what, inverse.nnz, time.time() - t0))
 

@@ -4,6 +4,12 @@ the passes against 8 TB/s), check_every at 1, 8 and 32, and the projection metho
 --reps runs after --warmup.  Prints one JSON object per row; --out writes them all to a file.
 
     python scripts/iter_bench.py [--reps 10] [--warmup 2] [--widths 1 16 32] [--skip-large] [--out profiles/iter_bench.json]
+
+--poly K[,K..] runs the sweep of the Chebyshev polynomial preconditioner instead: CG to 1e-10 on the same
+Laplacians and on laplace7(100,100,100) at every degree given, with the fused step kernel and without it, degree 0 in the same run as the
+comparison, and the end-to-end line (256 x 256, method 2.2, CG at 1e-8) at degree 0 and at the degree that was fastest at 16 columns.
+
+    python scripts/iter_bench.py --poly 0,2,4,8 [--poly-ratio R] --out profiles/iter_poly_bench.json
 """
 import argparse
 import json
@@ -69,6 +75,74 @@ def iter_row(ctx, rails_amd, inv, A, name, nc, tol, a, split=False):
     return row
 
 
+def solver_row(ctx, rails_amd, A, op, B, method, kind, poly=0, ratio=None):
+    """one end-to-end solve of the 256 x 256 problem: method 1, or 2.2 with the LU or CG at 1e-8 (polynomial of degree `poly`) as A^-1"""
+    inverse = None
+    t0 = time.perf_counter()
+    if kind == "lu":
+        inverse = rails_amd.SparseLU(ctx, A)
+    elif kind:
+        inverse = rails_amd.IterativeInverse(ctx, A, method="cg", tol=1e-8, maxit=20000, poly_degree=poly, poly_ratio=ratio)
+    t_setup = time.perf_counter() - t0
+    ctx.set_seed(1)
+    s = rails_amd.Solver(ctx, op, B)
+    if inverse is not None:
+        s.set_inverse(inverse)
+    assert s.set_parameters({"Maximum iterations": 3000, "Tolerance": 1e-6, "Expand size": 3, "Lanczos iterations": 10, "Projection method": method}) == 0
+    s.set_option("verbose", 0)
+    ctx.sync()
+    t0 = time.perf_counter()
+    code, V, T = s.solve()
+    ctx.sync()
+    row = {"problem": "laplace 256x256", "method": method, "inverse": kind, "code": code, "trips": s.trips(), "seconds": time.perf_counter() - t0,
+           "inverse_setup_seconds": t_setup, "k": V.shape[1], "relative_residual": s.relative_residual()}
+    if kind and kind != "lu":
+        st = inverse.stats()
+        row.update({"inner_solves": st["total_solves"], "inner_iterations": st["total_iterations"], "flagged_columns": st["total_flagged_columns"],
+                    "poly_degree": poly, "inner_products_with_A": st["total_products"]})
+    s.close()
+    if inverse is not None:
+        inverse.close()
+    return row
+
+
+def poly_sweep(ctx, rails_amd, a, emit):
+    import scipy.sparse as sp
+
+    from rails_amd import problems as P
+
+    degrees = [int(v) for v in a.poly.split(",")]
+    problems = [("laplace %dx%d" % (k, k), laplacian(k)) for k in a.grids]
+    if not a.skip_large:
+        rowptr, col, val = P.laplace7(100, 100, 100)
+        n = rowptr.size - 1
+        problems.append(("laplace7(100,100,100)", sp.csr_matrix((val, col, rowptr), shape=(n, n))))
+    best = {}
+    for name, A in problems:
+        inv = rails_amd.IterativeInverse(ctx, A, method="cg", maxit=20000, poly_ratio=a.poly_ratio)
+        for nc in a.widths:
+            for K in degrees:
+                for fused in ((1, 0) if K else (1,)):
+                    inv.set("poly_degree", K)
+                    inv.set("poly_fused", fused)
+                    row = iter_row(ctx, rails_amd, inv, A, name, nc, 1e-10, a)
+                    st = inv.stats()
+                    row.update({"poly_degree": K, "poly_fused": fused if K else None, "poly_ratio": st["eig_hi"] / st["eig_lo"] if K else None,
+                                "inner_products": st["inner_products"], "fused_launches": st["fused_launches"]})
+                    emit("poly", row)
+                    if nc == 16 and (name not in best or row["solve_ms"] < best[name][0]):
+                        best[name] = (row["solve_ms"], K)
+        inv.close()
+    if not a.skip_solver:
+        A = laplacian(256)
+        n = A.shape[0]
+        op = rails_amd.HipOperatorWrapper(ctx, A.indptr.astype(np.int64), A.indices.astype(np.int32), A.data.astype(np.float64))
+        B = np.asfortranarray(np.random.default_rng(4).uniform(0, 1, (n, 1)))
+        K = best.get("laplace 256x256", (0.0, max(degrees)))[1]
+        for poly in sorted({0, K}):
+            emit("poly_solver", solver_row(ctx, rails_amd, A, op, B, 2.2, "iterative 1e-8", poly=poly, ratio=a.poly_ratio))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -77,6 +151,8 @@ def main():
     ap.add_argument("--grids", type=int, nargs="+", default=[256, 512])
     ap.add_argument("--skip-large", action="store_true", help="leave out the 1M-row operators")
     ap.add_argument("--skip-solver", action="store_true", help="leave out the end-to-end projection runs")
+    ap.add_argument("--poly", metavar="K[,K..]", help="the sweep of the polynomial preconditioner at these degrees, instead of everything else")
+    ap.add_argument("--poly-ratio", type=float, default=None, help="hi / lo of the polynomial's interval (default: the library's)")
     ap.add_argument("--out")
     a = ap.parse_args()
     import scipy.sparse as sp
@@ -89,8 +165,17 @@ def main():
     out = {"laplace2d": [], "large": [], "check_every": [], "solver": []}
 
     def emit(key, row):
-        out[key].append(row)
+        out.setdefault(key, []).append(row)
         print(json.dumps(row), flush=True)
+
+    if a.poly:
+        out = {}
+        poly_sweep(ctx, rails_amd, a, emit)
+        ctx.close()
+        if a.out:
+            with open(a.out, "w") as fh:
+                json.dump(out, fh, indent=1)
+        return
 
     for k in a.grids:
         A = laplacian(k)
@@ -139,32 +224,7 @@ def main():
         B = np.asfortranarray(np.random.default_rng(4).uniform(0, 1, (n, 1)))
         op = rails_amd.HipOperatorWrapper(ctx, *csr)
         for method, kind in ((1.0, None), (2.2, "lu"), (2.2, "iterative 1e-8")):
-            inverse = None
-            t0 = time.perf_counter()
-            if kind == "lu":
-                inverse = rails_amd.SparseLU(ctx, A)
-            elif kind:
-                inverse = rails_amd.IterativeInverse(ctx, A, method="cg", tol=1e-8, maxit=20000)
-            t_setup = time.perf_counter() - t0
-            ctx.set_seed(1)
-            s = rails_amd.Solver(ctx, op, B)
-            if inverse is not None:
-                s.set_inverse(inverse)
-            assert s.set_parameters({"Maximum iterations": 3000, "Tolerance": 1e-6, "Expand size": 3, "Lanczos iterations": 10, "Projection method": method}) == 0
-            s.set_option("verbose", 0)
-            ctx.sync()
-            t0 = time.perf_counter()
-            code, V, T = s.solve()
-            ctx.sync()
-            row = {"problem": "laplace 256x256", "method": method, "inverse": kind, "code": code, "trips": s.trips(), "seconds": time.perf_counter() - t0,
-                   "inverse_setup_seconds": t_setup, "k": V.shape[1], "relative_residual": s.relative_residual()}
-            if kind and kind != "lu":
-                st = inverse.stats()
-                row.update({"inner_solves": st["total_solves"], "inner_iterations": st["total_iterations"], "flagged_columns": st["total_flagged_columns"]})
-            emit("solver", row)
-            s.close()
-            if inverse is not None:
-                inverse.close()
+            emit("solver", solver_row(ctx, rails_amd, A, op, B, method, kind))
     ctx.close()
     if a.out:
         with open(a.out, "w") as fh:
