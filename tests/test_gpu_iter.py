@@ -1,7 +1,8 @@
 """The iterative A^-1 operator (include/rails_hip.h: rails_iter_*, rails_amd/csrc/itsolve.hip) on the GPU against the numpy restatement of
 tests/iter_reference.py: solves through the operator handle (rails_spmm) and through rails_iter_solve on full panels and on windows at odd
 columns of wide panels, the transposed solve, determinism and independence of check_every, columns of different speed in one solve, the
-iteration cap, the breakdown rule, the refusals, and the work panels."""
+iteration cap, the breakdown rule, the refusals, and the work panels.
+The passes themselves, iterate by iterate against a longdouble run: tests/test_gpu_iter_steps.py."""
 import ctypes as C
 
 import numpy as np
