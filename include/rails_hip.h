@@ -228,7 +228,18 @@ int rails_csr_create_lu(rails_ctx *ctx, rails_lu *lu, rails_csr **out);
  * comes from diag_host (m entries, none zero); with diag_host = NULL from the CSR diagonal when A is a CSR matrix and every diagonal
  * entry is stored and nonzero; otherwise there is none.  Every column is a system of its own (start value zero, tolerance relative to
  * its own ||b||); all scalars stay on the device and the host reads one number back every `check_every` iterations.  No floating-point
- * atomics: two solves of the same input give the same bits, whatever check_every is.  Single GPU only.
+ * atomics: two solves of the same input give the same bits, whatever check_every is.
+ * On a row partition.  A context reduces when it has more than one rank, an all-reduce hook or an RCCL communicator.  On such a context
+ * A may be a stored CSR row block with ghost columns whose halo plan is set (rails_csr_set_halo; "square" then means globally), the
+ * inner products are summed over the ranks (an all-reduce of at most 64 doubles between the kernel that sums this rank's partial sums and
+ * the kernel that computes the scalars), and every rank holds the same scalars, flags and counts bit for bit.  rails_iter_create,
+ * rails_iter_set, rails_iter_solve and rails_iter_precondition are then collective calls: every rank makes them in the same order with
+ * the same nc and settings.  rails_iter_create makes one all-reduce, through which the ranks agree on whether the Jacobi diagonal exists
+ * (on every rank, or on none), on the sign of the diagonal (negative only when it is on every rank) and on the two Gershgorin bounds (the
+ * largest).  The hook or the communicator has to be installed before the object is made: a context with more than one rank and neither
+ * is refused (RAILS_EINVAL), since the first inner product would fail.  A transposed solve (trans != 0) on an operator with ghost rows is
+ * refused with RAILS_EINVAL before any collective: the transposed product of a row block is single GPU.  A right-hand side that is not
+ * finite on any rank gives RAILS_EINVAL on every rank.  On a context that does not reduce nothing of this runs.
  * Settings (rails_iter_set): "tolerance" 1e-10, "max_iterations" 1000, "jacobi" 1, "check_every" 8, "strict" 0, and those of the polynomial
  * preconditioner below: "poly_degree" 0, "poly_ratio" 10, "eig_max" 0, "poly_fused" 1.
  * Chebyshev polynomial preconditioner (CG only; rails_amd/csrc/cheb_coef.h): with "poly_degree" K in 1 .. 64 the
@@ -237,7 +248,9 @@ int rails_csr_create_lu(rails_ctx *ctx, rails_lu *lu, rails_csr **out);
  * polynomial is fitted to [hi / "poly_ratio", hi]; hi is a Gershgorin bound on the spectrum of G A taken at create time from the CSR
  * arrays a stored operator keeps on the host, or "eig_max" when that is above 0 (an operator without host arrays -- a callback, an LU
  * handle -- needs it).  For a stored CSR operator without ghost rows, of fewer than 2^24 rows and with work panels below 4 GiB each
- * product is fused with its recurrence update in one kernel ("poly_fused" 0: never).  Degree 0, the default, is the solve without any
+ * product is fused with its recurrence update in one kernel ("poly_fused" 0: never); a row block with ghost rows (fewer than 2^24 of
+ * them) takes the same kernel in a ghost-row form, behind a ghost-row exchange the object issues itself -- one exchange per product
+ * either way, and no all-reduce inside the polynomial.  Degree 0, the default, is the solve without any
  * of this, bit for bit.  RAILS_EINVAL: a degree above 0 on a BiCGStab object, a degree outside 0 .. 64, a ratio of at most 1, and a
  * solve with a degree above 0 and no bound.
  * Outcomes: a zero right-hand-side column gives x = 0 after 0 iterations; a column that stops at max_iterations or breaks down (a
@@ -261,7 +274,10 @@ int rails_iter_precondition(rails_ctx *ctx, rails_iter *it, const rails_panel *X
  * converge, [4] of those, broken down, [5] worst relative residual of the recurrence, [6] work-panel columns, [7] products with A;
  * totals since creation: [8] solves, [9] columns, [10] iterations summed over columns, [11] flagged columns, [12] products; the polynomial
  * preconditioner: [13] its applications in the last solve, [14] launches of the fused step kernel, [15] hi and [16] lo of the interval in
- * use (0 with degree 0).  [7] counts every product with A, those inside fused steps included.  Returns the number of entries written (at
+ * use (0 with degree 0); on a context that reduces: [17] all-reduces issued in the last call (per group of 32 columns, conjugate gradients
+ * 1 at the start and 2 per queued iteration, BiCGStab 1 and 3; the polynomial adds none), [18] ghost-row exchanges the object issued
+ * itself (before fused steps; those inside rails_spmm are not counted).  [7] counts every product with A, those inside fused steps
+ * included.  Returns the number of entries written (at
  * most cap: a caller that passes 13 sees what it always saw), or a negative code. */
 int rails_iter_stats(const rails_iter *it, double *info, int cap);
 /* Per column of the last solve (any pointer may be NULL): iterations, relative residual of the recurrence, flags (2 converged, 4 stopped at

@@ -57,4 +57,17 @@ inline bool rails_cheb_fused_eligible(bool stored_csr, int64_t n_ghost, int64_t 
     return (uint64_t)m * (uint64_t)ld * 8u < 0xffffff00ull;
 }
 
+// The ghost-row form of the fused step (a row-partitioned operator with its halo plan set): column c < m is a row of the work panel
+// (stride ld), column c >= m is row c - m of the operator's ghost buffer (n_ghost rows of ldg doubles, filled by the exchange the object
+// makes before the step) -- k_spmm_narrow's select between two bases and two strides, each with 24-bit row numbers and 32-bit byte
+// offsets.  So: a stored CSR operator, 1 <= m < 2^24 local rows and fewer than 2^24 ghost rows, both row strides times 8 below 2^24, the
+// panel and the ghost buffer below 4 GiB each.
+inline bool rails_cheb_fused_ghost_eligible(bool stored_csr, int64_t m, int64_t n_ghost, int64_t ld, int64_t ldg)
+{
+    if (!stored_csr || m < 1 || n_ghost < 0 || ld < 1 || ldg < 1) return false;
+    if (m >= (int64_t)1 << 24 || n_ghost >= (int64_t)1 << 24) return false;
+    if (ld * 8 >= (int64_t)1 << 24 || ldg * 8 >= (int64_t)1 << 24) return false;
+    return (uint64_t)m * (uint64_t)ld * 8u < 0xffffff00ull && (uint64_t)n_ghost * (uint64_t)ldg * 8u < 0xffffff00ull;
+}
+
 #endif

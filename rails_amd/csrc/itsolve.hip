@@ -16,8 +16,13 @@
 // Passes: thread (tx, ty) of a block owns the column pair 2 tx, 2 tx + 1 and every TY-th row of its block's slab (k_colnorms2's shape,
 // dense.hip), adds its rows in increasing order, the TY row classes meet in an LDS tree of fixed shape, the per-block partial sums go to
 // the context workspace, and the one-workgroup kernel k_iter_scalars sums them over the blocks in a fixed order (iter_reduce) and then
-// computes the scalars (iter_compute) -- two device functions, so that an all-reduce can sit between them in a row-partitioned form.
-// No floating-point atomics: two runs give the same bits.
+// computes the scalars (iter_compute).  No floating-point atomics: two runs give the same bits.
+//
+// On a context that reduces (more than one rank, an all-reduce hook, a communicator) the two device functions are two kernels with an
+// all-reduce of the sums between them (k_iter_reduce, rails_allreduce_dev, k_iter_compute): every rank holds the same scalars bit for bit,
+// so every rank queues the same iterations and issues the same collectives.  A is then a row block with its ghost-row plan; the products
+// exchange ghost rows inside rails_spmm, the fused polynomial step in its ghost-row form behind an exchange of the object's own.  What
+// the ranks must agree on when the object is made is iter_agree.h.  DESIGN.md section 14, "On a row partition".
 #include "rails_internal.h"
 
 #include <algorithm>
@@ -25,6 +30,7 @@
 #include <vector>
 
 #include "cheb_coef.h"
+#include "iter_agree.h"
 #include "iter_scalars.h"
 
 namespace {
@@ -263,11 +269,16 @@ __global__ __launch_bounds__(256) void k_cheb_pass(PassGeom g, const double *__r
 // is longer than the LDS buffer and for the lane of an odd last column), then in the same thread d = a d + b g (r - t) in place and
 // Zout = Zin + d.  Zin and Zout are different panels: every block reads rows of Zin that other blocks own.  All panels are work panels of
 // the object: window at column 0, one row stride, rows 16-byte aligned.  No atomics, no inner products.
-template <int RPG, int LPR>
+//
+// GHOST, a row-partitioned operator: column c >= m is row c - m of the operator's ghost buffer Zg (row stride ldg doubles), which the
+// object fills before the step with the rows of Zin the neighbours own (rails_halo_exchange, an even number of columns, so that ghost rows
+// are 16-byte aligned like panel rows) -- the select between two bases and two strides k_spmm_narrow<RPG, true, LPR> makes.  The epilogue
+// is the same: local rows only.
+template <int RPG, int LPR, bool GHOST>
 __global__ __launch_bounds__(256) void k_cheb_step_csr(int64_t m, const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
                                                        const double *__restrict__ val, const double *__restrict__ Zin, int ld, int nc, int64_t blocks_per_xcd,
                                                        const double *__restrict__ gvec, double gs, double a, double b, const double *__restrict__ R,
-                                                       double *__restrict__ D, double *__restrict__ Zout)
+                                                       double *__restrict__ D, double *__restrict__ Zout, const double *__restrict__ Zg, int ldg)
 {
     constexpr int GROUPS = 256 / LPR, ROWS = GROUPS * RPG, CAP = 2048;
     __shared__ double s_val[CAP];
@@ -291,8 +302,13 @@ __global__ __launch_bounds__(256) void k_cheb_step_csr(int64_t m, const int64_t 
     if (cb >= nc) return;
     const bool full = (cb + 2 <= nc);
     const uint32_t cb8 = (uint32_t)cb * 8u, ld8 = (uint32_t)ld * 8u;
-    const char *Zb = reinterpret_cast<const char *>(Zin);
-    auto zrow = [&](uint32_t c) -> const char * { return Zb + (__umul24(c, ld8) + cb8); };
+    const uint32_t ldg8 = (uint32_t)ldg * 8u, m32 = (uint32_t)m;
+    const char *Zb = reinterpret_cast<const char *>(Zin), *Gb = reinterpret_cast<const char *>(Zg);
+    auto zrow = [&](uint32_t c) -> const char * {
+        if (!GHOST) return Zb + (__umul24(c, ld8) + cb8);
+        const bool local = c < m32;
+        return (local ? Zb : Gb) + ((local ? __umul24(c, ld8) : __umul24(c - m32, ldg8)) + cb8);
+    };
     for (int rr = 0; rr < RPG; ++rr) {
         const int64_t row = r0 + (int64_t)rr * GROUPS + g; // the rows in flight are consecutive
         if (row >= m) break;
@@ -392,12 +408,10 @@ __device__ __forceinline__ void iter_compute(int step, rails_iter_col &c, double
     }
 }
 
-// one workgroup: reduce, compute, count.  status[0] = active columns, status[1] = columns whose right-hand side is not finite (start only)
-__global__ __launch_bounds__(1024) void k_iter_scalars(int step, const double *__restrict__ partial, int64_t nslab, int ncw, int nq,
-                                                       rails_iter_col *cols, int32_t *status, double tol2, int maxit, double sign)
+// the columns' scalar step from the reduced sums, then the count (thread 0 of the one workgroup)
+__device__ __forceinline__ void iter_columns(int step, const double *sums, int ncw, int nq, rails_iter_col *cols, int32_t *status, double tol2, int maxit,
+                                             double sign)
 {
-    __shared__ double sums[64];
-    iter_reduce(partial, nslab, nq * ncw, sums);
     if ((int)threadIdx.x < ncw) {
         rails_iter_col c = cols[threadIdx.x];
         iter_compute(step, c, sums[threadIdx.x], nq == 2 ? sums[ncw + threadIdx.x] : 0.0, tol2, maxit, sign);
@@ -413,6 +427,32 @@ __global__ __launch_bounds__(1024) void k_iter_scalars(int step, const double *_
         status[0] = active;
         if (step == STEP_CG_INIT || step == STEP_BI_INIT) status[1] = bad;
     }
+}
+
+// one workgroup: reduce, compute, count.  status[0] = active columns, status[1] = columns whose right-hand side is not finite (start only)
+__global__ __launch_bounds__(1024) void k_iter_scalars(int step, const double *__restrict__ partial, int64_t nslab, int ncw, int nq,
+                                                       rails_iter_col *cols, int32_t *status, double tol2, int maxit, double sign)
+{
+    __shared__ double sums[64];
+    iter_reduce(partial, nslab, nq * ncw, sums);
+    iter_columns(step, sums, ncw, nq, cols, status, tol2, maxit, sign);
+}
+
+// The scalar step of a context that reduces (a row partition, an all-reduce hook, a communicator), in three stream-ordered steps:
+// k_iter_reduce sums this rank's partial sums exactly as k_iter_scalars does and writes the nq * ncw <= 64 sums to a buffer of the
+// object, rails_allreduce_dev adds them over the ranks, k_iter_compute goes on from there.  Every rank then computes from the same sums,
+// so the columns' scalars, flags and the active count are the same bits on every rank.
+__global__ __launch_bounds__(1024) void k_iter_reduce(const double *__restrict__ partial, int64_t nslab, int n, double *__restrict__ out)
+{
+    __shared__ double sums[64];
+    iter_reduce(partial, nslab, n, sums);
+    if ((int)threadIdx.x < n) out[threadIdx.x] = sums[threadIdx.x];
+}
+
+__global__ __launch_bounds__(64) void k_iter_compute(int step, const double *__restrict__ sums, int ncw, int nq, rails_iter_col *cols, int32_t *status,
+                                                     double tol2, int maxit, double sign)
+{
+    iter_columns(step, sums, ncw, nq, cols, status, tol2, maxit, sign);
 }
 
 // CG: x r p q [z]; BiCGStab: x r p v(=Q) [p^(=Z)] r^ t [s^]; the polynomial: z, its direction d, the second z of the fused step's ping-pong
@@ -444,6 +484,10 @@ struct rails_iter {
     double poly_ratio = RAILS_ITER_POLY_RATIO, eig_max = 0.0;
     double hi_jacobi = 0.0, hi_plain = 0.0; // Gershgorin bounds on D^-1 A and on +-A from the host CSR arrays (0: none)
     long last_poly = 0, last_fused = 0;
+    // a context that reduces (rails_allreduce_dev does something on it): the scalar step in three parts around an all-reduce of `sums_dev`
+    bool reduces = false;
+    double *sums_dev = nullptr; // 64 doubles
+    long last_allreduces = 0, last_halo = 0; // all-reduces of the last call; ghost-row exchanges the object issued itself (fused steps)
     double tot_solves = 0, tot_iterations = 0, tot_flagged = 0, tot_products = 0, tot_columns = 0;
 };
 
@@ -520,16 +564,24 @@ struct Run {
     double tol2;
     // the polynomial: degree (0: off), theta and the coefficient pairs, whether its steps run on the fused kernel
     int K = 0;
-    bool fused = false;
+    bool fused = false, ghost = false; // ghost: the fused step in its ghost-row form, with an exchange of the object's own before it
     double theta = 1.0, ca[RAILS_CHEB_MAX_DEGREE], cb[RAILS_CHEB_MAX_DEGREE];
 
     double *d(int k) const { return it->w[k]->d; }
     int scalars(int step, int nq)
     {
         // (with the polynomial r.z carries the sign of the operator itself, as with Jacobi)
-        RAILS_LAUNCH(k_iter_scalars, dim3(1), dim3(1024), 0, c->stream, step, c->ws, nslab, g.ncw, nq, cols, it->status_dev, tol2, it->maxit,
-                     (jac || K > 0) ? 1.0 : it->defsign);
-        it->last_launches++;
+        const double sign = (jac || K > 0) ? 1.0 : it->defsign;
+        if (!it->reduces) {
+            RAILS_LAUNCH(k_iter_scalars, dim3(1), dim3(1024), 0, c->stream, step, c->ws, nslab, g.ncw, nq, cols, it->status_dev, tol2, it->maxit, sign);
+            it->last_launches++;
+            return RAILS_OK;
+        }
+        RAILS_LAUNCH(k_iter_reduce, dim3(1), dim3(1024), 0, c->stream, c->ws, nslab, nq * g.ncw, it->sums_dev);
+        RAILS_TRY(rails_allreduce_dev(c, it->sums_dev, (size_t)(nq * g.ncw)));
+        it->last_allreduces++;
+        RAILS_LAUNCH(k_iter_compute, dim3(1), dim3(64), 0, c->stream, step, it->sums_dev, g.ncw, nq, cols, it->status_dev, tol2, it->maxit, sign);
+        it->last_launches += 2;
         return RAILS_OK;
     }
     int product(int from, int to)
@@ -579,12 +631,27 @@ struct Run {
                 continue;
             }
             const int zout = zin == W_Z ? W_Z2 : W_Z;
-            if (g.ncw <= 16)
-                RAILS_LAUNCH((k_cheb_step_csr<2, 8>), dim3((unsigned)(bpx * 8)), block, 0, c->stream, it->m, A->rowptr, A->col, A->val, d(zin), g.ld, g.ncw, bpx,
-                             gvec, gs, ca[k], cb[k], d(W_R), d(W_D), d(zout));
+            if (ghost) {
+                // one exchange per step, as the unfused step's rails_spmm makes one: ranks that choose differently stay in step.  An even
+                // number of columns, so that ghost rows are as aligned as panel rows: at an odd width the panel's column ncw travels too.
+                // That is the pad column (zeroed at allocation, never written) when the group is as wide as the panels, and a column a
+                // wider group has used otherwise; on the receiving side nobody reads it, since the lane of an odd last column takes its
+                // one-entry path -- what it holds reaches no result, as with the pair loads of every pass (section 14's last test)
+                const int nce = (g.ncw + 1) & ~1;
+                RAILS_TRY(rails_halo_exchange(c, it->A, d(zin), g.ld, nce));
+                it->last_halo++;
+                if (g.ncw <= 16)
+                    RAILS_LAUNCH((k_cheb_step_csr<2, 8, true>), dim3((unsigned)(bpx * 8)), block, 0, c->stream, it->m, A->rowptr, A->col, A->val, d(zin), g.ld,
+                                 g.ncw, bpx, gvec, gs, ca[k], cb[k], d(W_R), d(W_D), d(zout), A->ext, nce);
+                else
+                    RAILS_LAUNCH((k_cheb_step_csr<4, 16, true>), dim3((unsigned)(bpx * 8)), block, 0, c->stream, it->m, A->rowptr, A->col, A->val, d(zin), g.ld,
+                                 g.ncw, bpx, gvec, gs, ca[k], cb[k], d(W_R), d(W_D), d(zout), A->ext, nce);
+            } else if (g.ncw <= 16)
+                RAILS_LAUNCH((k_cheb_step_csr<2, 8, false>), dim3((unsigned)(bpx * 8)), block, 0, c->stream, it->m, A->rowptr, A->col, A->val, d(zin), g.ld, g.ncw, bpx,
+                             gvec, gs, ca[k], cb[k], d(W_R), d(W_D), d(zout), nullptr, 0);
             else
-                RAILS_LAUNCH((k_cheb_step_csr<4, 16>), dim3((unsigned)(bpx * 8)), block, 0, c->stream, it->m, A->rowptr, A->col, A->val, d(zin), g.ld, g.ncw, bpx,
-                             gvec, gs, ca[k], cb[k], d(W_R), d(W_D), d(zout));
+                RAILS_LAUNCH((k_cheb_step_csr<4, 16, false>), dim3((unsigned)(bpx * 8)), block, 0, c->stream, it->m, A->rowptr, A->col, A->val, d(zin), g.ld, g.ncw, bpx,
+                             gvec, gs, ca[k], cb[k], d(W_R), d(W_D), d(zout), nullptr, 0);
             it->last_launches++;
             it->last_products++;
             it->last_fused++;
@@ -676,7 +743,16 @@ int poly_setup(Run &run, const char *who)
     RAILS_REQUIRE(rails_cheb_coef(hi / it->poly_ratio, hi, run.K, &run.theta, run.ca, run.cb), "%s: no polynomial of degree %d on [%g, %g]", who, run.K,
                   hi / it->poly_ratio, hi);
     const rails_csr *A = it->A;
-    run.fused = it->poly_fused && rails_cheb_fused_eligible(A->kind == rails_csr::STORED && !A->rect && A->rowptr && A->col && A->val, A->n_ghost, it->m, it->w[W_Z]->ld);
+    const bool stored = A->kind == rails_csr::STORED && !A->rect && A->rowptr && A->col && A->val;
+    // an operator that exchanges (rows to send or ghost rows to receive: rails_spmm's own condition, so that a step issues an exchange in
+    // the fused form exactly when it does in the unfused one -- a rank that only sends, or only receives, takes part; a rank whose plan is
+    // empty issues none in either form) takes the ghost-row form; its ghost buffer's row stride is the group's width rounded up to even,
+    // at most RAILS_ITER_GROUP
+    run.ghost = A->n_ghost > 0 || A->n_send > 0;
+    if (run.ghost)
+        run.fused = it->poly_fused && rails_cheb_fused_ghost_eligible(stored, it->m, A->n_ghost, it->w[W_Z]->ld, RAILS_ITER_GROUP);
+    else
+        run.fused = it->poly_fused && rails_cheb_fused_eligible(stored, A->n_ghost, it->m, it->w[W_Z]->ld);
     return RAILS_OK;
 }
 
@@ -709,27 +785,64 @@ extern "C" void rails_iter_destroy(rails_iter *it)
     hipFree(it->dinv);
     hipFree(it->cols_dev);
     hipFree(it->status_dev);
+    hipFree(it->sums_dev);
     if (it->pinned) hipHostFree(it->pinned);
     delete it;
 }
 
+namespace {
+
+// The gather of iter_agree.h: this rank's slot of a zeroed vector of nranks slots, one sum all-reduce, the whole vector back on the host.
+int gather_slots(rails_ctx *c, const double *mine, std::vector<double> &all)
+{
+    const int nr = std::max(1, c->nranks), n = nr * RAILS_AGREE_SLOT;
+    RAILS_REQUIRE(c->rank >= 0 && c->rank < nr, "rails_iter_create: rank %d of %d", c->rank, nr);
+    all.assign((size_t)n, 0.0);
+    std::copy(mine, mine + RAILS_AGREE_SLOT, all.begin() + (size_t)c->rank * RAILS_AGREE_SLOT);
+    double *dev = nullptr;
+    RAILS_HIP_CHECK(hipMalloc((void **)&dev, (size_t)n * sizeof(double)));
+    int rc = RAILS_OK;
+    hipError_t e = hipMemcpyAsync(dev, all.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // (the source is pageable host memory)
+    if (e == hipSuccess) rc = rails_allreduce_dev(c, dev, (size_t)n);
+    if (e == hipSuccess && rc == RAILS_OK) e = hipMemcpyAsync(all.data(), dev, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && rc == RAILS_OK) e = rails_stream_sync(c);
+    hipFree(dev);
+    if (rc != RAILS_OK) return rc;
+    RAILS_HIP_CHECK(e);
+    return RAILS_OK;
+}
+
+} // namespace
+
+// On a context that reduces, create is a collective call (one all-reduce).  Refusals that every rank reaches alike -- the method, the
+// context, a partition without a hook or communicator -- come before it; what only this rank can see (its block's shape, a zero in the
+// diagonal it was given) travels through it, so that every rank refuses and none is left waiting.
 extern "C" int rails_iter_create(rails_ctx *c, rails_csr *A, int method, const double *diag_host, rails_iter **out)
 {
     if (c) hipSetDevice(c->device);
     RAILS_REQUIRE(c && A && out, "rails_iter_create: null argument");
     RAILS_REQUIRE(method == RAILS_ITER_CG || method == RAILS_ITER_BICGSTAB, "rails_iter_create: method %d is neither RAILS_ITER_CG nor RAILS_ITER_BICGSTAB", method);
     RAILS_REQUIRE(c == A->ctx, "rails_iter_create: the operator belongs to another context");
-    RAILS_REQUIRE(c->nranks == 1 && !c->rccl, "rails_iter_create: single GPU only (the context has a partition or a communicator)");
-    RAILS_REQUIRE(!A->rect && A->kind != rails_csr::SPRHS && A->ncols_ext == A->m, "rails_iter_create: the operator is rectangular (%lld x %lld)", (long long)A->m,
-                  (long long)rails_csr_cols(A));
-    RAILS_REQUIRE(A->m >= 1, "rails_iter_create: an operator without rows");
+    RAILS_REQUIRE(c->nranks <= 1 || c->allreduce || c->rccl,
+                  "rails_iter_create: the context is row-partitioned but has neither an all-reduce hook nor a communicator: without one this object is single GPU only");
+    const bool reduces = c->nranks > 1 || c->allreduce || c->rccl; // rails_allreduce_dev's own condition
     const int64_t m = A->m;
+    // square: globally, for a stored row block whose halo plan is set (rails_csr_set_halo: m + n_ghost == ncols_ext)
+    const bool ghosted = reduces && A->kind == rails_csr::STORED && !A->rect && A->ncols_ext > m && A->n_ghost == A->ncols_ext - m;
+    char refusal[192] = "";
+    if (A->rect || A->kind == rails_csr::SPRHS || (A->ncols_ext != m && !ghosted))
+        snprintf(refusal, sizeof refusal, "rails_iter_create: the operator is rectangular (%lld x %lld)", (long long)m, (long long)rails_csr_cols(A));
+    else if (m < 1)
+        snprintf(refusal, sizeof refusal, "rails_iter_create: an operator without rows");
+    const bool host_csr = !refusal[0] && A->kind == rails_csr::STORED && (int64_t)A->h_rowptr.size() == m + 1 && (int64_t)A->h_val.size() == A->h_rowptr[m];
     std::vector<double> dinv;
-    if (diag_host) {
+    if (refusal[0]) {
+    } else if (diag_host) {
         dinv.assign(diag_host, diag_host + m);
-        for (int64_t i = 0; i < m; ++i)
-            RAILS_REQUIRE(dinv[i] != 0.0 && rails_iter_finite(dinv[i]), "rails_iter_create: diagonal entry %lld is %g", (long long)i, dinv[i]);
-    } else if (A->kind == rails_csr::STORED && (int64_t)A->h_rowptr.size() == m + 1 && (int64_t)A->h_val.size() == A->h_rowptr[m]) {
+        for (int64_t i = 0; i < m && !refusal[0]; ++i)
+            if (!(dinv[i] != 0.0 && rails_iter_finite(dinv[i]))) snprintf(refusal, sizeof refusal, "rails_iter_create: diagonal entry %lld is %g", (long long)i, dinv[i]);
+    } else if (host_csr) {
         // the CSR diagonal, when every entry of it is stored and nonzero; otherwise no preconditioner
         dinv.assign((size_t)m, 0.0);
         bool ok = true;
@@ -744,27 +857,56 @@ extern "C" int rails_iter_create(rails_ctx *c, rails_csr *A, int method, const d
         }
         if (!ok) dinv.clear();
     }
-    rails_iter *it = new rails_iter;
-    it->ctx = c;
-    it->A = A;
-    it->method = method;
-    it->m = m;
+    if (refusal[0] && !reduces) {
+        rails_set_error("%s", refusal);
+        return RAILS_EINVAL;
+    }
+    if (refusal[0]) dinv.clear();
     bool negative = !dinv.empty();
     for (double &v : dinv) {
         negative = negative && v < 0.0;
         v = 1.0 / v;
     }
-    it->defsign = negative ? -1.0 : 1.0;
-    if (A->kind == rails_csr::STORED && (int64_t)A->h_rowptr.size() == m + 1 && (int64_t)A->h_val.size() == A->h_rowptr[m]) {
-        // the polynomial preconditioner's upper bounds (two numbers; used only with "poly_degree" above 0)
-        it->hi_plain = rails_cheb_gershgorin(m, A->h_rowptr.data(), A->h_val.data(), nullptr);
-        if (!dinv.empty()) it->hi_jacobi = rails_cheb_gershgorin(m, A->h_rowptr.data(), A->h_val.data(), dinv.data());
+    double defsign = negative ? -1.0 : 1.0, hi_plain = 0.0, hi_jacobi = 0.0;
+    if (host_csr) {
+        // the polynomial preconditioner's upper bounds (two numbers; used only with "poly_degree" above 0).  A row block's rows hold their
+        // ghost columns' entries: the local row sums are complete
+        hi_plain = rails_cheb_gershgorin(m, A->h_rowptr.data(), A->h_val.data(), nullptr);
+        if (!dinv.empty()) hi_jacobi = rails_cheb_gershgorin(m, A->h_rowptr.data(), A->h_val.data(), dinv.data());
     }
+    if (reduces) {
+        double mine[RAILS_AGREE_SLOT];
+        rails_iter_agree_fill(mine, refusal[0] ? RAILS_AGREE_REFUSED : dinv.empty() ? RAILS_AGREE_NO_DIAG : RAILS_AGREE_DIAG, negative, hi_plain, hi_jacobi);
+        std::vector<double> all;
+        RAILS_TRY(gather_slots(c, mine, all));
+        const rails_iter_agreed ag = rails_iter_agree(all.data(), std::max(1, c->nranks));
+        if (ag.refused) {
+            rails_set_error("%s", refusal[0] ? refusal : "rails_iter_create: another rank refused its arguments");
+            return RAILS_EINVAL;
+        }
+        if (!ag.jacobi) dinv.clear();
+        defsign = ag.defsign;
+        hi_plain = ag.hi_plain;
+        hi_jacobi = ag.hi_jacobi;
+    }
+    rails_iter *it = new rails_iter;
+    it->ctx = c;
+    it->A = A;
+    it->method = method;
+    it->m = m;
+    it->reduces = reduces;
+    it->defsign = defsign;
+    it->hi_plain = hi_plain;
+    it->hi_jacobi = hi_jacobi;
     hipError_t e = hipMalloc((void **)&it->status_dev, 16 * sizeof(int32_t));
     if (e == hipSuccess) e = hipMemset(it->status_dev, 0, 16 * sizeof(int32_t));
     if (e == hipSuccess && !dinv.empty()) {
         e = hipMalloc((void **)&it->dinv, (size_t)m * sizeof(double));
         if (e == hipSuccess) e = hipMemcpy(it->dinv, dinv.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess && reduces) {
+        e = hipMalloc((void **)&it->sums_dev, 64 * sizeof(double));
+        if (e == hipSuccess) e = hipMemset(it->sums_dev, 0, 64 * sizeof(double));
     }
     if (e != hipSuccess) {
         rails_set_error("rails_iter_create: device allocation or upload failed: %s", hipGetErrorString(e));
@@ -820,12 +962,17 @@ extern "C" int rails_iter_solve(rails_ctx *c, rails_iter *it, int trans, const r
     rails_slow_guard slow__(c, "rails_iter_solve", nc, it ? it->m : 0);
     RAILS_REQUIRE(c && it && X && Y, "rails_iter_solve: null argument");
     RAILS_REQUIRE(c == it->ctx, "rails_iter_solve: the object belongs to another context");
-    RAILS_REQUIRE(c->nranks == 1 && !c->rccl, "rails_iter_solve: single GPU only (the context has a partition or a communicator)");
+    // Collective on a context that reduces.  The rule that keeps the ranks from deadlocking: every decision that changes how many
+    // collectives are issued -- a refusal, the group loop, the number of iterations queued, the early exit, the non-finite right-hand side's
+    // RAILS_EINVAL -- is a function of the arguments and settings every rank passes alike (nc, trans, max_iterations, check_every) and of
+    // all-reduced data (the columns' scalars and the counts in `status`, the same bits on every rank), never of this rank's rows.
+    RAILS_REQUIRE(!trans || (it->A->n_ghost == 0 && it->A->n_send == 0 && it->A->ncols_ext == it->A->m),
+                  "rails_iter_solve: the transposed solve of a row-partitioned operator (ghost rows) is not available: rails_spmm's transposed product is single GPU");
     RAILS_REQUIRE(X->m == it->m && Y->m == it->m, "rails_iter_solve: the operator has %lld rows, X %lld, Y %lld", (long long)it->m, (long long)X->m,
                   (long long)Y->m);
     RAILS_REQUIRE(xc0 >= 0 && nc >= 0 && xc0 + nc <= X->cap && yc0 >= 0 && yc0 + nc <= Y->cap, "rails_iter_solve: column windows outside the panels");
     if (X->d == Y->d) RAILS_REQUIRE(xc0 + nc <= yc0 || yc0 + nc <= xc0, "rails_iter_solve: X and Y windows alias");
-    it->last_dots = it->last_launches = it->last_products = it->last_poly = it->last_fused = 0;
+    it->last_dots = it->last_launches = it->last_products = it->last_poly = it->last_fused = it->last_allreduces = it->last_halo = 0;
     it->last.clear();
     if (nc == 0) return RAILS_OK;
     RAILS_TRY(grow_work(c, it, std::min(nc, RAILS_ITER_GROUP)));
@@ -885,12 +1032,11 @@ extern "C" int rails_iter_precondition(rails_ctx *c, rails_iter *it, const rails
     if (c) hipSetDevice(c->device);
     RAILS_REQUIRE(c && it && X && Y, "rails_iter_precondition: null argument");
     RAILS_REQUIRE(c == it->ctx, "rails_iter_precondition: the object belongs to another context");
-    RAILS_REQUIRE(c->nranks == 1 && !c->rccl, "rails_iter_precondition: single GPU only (the context has a partition or a communicator)");
     RAILS_REQUIRE(X->m == it->m && Y->m == it->m, "rails_iter_precondition: the operator has %lld rows, X %lld, Y %lld", (long long)it->m, (long long)X->m,
                   (long long)Y->m);
     RAILS_REQUIRE(xc0 >= 0 && nc >= 0 && xc0 + nc <= X->cap && yc0 >= 0 && yc0 + nc <= Y->cap, "rails_iter_precondition: column windows outside the panels");
     if (X->d == Y->d) RAILS_REQUIRE(xc0 + nc <= yc0 || yc0 + nc <= xc0, "rails_iter_precondition: X and Y windows alias");
-    it->last_dots = it->last_launches = it->last_products = it->last_poly = it->last_fused = 0; // the counters count this call
+    it->last_dots = it->last_launches = it->last_products = it->last_poly = it->last_fused = it->last_allreduces = it->last_halo = 0; // the counters count this call
     if (nc == 0) return RAILS_OK;
     unsigned want = 1u << W_R | 1u << W_Z | 1u << W_D;
     if (it->poly_degree > 0) want |= 1u << W_Z2 | 1u << W_Q;
@@ -919,7 +1065,10 @@ extern "C" int rails_iter_precondition(rails_ctx *c, rails_iter *it, const rails
 // broke down, [5] worst relative residual of the recurrence, [6] work-panel columns, [7] products with A in the last solve; totals since
 // creation: [8] solves, [9] columns, [10] iterations summed over the columns, [11] flagged columns, [12] products with A; the polynomial
 // preconditioner: [13] its applications in the last solve, [14] launches of the fused step kernel in it, [15] hi and [16] lo of the
-// interval in use (0 with degree 0).  [7] counts every product, those inside the fused step included.
+// interval in use (0 with degree 0); a context that reduces: [17] all-reduces issued in the last call (per group of columns CG 1 at the start
+// and 2 per queued iteration, BiCGStab 1 and 3; the polynomial adds none), [18] ghost-row exchanges the object issued itself (one before
+// every fused step in its ghost-row form; those inside rails_spmm are not counted).  [7] counts every product, those inside the fused step
+// included.
 extern "C" int rails_iter_stats(const rails_iter *it, double *info, int cap)
 {
     RAILS_REQUIRE(it && info && cap >= 0, "rails_iter_stats: bad argument");
@@ -932,10 +1081,10 @@ extern "C" int rails_iter_stats(const rails_iter *it, double *info, int cap)
         if (!(rel <= worst)) worst = rel; // a NaN shows
     }
     const double hi = it->poly_degree > 0 ? poly_hi(it) : 0.0;
-    const double v[17] = {most, (double)it->last_dots, (double)it->last_launches, unconv, broke, worst, (double)it->work_cols, (double)it->last_products,
+    const double v[19] = {most, (double)it->last_dots, (double)it->last_launches, unconv, broke, worst, (double)it->work_cols, (double)it->last_products,
                           it->tot_solves, it->tot_columns, it->tot_iterations, it->tot_flagged, it->tot_products,
-                          (double)it->last_poly, (double)it->last_fused, hi, hi / it->poly_ratio};
-    const int k = std::min(cap, 17);
+                          (double)it->last_poly, (double)it->last_fused, hi, hi / it->poly_ratio, (double)it->last_allreduces, (double)it->last_halo};
+    const int k = std::min(cap, 19);
     for (int i = 0; i < k; ++i) info[i] = v[i];
     return k;
 }
@@ -959,7 +1108,6 @@ extern "C" int rails_csr_create_iter(rails_ctx *c, rails_iter *it, rails_csr **o
 {
     RAILS_REQUIRE(c && it && out, "rails_csr_create_iter: null argument");
     RAILS_REQUIRE(c == it->ctx, "rails_csr_create_iter: the object belongs to another context");
-    RAILS_REQUIRE(c->nranks == 1 && !c->rccl, "rails_csr_create_iter: single GPU only (the context has a partition or a communicator)");
     rails_csr *A = new rails_csr();
     A->ctx = c;
     A->m = it->m;

@@ -270,6 +270,9 @@ void rails_rccl_release(rails_ctx *c);
 // spmm.hip: the facts op_choice.h decides on, for a product of nc columns between windows of that alignment
 struct OpFacts;
 OpFacts rails_op_facts(const rails_ctx *c, const rails_csr *A, int nc, bool x_vec2, bool y_vec2);
+// spmm.hip: rails_spmm's ghost-row exchange on its own -- pack nc columns of the rows the neighbours need from Xp (row stride ldx), exchange;
+// afterwards, in stream order, A->ext holds the ghost rows with row stride nc.  Grows the operator's two buffers as rails_spmm does.
+int rails_halo_exchange(rails_ctx *c, rails_csr *A, const double *Xp, int ldx, int nc);
 // spmm_sweep.hip: the sweep kernel for banded patterns; *done tells whether it computed the product
 int rails_spmm_sweep(rails_ctx *c, rails_csr *A, const double *X, int ldx, const double *Xg, int ldg, double *Y, int ldy, int nc, bool aligned,
                      bool force, bool *done);

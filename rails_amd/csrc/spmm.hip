@@ -890,6 +890,17 @@ int local_product(rails_ctx *c, rails_csr *A, const OpOrder &order, const Produc
 
 } // namespace
 
+// The exchange of rails_spmm on its own (itsolve.hip's fused polynomial step gathers from the ghost buffer itself): grows the two buffers
+// as rails_spmm does, packs nc columns from Xp and exchanges; afterwards (in stream order) A->ext holds the ghost rows with row stride nc.
+// The caller decides whether to exchange by rails_spmm's condition (n_ghost > 0 || n_send > 0); a rank that only sends or only receives
+// takes part with an empty buffer on the other side.
+int rails_halo_exchange(rails_ctx *c, rails_csr *A, const double *Xp, int ldx, int nc)
+{
+    RAILS_TRY(grow_buffer(c, &A->send_buf, &A->send_cap, (size_t)(A->n_send ? A->n_send : 1) * nc * sizeof(double)));
+    RAILS_TRY(grow_buffer(c, &A->ext, &A->ext_cap, (size_t)(A->n_ghost ? A->n_ghost : 1) * nc * sizeof(double)));
+    return exchange_halo(c, A, Xp, ldx, nc);
+}
+
 extern "C" int rails_spmm(rails_ctx *c, rails_csr *A, int trans, const rails_panel *X, int xc0, int nc, rails_panel *Y, int yc0)
 {
     if (c) hipSetDevice(c->device); // allocations and launches go to the context's device whatever the caller's current device is

@@ -27,7 +27,12 @@ class IterativeInverse:
     (HipOperatorWrapper) whose products are the solves: it goes wherever an operator goes (Solver.set_inverse, rails_spmm).
     poly_degree K > 0 (conjugate gradients only): precondition with the Chebyshev polynomial z = p_K(G A) G r, K products per application
     and no inner product between them, fitted to [hi / poly_ratio, hi]; hi is eig_max, or (None) a Gershgorin bound from the CSR arrays --
-    an operator that is not a CSR matrix needs eig_max.  poly_ratio None: the library's default."""
+    an operator that is not a CSR matrix needs eig_max.  poly_ratio None: the library's default.
+
+    On a row-partitioned context (Context.set_partition with more than one rank) A is the rank's operator wrapper with its halo plan set,
+    the all-reduce hook or the communicator is installed before the object is made, and making it, set(), solve() and precondition() are
+    collective calls: every rank makes them in the same order with the same widths and settings.  The matrix forms are refused there
+    (ValueError), and so is trans=True (the transposed product of a row block is single GPU)."""
 
     def __init__(self, ctx, A, method="auto", tol=1e-10, maxit=1000, jacobi=True, strict=False, diag=None, check_every=None, poly_degree=0,
                  poly_ratio=None, eig_max=None):
@@ -40,6 +45,9 @@ class IterativeInverse:
                 raise ValueError("IterativeInverse: pass the operator itself and solve with trans=True")
             self.A = A
         else:
+            if getattr(ctx, "nranks", 1) > 1:
+                raise ValueError("IterativeInverse: the context is row-partitioned (%d ranks): pass the rank's operator wrapper, the one with its halo "
+                                 "plan (HipOperatorWrapper.set_halo), and name the method" % ctx.nranks)
             import scipy.sparse as sp
 
             if isinstance(A, tuple):
@@ -112,11 +120,11 @@ class IterativeInverse:
 
     def stats(self):
         """the last solve and the totals since creation (rails_iter_stats)"""
-        info = (C.c_double * 17)()
-        k = self.ctx.lib.rails_iter_stats(self.h, info, 17)
+        info = (C.c_double * 19)()
+        k = self.ctx.lib.rails_iter_stats(self.h, info, 19)
         names = ("max_iterations_of_a_column", "inner_products", "launches", "unconverged_columns", "breakdown_columns", "worst_relative_residual",
                  "workspace_columns", "products", "total_solves", "total_columns", "total_iterations", "total_flagged_columns", "total_products",
-                 "poly_applications", "fused_launches", "eig_hi", "eig_lo")
+                 "poly_applications", "fused_launches", "eig_hi", "eig_lo", "allreduces", "halo_exchanges")
         out = {names[i]: info[i] for i in range(max(k, 0))}
         return {n: (v if n in ("worst_relative_residual", "eig_hi", "eig_lo") else int(v)) for n, v in out.items()}
 

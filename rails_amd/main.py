@@ -3,7 +3,8 @@
     python -m rails_amd.main [params.xml] [--dir DIR] [--A A.mtx] [--B B.mtx] [--M M.mtx] [--V V.mtx] [--T T.mtx]
                                [--eigs K] [--variance FILE] [--sparse-B] [--warm-start V.mtx | --start-space S.mtx] [--restart-upon-start]
                                [--inverse {lu,cg,bicgstab,iterative}] [--inverse-tol T] [--inverse-poly K]
-    python -m torch.distributed.run --nproc-per-node N -m rails_amd.main ...      (one rank per GPU, rows partitioned)
+    python -m torch.distributed.run --nproc-per-node N -m rails_amd.main ... [--backend {nccl,gloo}] [--one-device]
+                                                                                  (one rank per GPU, rows partitioned)
 
 File names, formats and the parameter file follow the reference's driver (src/main.cpp:57-68,111,123-126): `A.mtx`, `B.mtx`
 and `M.mtx` in, `V.mtx` and `T.mtx` out, solver parameters from the "Lyapunov Solver" sublist of a Teuchos XML file.  A diagonal
@@ -21,7 +22,13 @@ factorised on the host and applied on the device, `cg` / `bicgstab` an iteration
 (rails_amd.IterativeInverse; the reference allows an approximate inverse), `iterative` conjugate gradients when A equals its transpose and
 BiCGStab otherwise.  `--inverse-poly K` preconditions the conjugate gradients with a Chebyshev polynomial of degree K (K products in a
 row without an inner product between them; 0, the default, is off); with an inverse that resolves to BiCGStab the driver refuses it.  A
-Schur-complement problem keeps the inverse of its Schur operator.
+Schur-complement problem keeps the inverse of its Schur operator.  On more than one rank the sparse LU is not available (a factorisation
+does not partition by rows): name one of the iterative inverses there.  Each rank then builds its inverse from its own row block, the
+inner products of the iteration are all-reduced, and `iterative` decides symmetry on the whole matrix, which every rank has read.  No run
+on more than one GPU has been made yet; what an inner iteration costs on a real partition is unmeasured.
+
+`--backend gloo` runs the collectives through torch.distributed's gloo backend, staged through host memory, and `--one-device` puts every
+rank on device 0: a rehearsal of the multi-process path on a machine with one GPU, as bench.py has it.
 
 `--eigs K` and `--variance FILE` are the second half of the reference's driver (src/main.cpp:140-170) on the solution object
 (rails_amd.Solution): the K eigenvalues of largest modulus of the covariance X, each next to its share of the trace, written to
@@ -70,6 +77,9 @@ def main(argv=None):
     ap.add_argument("--inverse-tol", type=float, default=1e-10, metavar="T", help="relative tolerance of an iterative inverse (per column)")
     ap.add_argument("--inverse-poly", type=int, default=0, metavar="K", help="degree of the Chebyshev polynomial preconditioner of a conjugate-gradients inverse "
                                                                             "(K products per application; 0: off)")
+    ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend of a run on several ranks; gloo = rehearsal of the "
+                                                                                "multi-process path (collectives staged through host memory)")
+    ap.add_argument("--one-device", action="store_true", help="every rank uses device 0 (rehearsal on a machine with one GPU)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args(argv)
@@ -81,14 +91,18 @@ def main(argv=None):
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    local_rank = 0 if args.one_device else int(os.environ.get("LOCAL_RANK", "0"))
+    staged = args.backend != "nccl"  # device buffers travel through host tensors
     dist = None
     torch.cuda.set_device(local_rank)
     if world > 1:
         import torch.distributed as dist
 
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        dist.init_process_group(backend="nccl", device_id=torch.device("cuda", local_rank))
+        if args.backend == "nccl":
+            dist.init_process_group(backend="nccl", device_id=torch.device("cuda", local_rank))
+        else:
+            dist.init_process_group(backend="gloo")
 
     def path(name):
         return name if os.path.isabs(name) else os.path.join(args.dir, name)
@@ -149,7 +163,7 @@ def main(argv=None):
         p0, p1 = rp[r0], rp[r1]
         plan = partition.HaloPlan(starts, rank, cg[p0:p1], partition.all_gather_object_fn())
         op = rails_amd.HipOperatorWrapper(ctx, (rp[r0:r1 + 1] - p0).astype(np.int64), plan.col_local, vv[p0:p1], ncols_ext=plan.m_local + plan.n_ghost)
-        op.set_halo(plan, partition.make_halo(plan, on_device=True))
+        op.set_halo(plan, partition.make_halo(plan, on_device=True, host_staged=staged))
         return op
 
     schur = None
@@ -193,7 +207,7 @@ def main(argv=None):
     A = schur.op if schur is not None else operator((rowptr, col, val))
     Mop = operator(Mcsr) if Mcsr else None
     if world > 1:
-        ctx.set_allreduce(partition.make_allreduce(on_device=True))
+        ctx.set_allreduce(partition.make_allreduce(on_device=True, host_staged=staged))
     solver = rails_amd.Solver(ctx, A, B if args.sparse_B else B[r0:r1], M=Mop, m_global=m)
     code = solver.set_parameters(params)
     if code != 0:
@@ -211,8 +225,9 @@ def main(argv=None):
     method = next((float(v) for k, v in params.items() if k.lower() == "projection method"), 1.0)
     inverse = None
     if method > 1:
-        if world > 1:
-            raise SystemExit("'Projection method' %g: the %s inverse runs on one rank" % (method, "sparse LU" if args.inverse == "lu" else "iterative"))
+        if world > 1 and args.inverse == "lu":
+            raise SystemExit("'Projection method' %g on %d ranks: the sparse LU inverse runs on one rank; use --inverse iterative (or cg, bicgstab), "
+                             "the inverse that partitions by rows" % (method, world))
         t0 = time.time()
         if schur is not None:
             inverse = schur.inverse()
@@ -220,14 +235,24 @@ def main(argv=None):
         elif args.inverse == "lu":
             inverse = rails_amd.SparseLU(ctx, (rowptr, col.astype(np.int32), val))
             what = "a sparse LU of A"
+        elif world > 1:
+            # the rank's own row block with its halo plan; the all-reduce hook is in place (above).  Symmetry is a property of the whole
+            # matrix, which every rank has read: every rank reaches the same method
+            how = args.inverse
+            if how == "iterative":
+                import scipy.sparse as sp
+
+                Afull = sp.csr_matrix((val, col, rowptr), shape=(m, m))
+                how = "cg" if (Afull != Afull.T).nnz == 0 else "bicgstab"
+            inverse = rails_amd.IterativeInverse(ctx, A, method=how, tol=args.inverse_tol)
         else:
             inverse = rails_amd.IterativeInverse(ctx, (rowptr, col.astype(np.int32), val), method="auto" if args.inverse == "iterative" else args.inverse,
                                                  tol=args.inverse_tol)
-            if args.inverse_poly and inverse.method != "cg":
+        if isinstance(inverse, rails_amd.IterativeInverse) and args.inverse_poly:  # on one rank or on several: the method is the same on every rank
+            if inverse.method != "cg":
                 raise SystemExit("--inverse-poly %d: the polynomial preconditioner is for conjugate gradients, and the inverse chosen is %s" % (
                     args.inverse_poly, inverse.method))
-            if args.inverse_poly:
-                inverse.set("poly_degree", args.inverse_poly)
+            inverse.set("poly_degree", args.inverse_poly)
         solver.set_inverse(inverse)
         if isinstance(inverse, rails_amd.IterativeInverse):
             _log(rank, "Projection method %g: A^-1 is an iterative solve on the device, method %s, Jacobi, tolerance %g" % (method, inverse.method, args.inverse_tol))
@@ -254,6 +279,9 @@ def main(argv=None):
         st = inverse.stats()
         _log(rank, "iterative inverse (%s): %d solves of %d columns, %d inner iterations in all, %d flagged columns" % (
             inverse.method, st["total_solves"], st["total_columns"], st["total_iterations"], st["total_flagged_columns"]))
+        if args.inverse_poly:  # what the object itself counted in its last solve, not what was asked for
+            _log(rank, "its last solve: %d applications of the polynomial, %d products with A, %d of them in fused steps" % (
+                st["poly_applications"], st["products"], st["fused_launches"]))
     if Nsp is not None:
         _log(rank, "nullspace: %d of %d columns kept" % (solver.nullspace_rank, Nsp.shape[1]))
     if S0 is not None:

@@ -40,6 +40,7 @@ class Context:
         check(self.lib.rails_ctx_create(device, C.c_void_p(stream) if stream else None, C.byref(h)), "rails_ctx_create")
         self.h = h
         self._cb = None
+        self.nranks = 1  # ranks of the row partition (set_partition)
         self._solvers = weakref.WeakSet()  # closed before the context (their C++ side owns panels of this context)
         self.set_seed(seed, first_stream)
 
@@ -48,6 +49,7 @@ class Context:
 
     def set_partition(self, rank, nranks, row0, m_global):
         check(self.lib.rails_ctx_set_partition(self.h, rank, nranks, row0, m_global), "rails_ctx_set_partition")
+        self.nranks = int(nranks)
 
     def set_allreduce(self, pyfunc):
         """pyfunc(dev_ptr:int, n:int, stream:int) -> 0 on success."""
