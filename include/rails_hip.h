@@ -64,6 +64,8 @@ int rails_ctx_create(int device, void *stream, rails_ctx **out);
 int rails_ctx_destroy(rails_ctx *ctx);
 int rails_ctx_sync(rails_ctx *ctx);
 void *rails_ctx_stream(rails_ctx *ctx);
+/* compute units of the context's device (the one-pass update + second projection launches min(row tiles, 2 x this) workgroups); 0 for NULL */
+int rails_ctx_num_cu(const rails_ctx *ctx);
 /* call counters of this context as a JSON object (block vs column-wise orthogonalisations, SpMM kernel choice, ...) */
 int rails_ctx_stats(rails_ctx *ctx, char *buf, int cap);
 /* Busy meter: with on != 0 every kernel launch of this context is bracketed by a pair of events, read at the next synchronisation of
@@ -420,6 +422,17 @@ int rails_dense_tile_fit(void);
 /* Template parameter of the context's last launch of k_update_gram<NBW, .>, of the wide-X Gram form k_gram_cols[2]<TI, ., .> and of
  * k_panel_gemm_wide<TR> (its last slice); 0 where there has been none.  Any of the three pointers may be NULL.  Read-only. */
 int rails_dense_last_tiles(const rails_ctx *ctx, int *update_gram_nbw, int *gram_cols_ti, int *gemm_wide_tr);
+
+/* The schedule of the one-pass form of rails_update_gram_deferred[_out]: the pipelined kernel (C in registers, one register set of X
+ * refilled block by block, one conflict-free turn-around per tile) or the kernel as it was.  Both form the same
+ * partial sums and add them in the same order: results are the same bits either way, and which shapes take the one-pass form does
+ * not depend on it.  On by default; RAILS_UPDATE_GRAM_PIPELINE=0 in the environment (read at the first use) or this process-wide
+ * setter (on = 0; it wins over the variable) restores the earlier kernel. */
+void rails_dense_set_update_gram_pipeline(int on);
+int rails_dense_update_gram_pipeline(void);
+/* *form = which kernel the context's last one-pass update + second projection launched: 1 the earlier kernel, 2 the pipelined one;
+ * 0 where there has been none.  Read-only. */
+int rails_dense_last_update_gram_form(const rails_ctx *ctx, int *form);
 
 /* Orthonormalise columns [k_old, k_old+w) of V against columns [0, k_old) and among themselves,
  * equivalent to the reference's column-wise CGS2 with pre/post normalisation

@@ -28,6 +28,7 @@ SIGNATURES = {
     "rails_ctx_destroy": (C.c_int, [_vp]),
     "rails_ctx_sync": (C.c_int, [_vp]),
     "rails_ctx_stream": (_vp, [_vp]),
+    "rails_ctx_num_cu": (C.c_int, [_vp]),
     "rails_ctx_set_meter": (C.c_int, [_vp, C.c_int]),
     "rails_ctx_enable_library_gemm": (C.c_int, [_vp]),
     "rails_ctx_library_gemm_ready": (C.c_int, [_vp]),
@@ -119,6 +120,9 @@ SIGNATURES = {
     "rails_dense_set_tile_fit": (None, [C.c_int]),
     "rails_dense_tile_fit": (C.c_int, []),
     "rails_dense_last_tiles": (C.c_int, [_vp, _ip, _ip, _ip]),
+    "rails_dense_set_update_gram_pipeline": (None, [C.c_int]),
+    "rails_dense_update_gram_pipeline": (C.c_int, []),
+    "rails_dense_last_update_gram_form": (C.c_int, [_vp, _ip]),
     "rails_orthogonalize": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _ip]),
     "rails_orthogonalize_deflated": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _ip]),
     "rails_panel_colnorms2": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _dp]),

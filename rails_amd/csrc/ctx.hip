@@ -121,6 +121,8 @@ extern "C" int rails_ctx_stats(rails_ctx *c, char *buf, int cap)
 
 extern "C" void *rails_ctx_stream(rails_ctx *c) { return c ? (void *)c->stream : nullptr; }
 
+extern "C" int rails_ctx_num_cu(const rails_ctx *c) { return c ? c->num_cu : 0; }
+
 extern "C" int rails_ctx_set_meter(rails_ctx *c, int on)
 {
     RAILS_REQUIRE(c, "rails_ctx_set_meter: null context");

@@ -51,6 +51,23 @@ bool dense_tile_fit()
     return v != 0;
 }
 
+// The schedule of the fused update + second projection: k_update_gram_p, or k_update_gram as it was.  Process-wide
+// like the tile fit: rails_dense_set_update_gram_pipeline, or RAILS_UPDATE_GRAM_PIPELINE=0 in the environment (read at the first use,
+// unless the setter came first).  The same bits either way.
+std::atomic<int> g_update_gram_pipeline{-1}; // -1: not decided yet
+
+bool dense_update_gram_pipeline()
+{
+    int v = g_update_gram_pipeline.load(std::memory_order_relaxed);
+    if (v < 0) {
+        const char *e = getenv("RAILS_UPDATE_GRAM_PIPELINE");
+        int undecided = -1;
+        g_update_gram_pipeline.compare_exchange_strong(undecided, (e ? atoi(e) : 1) ? 1 : 0); // (a setter that got in between wins)
+        v = g_update_gram_pipeline.load(std::memory_order_relaxed);
+    }
+    return v != 0;
+}
+
 __device__ __forceinline__ v4f64 mfma_f64(double a, double b, v4f64 c)
 {
     return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
@@ -415,6 +432,17 @@ extern "C" int rails_dense_last_tiles(const rails_ctx *c, int *update_gram_nbw, 
     if (update_gram_nbw) *update_gram_nbw = c->last_update_gram_nbw;
     if (gram_cols_ti) *gram_cols_ti = c->last_gram_cols_ti;
     if (gemm_wide_tr) *gemm_wide_tr = c->last_gemm_wide_tr;
+    return RAILS_OK;
+}
+
+extern "C" void rails_dense_set_update_gram_pipeline(int on) { g_update_gram_pipeline.store(on ? 1 : 0); }
+
+extern "C" int rails_dense_update_gram_pipeline(void) { return dense_update_gram_pipeline() ? 1 : 0; }
+
+extern "C" int rails_dense_last_update_gram_form(const rails_ctx *c, int *form)
+{
+    RAILS_REQUIRE(c && form, "rails_dense_last_update_gram_form: null argument");
+    *form = c->last_update_gram_form;
     return RAILS_OK;
 }
 
@@ -893,14 +921,188 @@ __global__ __launch_bounds__(256, (NBW <= 6 ? 2 : 1)) void k_update_gram(double 
         }
 }
 
+// The same pass on another schedule: the same partial sums, formed and added in the same order, so the same bits
+// as k_update_gram; what differs is where the operands wait.
+//   C in registers.  A lane multiplies every tile by the same 4 NBW entries of C (rows (4b + wave) 16 + 4 kk + s of column li), so it
+//     loads them once: step 1 is 4 NBW MFMAs back to back with no LDS read and no wait between them, and the 40 to 80 KiB copy of C
+//     leaves the LDS.  Column 16 (the 17th column's multiply-adds) stays in the LDS, 64 NBW doubles read 32 bytes at a time: its values
+//     feed the vector unit, not the MFMA chain, and with them in registers <6, 1> does not fit 256 registers.
+//   One set of X registers, refilled block by block.  As soon as step 1 has used a block of this tile, the same block of the next tile
+//     is asked for into the same registers: every load has a whole tile's time to arrive, the loads are spread over the tile, and the
+//     48 registers of the second set are free (two sets and C in registers spill from <5, 1> on, and a spill reload in the loop made
+//     the compiler wait for every load in flight).
+//   One turn-around per tile.  A block goes into the LDS for step 2 right before step 1 multiplies it (NBW slabs of 2 KiB per wave), so
+//     the stores run under step 1's MFMAs and step 2 reads the slabs back without a store -> load round trip per block, a block's
+//     four values asked for before the MFMAs of the block before.  Rows keep their stride of 128 bytes, and the 16-byte chunks of a
+//     row are exchanged by (chunk ^ (row & 7)): the eight lanes of a 16-byte store's lane group hit eight different chunks (they all
+//     hit the same one before: 8-way), and the 32 lanes of an 8-byte load's group still read two whole rows, one per half of the banks.
+// The clamping of rows and columns, the cross-wave sums and the stores are those of k_update_gram, text for text.
+template <int NBW, int NE>
+__global__ __launch_bounds__(256, (NBW <= 6 ? 2 : 1)) void k_update_gram_p(double alpha, const double *__restrict__ X, int ldx, int k, const double *__restrict__ C, int r,
+                                                       const double *Yp, int ldy, double *Yo, int ldo, int r2, int64_t m, int64_t ntiles,
+                                                       double *__restrict__ partial)
+{
+    __shared__ double red[4][4][64]; // step-1 partial tiles: [wave][result register][lane]
+    __shared__ double rede[4][1][16];
+    __shared__ double awL[16 * 16];  // the updated tile, [row][column], zero beyond r2 columns / m rows
+    __shared__ __attribute__((aligned(16))) double T[4][NBW][16 * 16];
+    __shared__ __attribute__((aligned(16))) double c16[NE > 0 ? 64 * NBW : 2]; // column 16 of C, zero beyond k rows (the registers hold no more)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int li = lane & 15, kk = lane >> 4;
+    // this lane's entries of C, zero beyond k rows / r columns
+    double cr[NBW][4];
+#pragma unroll
+    for (int b = 0; b < NBW; ++b)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int kl = (b * 4 + wave) * 16 + 4 * kk + s;
+            cr[b][s] = (kl < k && li < r) ? C[kl + (int64_t)li * k] : 0.0;
+        }
+    if (NE > 0) {
+        for (int kl = threadIdx.x; kl < 64 * NBW; kl += 256) c16[kl] = (kl < k && 16 < r) ? C[kl + (int64_t)16 * k] : 0.0;
+        __syncthreads();
+    }
+    v4f64 acc2[NBW];
+#pragma unroll
+    for (int b = 0; b < NBW; ++b) acc2[b] = (v4f64){0.0, 0.0, 0.0, 0.0};
+
+    // One set of X registers: a block's part of the NEXT tile is asked for as soon as step 1 has used that block of this tile (its copy
+    // for step 2 is in the LDS by then), so every load has a whole tile's time to arrive, the loads of a tile are spread over step 1
+    // and not sent in one burst, and a wait for block b waits for nothing behind it.  Addresses are clamped as in k_update_gram: no
+    // branches and no selects on what comes back, zeros of C and of the Y' tile meet whatever lies outside the operands.
+    const int k4 = (k + 3) & ~3;
+    auto xrow_of = [&](int64_t tile) {
+        const int64_t myrow = (tile < ntiles ? tile : ntiles - 1) * 16 + li;
+        return X + (myrow < m ? myrow : m - 1) * ldx;
+    };
+    auto fetch_block = [&](const double *xrow, int b, double *xs) {
+        const int kcol = (b * 4 + wave) * 16 + 4 * kk;
+        const double *src = xrow + (kcol < k4 ? kcol : 0);
+        const v2f64 t0 = *reinterpret_cast<const v2f64 *>(src);
+        const v2f64 t1 = *reinterpret_cast<const v2f64 *>(src + 2);
+        xs[0] = t0.x;
+        xs[1] = t0.y;
+        xs[2] = t1.x;
+        xs[3] = t1.y;
+    };
+    const int erow = threadIdx.x & 15, ene = threadIdx.x >> 4;
+    auto fetch_y = [&](int64_t tile, double &yv, double &ye) {
+        const int64_t t16 = (tile < ntiles ? tile : ntiles - 1) * 16;
+        const int64_t yrow = t16 + kk + 4 * wave, er = t16 + erow;
+        yv = Yp[(yrow < m ? yrow : m - 1) * ldy + (li < r ? li : 0)]; // (used only where it is valid)
+        ye = NE > 0 ? Yp[(er < m ? er : m - 1) * ldy + (16 + ene < r ? 16 + ene : 0)] : 0.0;
+    };
+    // the turn-around's places (doubles within a slab of 16 x 16): this lane's two 16-byte chunks of row li on the way in, its entry
+    // (row 4 q + kk, column li) on the way out (rows 4 q + kk and 4 (q + 2) + kk have the same three low bits: two places and a constant)
+    const int tw0 = li * 16 + 2 * ((2 * kk) ^ (li & 7)), tw1 = li * 16 + 2 * ((2 * kk + 1) ^ (li & 7));
+    const int tr0 = kk * 16 + 2 * ((li >> 1) ^ kk) + (li & 1), tr1 = (4 + kk) * 16 + 2 * ((li >> 1) ^ (4 + kk)) + (li & 1);
+    double xs[NBW][4], yv, ye;
+    {
+        const double *xrow = xrow_of(blockIdx.x);
+#pragma unroll
+        for (int b = 0; b < NBW; ++b) fetch_block(xrow, b, xs[b]);
+        fetch_y(blockIdx.x, yv, ye);
+    }
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int64_t row0 = tile * 16;
+        const double *xnext = xrow_of(tile + gridDim.x); // (past the last tile: the last tile again, and nobody uses it)
+        const int64_t yrow = row0 + kk + 4 * wave;
+        const bool yok = yrow < m && li < r;
+        const bool eok = ene < NE && 16 + ene < r && row0 + erow < m;
+        // step 1
+        v4f64 p = (v4f64){0.0, 0.0, 0.0, 0.0};
+        double e[NE > 0 ? NE : 1];
+#pragma unroll
+        for (int q = 0; q < NE; ++q) e[q] = 0.0;
+#pragma unroll
+        for (int b = 0; b < NBW; ++b) {
+            *reinterpret_cast<v2f64 *>(&T[wave][b][tw0]) = (v2f64){xs[b][0], xs[b][1]};
+            *reinterpret_cast<v2f64 *>(&T[wave][b][tw1]) = (v2f64){xs[b][2], xs[b][3]};
+            double ce[4] = {0.0, 0.0, 0.0, 0.0};
+            if (NE > 0) {
+                const v2f64 c0 = *reinterpret_cast<const v2f64 *>(&c16[(b * 4 + wave) * 16 + 4 * kk]);
+                const v2f64 c1 = *reinterpret_cast<const v2f64 *>(&c16[(b * 4 + wave) * 16 + 4 * kk + 2]);
+                ce[0] = c0.x, ce[1] = c0.y, ce[2] = c1.x, ce[3] = c1.y;
+            }
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                p = mfma_f64(xs[b][s], cr[b][s], p);
+#pragma unroll
+                for (int q = 0; q < NE; ++q) e[q] += xs[b][s] * ce[s];
+            }
+            __builtin_amdgcn_sched_barrier(0); // (the load below stays below: above, it needs a second set of registers)
+            fetch_block(xnext, b, xs[b]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int v = 0; v < 4; ++v) red[wave][v][lane] = p[v];
+#pragma unroll
+        for (int q = 0; q < NE; ++q) {
+            double t = e[q];
+            t += __shfl_xor(t, 16, 64);
+            t += __shfl_xor(t, 32, 64);
+            if (kk == 0) rede[wave][q][li] = t;
+        }
+        __syncthreads();
+        {
+            const double sum = ((red[0][wave][lane] + red[1][wave][lane]) + red[2][wave][lane]) + red[3][wave][lane];
+            const double ynew = yv + alpha * sum;
+            if (yok) Yo[yrow * ldo + li] = ynew;
+            awL[(kk + 4 * wave) * 16 + li] = (yok && li < r2) ? ynew : 0.0;
+            if (NE > 0 && eok) {
+                const double se = ((rede[0][ene][erow] + rede[1][ene][erow]) + rede[2][ene][erow]) + rede[3][ene][erow];
+                Yo[(row0 + erow) * ldo + 16 + ene] = ye + alpha * se;
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        fetch_y(tile + gridDim.x, yv, ye);
+        __syncthreads();
+        // step 2 (a block's four values are asked for before the MFMAs of the block before, and no earlier)
+        double bq[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) bq[q] = awL[(4 * q + kk) * 16 + li];
+        double a4[2][4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) a4[0][q] = T[wave][0][((q & 1) ? tr1 : tr0) + 128 * (q >> 1)];
+#pragma unroll
+        for (int b = 0; b < NBW; ++b) {
+            if (b + 1 < NBW) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) a4[(b + 1) & 1][q] = T[wave][b + 1][((q & 1) ? tr1 : tr0) + 128 * (q >> 1)];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc2[b] = mfma_f64(a4[b & 1][q], bq[q], acc2[b]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        // (the next tile's stores into T stay behind these loads)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+    double *P = partial + (int64_t)blockIdx.x * k * r2;
+#pragma unroll
+    for (int b = 0; b < NBW; ++b)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int ci = (b * 4 + wave) * 16 + kk + 4 * v; // D row -> X column
+            if (ci < k && li < r2) P[ci + (int64_t)li * k] = acc2[b][v];
+        }
+}
+
 template <int NBW>
 static void launch_update_gram(rails_ctx *c, int ne, unsigned grid, double alpha, const double *X, int ldx, int k, const double *C, int r, const double *Y, int ldy,
                                double *Yo, int ldo, int r2, int64_t m, int64_t ntiles)
 {
-    if (ne == 0)
+    const bool pipeline = dense_update_gram_pipeline();
+    if (pipeline && ne == 0)
+        RAILS_LAUNCH((k_update_gram_p<NBW, 0>), dim3(grid), dim3(256), 0, c->stream, alpha, X, ldx, k, C, r, Y, ldy, Yo, ldo, r2, m, ntiles, c->ws);
+    else if (pipeline)
+        RAILS_LAUNCH((k_update_gram_p<NBW, 1>), dim3(grid), dim3(256), 0, c->stream, alpha, X, ldx, k, C, r, Y, ldy, Yo, ldo, r2, m, ntiles, c->ws);
+    else if (ne == 0)
         RAILS_LAUNCH((k_update_gram<NBW, 0>), dim3(grid), dim3(256), 0, c->stream, alpha, X, ldx, k, C, r, Y, ldy, Yo, ldo, r2, m, ntiles, c->ws);
     else
         RAILS_LAUNCH((k_update_gram<NBW, 1>), dim3(grid), dim3(256), 0, c->stream, alpha, X, ldx, k, C, r, Y, ldy, Yo, ldo, r2, m, ntiles, c->ws);
+    c->last_update_gram_form = pipeline ? 2 : 1;
     c->last_update_gram_nbw = NBW;
 }
 

@@ -96,6 +96,7 @@ struct rails_ctx {
     long n_orth_range = 0, n_orth_range_passes = 0, n_orth_range_syncs = 0; // rails_orthogonalize_range: calls, passes over a block of columns, host synchronisations
     // template parameter of the last launch of k_update_gram<NBW, .>, k_gram_cols[2]<TI, ., .> and k_panel_gemm_wide<TR> (rails_dense_last_tiles); 0: none yet
     int last_update_gram_nbw = 0, last_gram_cols_ti = 0, last_gemm_wide_tr = 0;
+    int last_update_gram_form = 0; // the fused update + second projection's last launch: 1 k_update_gram, 2 k_update_gram_p (rails_dense_last_update_gram_form); 0: none yet
 };
 
 // the busy meter (see rails_ctx): RAILS_LAUNCH brackets a launch, rails_stream_sync reads what has been bracketed since the last one
