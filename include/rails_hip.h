@@ -243,7 +243,8 @@ int rails_csr_create_lu(rails_ctx *ctx, rails_lu *lu, rails_csr **out);
  * refused with RAILS_EINVAL before any collective: the transposed product of a row block is single GPU.  A right-hand side that is not
  * finite on any rank gives RAILS_EINVAL on every rank.  On a context that does not reduce nothing of this runs.
  * Settings (rails_iter_set): "tolerance" 1e-10, "max_iterations" 1000, "jacobi" 1, "check_every" 8, "strict" 0, and those of the polynomial
- * preconditioner below: "poly_degree" 0, "poly_ratio" 10, "eig_max" 0, "poly_fused" 1.
+ * preconditioner below: "poly_degree" 0, "poly_ratio" 10, "eig_max" 0, "poly_fused" 1; those of the multigrid preconditioner: "amg" 0,
+ * "amg_degree" 1, "amg_ratio" 4, "amg_theta" 0.08, "amg_coarse" 256.
  * Chebyshev polynomial preconditioner (CG only; rails_amd/csrc/cheb_coef.h): with "poly_degree" K in 1 .. 64 the
  * solve preconditions with z = p_K(G A) G r, K products with A in a row without an inner product, a scalar kernel or a read-back between
  * them; G is the Jacobi diagonal's inverse when Jacobi is in effect and otherwise +-I, the sign of the operator's diagonal.  The
@@ -255,6 +256,19 @@ int rails_csr_create_lu(rails_ctx *ctx, rails_lu *lu, rails_csr **out);
  * either way, and no all-reduce inside the polynomial.  Degree 0, the default, is the solve without any
  * of this, bit for bit.  RAILS_EINVAL: a degree above 0 on a BiCGStab object, a degree outside 0 .. 64, a ratio of at most 1, and a
  * solve with a degree above 0 and no bound.
+ * Smoothed-aggregation multigrid preconditioner (CG only, single GPU; rails_amd/csrc/amg_host.h): with "amg" 1
+ * the solve preconditions with one V-cycle, z = M r: per level a Chebyshev smoother of degree "amg_degree" (1; 0 .. 8) in the
+ * Jacobi-scaled level matrix on [hi / "amg_ratio", hi] ("amg_ratio" 4, above 1; hi the level's Gershgorin bound) before and, as its
+ * adjoint, after the coarse correction, and the dense inverse of the last matrix at the bottom; M is symmetric and definite with the
+ * operator's sign.  The hierarchy is built on the host from the CSR arrays of a stored square operator whose diagonal is stored, nonzero
+ * and of one sign (strength threshold "amg_theta" 0.08, in [0, 1), halved per level; levels until at most "amg_coarse" 256 rows are
+ * left, 1 .. 1024) by rails_iter_amg_setup, which the first solve or rails_iter_precondition with "amg" on calls when there is no
+ * hierarchy; a changed "amg_theta" or "amg_coarse" drops it.  "poly_fused" 0 keeps the cycle off the fused kernels too.  "amg" 0, the
+ * default, is the solve without any of this: the same kernels, bits and launch counts.  RAILS_EINVAL, before any device work: "amg" on
+ * a BiCGStab object; together with a "poly_degree" above 0, in whichever order the two are set; a callback, LU or iterative-solve
+ * operator (a sparse right-hand side or a rectangular handle is refused by rails_iter_create already); a context that reduces; 2^24 rows or more; and from the set-up a matrix with unsorted
+ * or repeated columns in a row, a zero, missing or non-finite diagonal entry, one that is not definite, or one that does not coarsen
+ * below 1025 rows (there is no huge dense block).
  * Outcomes: a zero right-hand-side column gives x = 0 after 0 iterations; a column that stops at max_iterations or breaks down (a
  * vanishing denominator; CG: p'Ap of the wrong sign, the operator is not definite) keeps its last iterate and is flagged, and the call
  * still returns RAILS_OK unless "strict" is set (RAILS_ENOCONV); a right-hand side that is not finite gives RAILS_EINVAL. */
@@ -272,6 +286,15 @@ int rails_iter_solve(rails_ctx *ctx, rails_iter *it, int trans, const rails_pane
  * G X).  Same window rules and groups of 32 columns as rails_iter_solve.  Queues its work and does not synchronise; the counters [1], [2],
  * [7], [13] and [14] of rails_iter_stats then count this call. */
 int rails_iter_precondition(rails_ctx *ctx, rails_iter *it, const rails_panel *X, int xc0, int nc, rails_panel *Y, int yc0);
+/* Builds or rebuilds the multigrid hierarchy of "amg" and uploads it, from the CSR arrays the operator's handle keeps on the host (every
+ * handle of rails_csr_create does).  With "amg" on, rails_iter_precondition applies one cycle.  Synchronises. */
+int rails_iter_amg_setup(rails_ctx *ctx, rails_iter *it);
+/* The hierarchy by its matrices, the last (dense) one included: rows[l], nnz[l] and hi[l] (the Gershgorin bound of the smoother's
+ * interval; 0 for the last matrix) for l < n.  Where cap allows, two more entries: [n] the last call's cycles, the products inside them
+ * (with the level matrices, P and R) and, in hi[n], the launches of the object's own kernels inside them; [n + 1] the set-up's host time
+ * and upload time in microseconds and, in hi[n + 1], the operator complexity.  Any pointer may be NULL.  Returns n (0: no hierarchy has
+ * been built) or a negative code; at most cap entries are written.  rails_iter_stats keeps its 19 entries. */
+int rails_iter_amg_info(const rails_iter *it, int64_t *rows, int64_t *nnz, double *hi, int cap);
 /* Last solve: info[0] most iterations of a column, [1] inner products, [2] launches of the library's own passes, [3] columns that did not
  * converge, [4] of those, broken down, [5] worst relative residual of the recurrence, [6] work-panel columns, [7] products with A;
  * totals since creation: [8] solves, [9] columns, [10] iterations summed over columns, [11] flagged columns, [12] products; the polynomial

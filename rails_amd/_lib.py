@@ -96,6 +96,8 @@ SIGNATURES = {
     "rails_iter_set": (C.c_int, [_vp, C.c_char_p, C.c_double]),
     "rails_iter_solve": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int]),
     "rails_iter_precondition": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int]),
+    "rails_iter_amg_setup": (C.c_int, [_vp, _vp]),
+    "rails_iter_amg_info": (C.c_int, [_vp, _i64p, _i64p, _dp, C.c_int]),
     "rails_iter_stats": (C.c_int, [_vp, _dp, C.c_int]),
     "rails_iter_columns": (C.c_int, [_vp, _i32p, _dp, _i32p, C.c_int]),
     "rails_csr_create_iter": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),

@@ -3,7 +3,9 @@
 // sparse LU (splu.hip) is latency-bound or cannot be formed at all.  Conjugate gradients for a definite operator of either sign,
 // BiCGStab (right-preconditioned) for a general one, both with an optional Jacobi preconditioner; conjugate gradients also with a
 // Chebyshev polynomial in the Jacobi-scaled operator ("poly_degree", cheb_coef.h), whose steps -- a product and its
-// recurrence update -- are one kernel each for a stored CSR operator (k_cheb_step_csr).
+// recurrence update -- are one kernel each for a stored CSR operator (k_cheb_step_csr); or, instead, with one V-cycle of smoothed-
+// aggregation multigrid ("amg", amg_host.h for the set-up on the host, Run::vcycle below) that smooths with the
+// same kernels and adds three of its own (k_amg_residual_csr, k_amg_prolong_add, k_amg_coarse_dense).
 //
 // Every column is a system of its own with its own scalars (rails_iter_col, iter_scalars.h) in a device block the object owns: no block
 // method, no small matrix on the host.  The iteration runs on work panels of the object (ordinary panels, window at column 0, so the
@@ -26,9 +28,11 @@
 #include "rails_internal.h"
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <vector>
 
+#include "amg_host.h"
 #include "cheb_coef.h"
 #include "iter_agree.h"
 #include "iter_scalars.h"
@@ -274,92 +278,94 @@ __global__ __launch_bounds__(256) void k_cheb_pass(PassGeom g, const double *__r
 // object fills before the step with the rows of Zin the neighbours own (rails_halo_exchange, an even number of columns, so that ghost rows
 // are 16-byte aligned like panel rows) -- the select between two bases and two strides k_spmm_narrow<RPG, true, LPR> makes.  The epilogue
 // is the same: local rows only.
+#include "csr_row_gather.inc"
+
 template <int RPG, int LPR, bool GHOST>
 __global__ __launch_bounds__(256) void k_cheb_step_csr(int64_t m, const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
                                                        const double *__restrict__ val, const double *__restrict__ Zin, int ld, int nc, int64_t blocks_per_xcd,
                                                        const double *__restrict__ gvec, double gs, double a, double b, const double *__restrict__ R,
                                                        double *__restrict__ D, double *__restrict__ Zout, const double *__restrict__ Zg, int ldg)
 {
-    constexpr int GROUPS = 256 / LPR, ROWS = GROUPS * RPG, CAP = 2048;
-    __shared__ double s_val[CAP];
-    __shared__ int32_t s_col[CAP];
-    const int g = threadIdx.x / LPR;
-    const int l = threadIdx.x % LPR;
-    const int64_t lb = (int64_t)(blockIdx.x & 7) * blocks_per_xcd + (blockIdx.x >> 3);
-    const int64_t r0 = lb * ROWS;
-    if (r0 >= m) return;
-    const int64_t r1 = (r0 + ROWS < m) ? r0 + ROWS : m;
-    const int64_t nz0 = rowptr[r0], nz1 = rowptr[r1];
-    const bool staged = (nz1 - nz0) <= CAP; // block-uniform
-    if (staged) {
-        for (int q = threadIdx.x; q < (int)(nz1 - nz0); q += 256) {
-            s_col[q] = col[nz0 + q];
-            s_val[q] = val[nz0 + q];
-        }
-        __syncthreads();
-    }
-    const int cb = l * 2;
-    if (cb >= nc) return;
-    const bool full = (cb + 2 <= nc);
-    const uint32_t cb8 = (uint32_t)cb * 8u, ld8 = (uint32_t)ld * 8u;
-    const uint32_t ldg8 = (uint32_t)ldg * 8u, m32 = (uint32_t)m;
-    const char *Zb = reinterpret_cast<const char *>(Zin), *Gb = reinterpret_cast<const char *>(Zg);
-    auto zrow = [&](uint32_t c) -> const char * {
-        if (!GHOST) return Zb + (__umul24(c, ld8) + cb8);
-        const bool local = c < m32;
-        return (local ? Zb : Gb) + ((local ? __umul24(c, ld8) : __umul24(c - m32, ldg8)) + cb8);
-    };
-    for (int rr = 0; rr < RPG; ++rr) {
-        const int64_t row = r0 + (int64_t)rr * GROUPS + g; // the rows in flight are consecutive
-        if (row >= m) break;
-        it_v2 acc = (it_v2){0.0, 0.0};
-        if (staged && full) {
-            int i = (int)(rowptr[row] - nz0);
-            const int i1 = (int)(rowptr[row + 1] - nz0);
-            for (; i + 8 <= i1; i += 8) {
-                it_v2 x[8];
-                double av[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    x[u] = *reinterpret_cast<const it_v2 *>(zrow((uint32_t)s_col[i + u]));
-                    av[u] = s_val[i + u];
-                }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    acc.x = __builtin_fma(av[u], x[u].x, acc.x);
-                    acc.y = __builtin_fma(av[u], x[u].y, acc.y);
-                }
-            }
-            for (; i < i1; i += 4) { // the last one to seven: groups of four, the slots past the end repeat the last entry with a zero
-                it_v2 x[4];
-                double av[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int q = i + u < i1 ? i + u : i1 - 1;
-                    x[u] = *reinterpret_cast<const it_v2 *>(zrow((uint32_t)s_col[q]));
-                    av[u] = i + u < i1 ? s_val[q] : 0.0;
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    acc.x = __builtin_fma(av[u], x[u].x, acc.x);
-                    acc.y = __builtin_fma(av[u], x[u].y, acc.y);
-                }
-            }
-        } else {
-            for (int64_t p = rowptr[row]; p < rowptr[row + 1]; ++p) {
-                const double av = val[p];
-                const double *src = reinterpret_cast<const double *>(zrow((uint32_t)col[p]));
-                acc.x = __builtin_fma(av, src[0], acc.x);
-                if (full) acc.y = __builtin_fma(av, src[1], acc.y);
-            }
-        }
+    csr_row_gather<RPG, LPR, GHOST>(m, rowptr, col, val, Zin, ld, nc, blocks_per_xcd, Zg, ldg, [&](int64_t row, int64_t o, it_v2 acc, bool full) {
         // the epilogue on this thread's own two entries of the row (the pad column beside an odd last column is read, never written)
-        const int64_t o = row * ld + cb;
         const it_v2 res = (ld2(R + o) - acc) * cheb_g(gvec, gs, row);
         const it_v2 d = ld2(D + o) * a + res * b;
         st2(D + o, d, full);
         st2(Zout + o, ld2(Zin + o) + d, full);
-    }
+    });
+}
+
+// ---- the multigrid cycle's own kernels.  All panels are work panels: window at column 0, one row stride ld, rows
+// 16-byte aligned, a zeroed pad column beside an odd width ----
+
+// Q = R - A Z by the fused step's row gather
+template <int RPG, int LPR>
+__global__ __launch_bounds__(256) void k_amg_residual_csr(int64_t m, const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+                                                          const double *__restrict__ val, const double *__restrict__ Z, int ld, int nc, int64_t blocks_per_xcd,
+                                                          const double *__restrict__ R, double *__restrict__ Q)
+{
+    csr_row_gather<RPG, LPR, false>(m, rowptr, col, val, Z, ld, nc, blocks_per_xcd, nullptr, 0,
+                                    [&](int64_t, int64_t o, it_v2 acc, bool full) { st2(Q + o, ld2(R + o) - acc, full); });
+}
+
+// the unfused residual, after Q = A Z: Q = R - Q
+__global__ __launch_bounds__(256) void k_amg_residual_pass(PassGeom g, const double *__restrict__ R, double *__restrict__ Q)
+{
+    iter_pass<0>(g, nullptr, [&](int64_t, int64_t o, bool has1, it_v2 *) { st2(Q + o, ld2(R + o) - ld2(Q + o), has1); });
+}
+
+// Z += P Zc in the passes' thread layout (a pair of columns per thread): a gather over the row of P, its entries added in stored order.
+// Rows of at most 8 entries -- all of them on a 2D grid -- load their entries and the rows of Zc they name first and add then; a longer
+// row (3D, wide bands: 13 to 26 entries) takes a plain loop.  The same sum either way.  Zc has the row stride of Z.
+__global__ __launch_bounds__(256) void k_amg_prolong_add(PassGeom g, const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+                                                         const double *__restrict__ val, const double *__restrict__ Zc, double *__restrict__ Z)
+{
+    iter_pass<0>(g, nullptr, [&](int64_t row, int64_t o, bool has1, it_v2 *) {
+        const int c = (int)(o - row * g.ld);
+        const int64_t p0 = rowptr[row], p1 = rowptr[row + 1];
+        it_v2 acc = (it_v2){0.0, 0.0};
+        if (p1 - p0 <= 8) {
+            it_v2 x[8];
+            double av[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (p0 + u < p1) { // nothing is read past the end of the row: an empty row reads nothing at all
+                    av[u] = val[p0 + u];
+                    x[u] = ld2(Zc + (int64_t)col[p0 + u] * g.ld + c);
+                }
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (p0 + u < p1) {
+                    acc.x = __builtin_fma(av[u], x[u].x, acc.x);
+                    acc.y = __builtin_fma(av[u], x[u].y, acc.y);
+                }
+        } else {
+            for (int64_t q = p0; q < p1; ++q) {
+                const it_v2 x = ld2(Zc + (int64_t)col[q] * g.ld + c);
+                const double av = val[q];
+                acc.x = __builtin_fma(av, x.x, acc.x);
+                acc.y = __builtin_fma(av, x.y, acc.y);
+            }
+        }
+        st2(Z + o, ld2(Z + o) + acc, has1);
+    });
+}
+
+// Z = Ainv R on the last level: Ainv is n x n (n <= 1024), column-major; row i of the result adds Ainv(i, k) R(k, :) for k = 0 .. n - 1 in
+// that order.  The passes' thread layout, no atomics.
+__global__ __launch_bounds__(256) void k_amg_coarse_dense(PassGeom g, const double *__restrict__ Ainv, const double *__restrict__ R, double *__restrict__ Z)
+{
+    iter_pass<0>(g, nullptr, [&](int64_t row, int64_t o, bool has1, it_v2 *) {
+        const int c = (int)(o - row * g.ld);
+        it_v2 acc = (it_v2){0.0, 0.0};
+        for (int64_t k = 0; k < g.m; ++k) {
+            const double av = Ainv[row + k * g.m];
+            const it_v2 x = ld2(R + k * g.ld + c);
+            acc.x = __builtin_fma(av, x.x, acc.x);
+            acc.y = __builtin_fma(av, x.y, acc.y);
+        }
+        st2(Z + o, acc, has1);
+    });
 }
 
 // CG with the polynomial, start (r = b in R, z = p(A) r in Z): p = z, x = 0; partial sums of r.z and r.r
@@ -458,6 +464,27 @@ __global__ __launch_bounds__(64) void k_iter_compute(int step, const double *__r
 // CG: x r p q [z]; BiCGStab: x r p v(=Q) [p^(=Z)] r^ t [s^]; the polynomial: z, its direction d, the second z of the fused step's ping-pong
 enum { W_X = 0, W_R, W_P, W_Q, W_Z, W_RH, W_T, W_SH, W_D, W_Z2, W_COUNT };
 
+// The multigrid hierarchy on the device (amg_host.h builds it on the host).  Level 0 works in the object's own work panels (r = W_R, z =
+// W_Z / W_Z2, d = W_D, q = W_Q) on the object's operator; the levels below own their operators and five panels of the same row stride;
+// the last matrix is its dense inverse with two panels (none when there is no level: W_R and W_Z then).
+enum { L_R = 0, L_Z, L_Z2, L_D, L_Q, L_COUNT };
+struct AmgLevel {
+    int64_t n = 0, nnz = 0;
+    double hi = 0.0;
+    rails_csr *A = nullptr; // level 0: the object's operator (not owned)
+    rails_csr *P = nullptr, *R = nullptr;
+    double *dinv = nullptr;
+    rails_panel *w[L_COUNT] = {};
+};
+struct Amg {
+    std::vector<AmgLevel> lv;
+    int64_t n_coarse = 0, coarse_nnz = 0;
+    double *Ainv = nullptr;
+    rails_panel *rc = nullptr, *zc = nullptr;
+    int cols = 0; // columns of the level panels
+    double host_seconds = 0.0, upload_seconds = 0.0;
+};
+
 } // namespace
 
 struct rails_iter {
@@ -488,6 +515,11 @@ struct rails_iter {
     bool reduces = false;
     double *sums_dev = nullptr; // 64 doubles
     long last_allreduces = 0, last_halo = 0; // all-reduces of the last call; ghost-row exchanges the object issued itself (fused steps)
+    // the multigrid preconditioner ("amg"): off by default; the hierarchy is built on first use (rails_iter_amg_setup)
+    int amg = 0, amg_degree = 1, amg_coarse = RAILS_AMG_COARSE;
+    double amg_ratio = 4.0, amg_theta = RAILS_AMG_THETA;
+    Amg *hier = nullptr;
+    long last_cycles = 0, last_cycle_products = 0, last_cycle_launches = 0; // of the last call: cycles, and the products and launches inside them
     double tot_solves = 0, tot_iterations = 0, tot_flagged = 0, tot_products = 0, tot_columns = 0;
 };
 
@@ -502,11 +534,75 @@ void release_work(rails_iter *it)
     it->work_cols = 0;
 }
 
+void amg_release_panels(Amg *H)
+{
+    for (AmgLevel &L : H->lv)
+        for (rails_panel *&p : L.w) {
+            rails_panel_destroy(p);
+            p = nullptr;
+        }
+    rails_panel_destroy(H->rc);
+    rails_panel_destroy(H->zc);
+    H->rc = H->zc = nullptr;
+    H->cols = 0;
+}
+
+// drops the hierarchy (a changed "amg_theta" or "amg_coarse", a rebuild, the end of the object)
+void amg_release(rails_iter *it)
+{
+    Amg *H = it->hier;
+    if (!H) return;
+    if (it->ctx) hipStreamSynchronize(it->ctx->stream);
+    amg_release_panels(H);
+    for (size_t l = 0; l < H->lv.size(); ++l) {
+        AmgLevel &L = H->lv[l];
+        if (l > 0) rails_csr_destroy(L.A);
+        rails_csr_destroy(L.P);
+        rails_csr_destroy(L.R);
+        hipFree(L.dinv);
+    }
+    hipFree(H->Ainv);
+    delete H;
+    it->hier = nullptr;
+}
+
+// the level panels follow the work panels: the same columns, so the same row stride; they grow only when a wider group arrives
+int amg_grow(rails_ctx *c, rails_iter *it)
+{
+    Amg *H = it->hier;
+    if (H->cols == it->work_cols) return RAILS_OK;
+    amg_release_panels(H);
+    for (size_t l = 1; l < H->lv.size(); ++l)
+        for (rails_panel *&p : H->lv[l].w) RAILS_TRY(rails_panel_create(c, H->lv[l].n, it->work_cols, &p)); // (zeroed: the pad column is)
+    if (!H->lv.empty()) {
+        RAILS_TRY(rails_panel_create(c, H->n_coarse, it->work_cols, &H->rc));
+        RAILS_TRY(rails_panel_create(c, H->n_coarse, it->work_cols, &H->zc));
+    }
+    H->cols = it->work_cols;
+    return RAILS_OK;
+}
+
+// What the multigrid preconditioner refuses, by reason.  "amg" cannot be on without having passed here (rails_iter_set is the gate, and it
+// holds the polynomial off afterwards), so a solve needs no check of its own; rails_iter_amg_setup, which may be called with "amg" off,
+// checks again.  A sparse right-hand side or a rectangular operator never gets this far: rails_iter_create refuses them.
+int amg_check(const rails_iter *it, const char *who)
+{
+    const rails_csr *A = it->A;
+    RAILS_REQUIRE(it->method == RAILS_ITER_CG, "%s: \"amg\" on a BiCGStab object: the multigrid preconditioner is for conjugate gradients (a symmetric definite operator)", who);
+    RAILS_REQUIRE(it->poly_degree == 0, "%s: \"amg\" together with poly_degree %d: one preconditioner at a time", who, it->poly_degree);
+    RAILS_REQUIRE(A->kind != rails_csr::CALLBACK, "%s: \"amg\" needs the entries of the matrix: the operator is a callback", who);
+    RAILS_REQUIRE(A->kind != rails_csr::LU && A->kind != rails_csr::ITER, "%s: \"amg\" needs the entries of the matrix: the operator is an LU or an iterative solve", who);
+    RAILS_REQUIRE(!it->reduces && A->n_ghost == 0 && A->n_send == 0,
+                  "%s: \"amg\" on a context that reduces (more than one rank, an all-reduce hook or a communicator): the multigrid preconditioner is single GPU", who);
+    RAILS_REQUIRE(it->m < ((int64_t)1 << 24), "%s: \"amg\" on %lld rows: the multigrid preconditioner takes fewer than 2^24", who, (long long)it->m);
+    return RAILS_OK;
+}
+
 bool uses_panel(const rails_iter *it, int which)
 {
     const bool jac = it->dinv != nullptr;
-    if (which == W_D || which == W_Z2) return it->poly_degree > 0;
-    if (which == W_Z && it->poly_degree > 0) return true;
+    if (which == W_D || which == W_Z2) return it->poly_degree > 0 || it->amg;
+    if (which == W_Z && (it->poly_degree > 0 || it->amg)) return true;
     if (it->method == RAILS_ITER_CG) return which == W_X || which == W_R || which == W_P || which == W_Q || (which == W_Z && jac);
     return which == W_X || which == W_R || which == W_P || which == W_Q || which == W_RH || which == W_T || ((which == W_Z || which == W_SH) && jac);
 }
@@ -566,12 +662,13 @@ struct Run {
     int K = 0;
     bool fused = false, ghost = false; // ghost: the fused step in its ghost-row form, with an exchange of the object's own before it
     double theta = 1.0, ca[RAILS_CHEB_MAX_DEGREE], cb[RAILS_CHEB_MAX_DEGREE];
+    bool amg = false; // the multigrid cycle is the preconditioner (K is 0 then)
 
     double *d(int k) const { return it->w[k]->d; }
     int scalars(int step, int nq)
     {
         // (with the polynomial r.z carries the sign of the operator itself, as with Jacobi)
-        const double sign = (jac || K > 0) ? 1.0 : it->defsign;
+        const double sign = (jac || K > 0 || amg) ? 1.0 : it->defsign;
         if (!it->reduces) {
             RAILS_LAUNCH(k_iter_scalars, dim3(1), dim3(1024), 0, c->stream, step, c->ws, nslab, g.ncw, nq, cols, it->status_dev, tol2, it->maxit, sign);
             it->last_launches++;
@@ -659,10 +756,117 @@ struct Run {
         }
         return RAILS_OK;
     }
+    // ---- the multigrid V-cycle: W_Z = M W_R.  Down: smooth from zero, residual, restrict; the dense inverse at
+    // the bottom; up: prolong and correct, smooth from z.  Nothing in here synchronises, allocates or reads back.
+    rails_panel *lpanel(int l, int which) const
+    {
+        static const int own[L_COUNT] = {W_R, W_Z, W_Z2, W_D, W_Q};
+        return l == 0 ? it->w[own[which]] : it->hier->lv[(size_t)l].w[which];
+    }
+    double *lp(int l, int which) const { return lpanel(l, which)->d; }
+    // a kernel on the shared row gather over level L's matrix: 64 rows per block, the blocks dealt over the 8 XCDs; its 8-lane form up to
+    // 16 columns, its 16-lane form above.  `rest` is what follows the gather's own arguments.
+    template <class K8, class K16, class... Rest>
+    void launch_gather(K8 k8, K16 k16, const AmgLevel &L, const double *zin, Rest... rest)
+    {
+        const int64_t bpx = ((L.n + 63) / 64 + 7) / 8;
+        if (g.ncw <= 16)
+            RAILS_LAUNCH(k8, dim3((unsigned)(bpx * 8)), dim3(256), 0, c->stream, L.n, L.A->rowptr, L.A->col, L.A->val, zin, g.ld, g.ncw, bpx, rest...);
+        else
+            RAILS_LAUNCH(k16, dim3((unsigned)(bpx * 8)), dim3(256), 0, c->stream, L.n, L.A->rowptr, L.A->col, L.A->val, zin, g.ld, g.ncw, bpx, rest...);
+    }
+    // the passes' geometry on n rows (set_group's rule)
+    void level_geom(int64_t n, PassGeom *lg, int64_t *slabs) const
+    {
+        const int TY = 256 >> g.tx_bits;
+        int64_t ns = std::max<int64_t>(1, std::min<int64_t>(1024, n / ((int64_t)TY * 8)));
+        const int64_t rps = (n + ns - 1) / ns;
+        *slabs = (n + rps - 1) / rps;
+        *lg = PassGeom{g.ncw, g.ld, g.tx_bits, n, rps};
+    }
+    void count_cycle(long launches, long products)
+    {
+        it->last_launches += launches;
+        it->last_cycle_launches += launches;
+        it->last_products += products;
+        it->last_cycle_products += products;
+    }
+    // one smoother step on level l: d = a d + b g (r - A z), z += d; *z names the panel that holds z and follows the fused step's ping-pong
+    int smooth_step(int l, bool lfused, const PassGeom &lg, int64_t slabs, double a, double b, int *z)
+    {
+        const AmgLevel &L = it->hier->lv[(size_t)l];
+        if (!lfused) {
+            RAILS_TRY(rails_spmm(c, L.A, 0, lpanel(l, *z), 0, g.ncw, lpanel(l, L_Q), 0));
+            RAILS_LAUNCH(k_cheb_pass, dim3((unsigned)slabs), dim3(256), 0, c->stream, lg, L.dinv, 1.0, a, b, lp(l, L_Q), lp(l, L_R), lp(l, L_D), lp(l, *z));
+            count_cycle(1, 1);
+            return RAILS_OK;
+        }
+        const int zout = *z == L_Z ? L_Z2 : L_Z;
+        launch_gather(k_cheb_step_csr<2, 8, false>, k_cheb_step_csr<4, 16, false>, L, lp(l, *z), (const double *)L.dinv, 1.0, a, b, (const double *)lp(l, L_R), lp(l, L_D),
+                      lp(l, zout), (const double *)nullptr, 0);
+        count_cycle(1, 1);
+        it->last_fused++;
+        *z = zout;
+        return RAILS_OK;
+    }
+    int vcycle()
+    {
+        Amg &H = *it->hier;
+        const int nl = (int)H.lv.size(), S = it->amg_degree;
+        int zat[RAILS_AMG_MAX_LEVELS];
+        bool lfused[RAILS_AMG_MAX_LEVELS];
+        double th[RAILS_AMG_MAX_LEVELS], a[9], b[9];
+        it->last_cycles++;
+        for (int l = 0; l < nl; ++l) {
+            const AmgLevel &L = H.lv[(size_t)l];
+            PassGeom lg;
+            int64_t slabs;
+            level_geom(L.n, &lg, &slabs);
+            RAILS_REQUIRE(rails_cheb_coef(L.hi / it->amg_ratio, L.hi, S, &th[l], a, b), "rails_iter: no smoother of degree %d on [%g, %g] (level %d)", S, L.hi / it->amg_ratio, L.hi, l);
+            lfused[l] = it->poly_fused && rails_cheb_fused_eligible(true, 0, L.n, g.ld);
+            // every fused step moves z to the other panel, and there are 2 S + 1 of them: the top level starts where its last one writes W_Z
+            zat[l] = lfused[l] ? L_Z2 : L_Z;
+            RAILS_LAUNCH(k_cheb_init, dim3((unsigned)slabs), dim3(256), 0, c->stream, lg, L.dinv, 1.0, th[l], lp(l, L_R), lp(l, L_D), lp(l, zat[l]));
+            count_cycle(1, 0);
+            for (int k = 0; k < S; ++k) RAILS_TRY(smooth_step(l, lfused[l], lg, slabs, a[k], b[k], &zat[l]));
+            if (lfused[l]) {
+                launch_gather(k_amg_residual_csr<2, 8>, k_amg_residual_csr<4, 16>, L, lp(l, zat[l]), (const double *)lp(l, L_R), lp(l, L_Q));
+            } else {
+                RAILS_TRY(rails_spmm(c, L.A, 0, lpanel(l, zat[l]), 0, g.ncw, lpanel(l, L_Q), 0));
+                RAILS_LAUNCH(k_amg_residual_pass, dim3((unsigned)slabs), dim3(256), 0, c->stream, lg, lp(l, L_R), lp(l, L_Q));
+            }
+            count_cycle(1, 1);
+            RAILS_TRY(rails_spmm(c, L.R, 0, lpanel(l, L_Q), 0, g.ncw, l + 1 < nl ? lpanel(l + 1, L_R) : H.rc, 0)); // r_{l+1} = P' q
+            count_cycle(0, 1);
+        }
+        {
+            PassGeom lg;
+            int64_t slabs;
+            level_geom(H.n_coarse, &lg, &slabs);
+            RAILS_LAUNCH(k_amg_coarse_dense, dim3((unsigned)slabs), dim3(256), 0, c->stream, lg, H.Ainv, nl ? H.rc->d : d(W_R), nl ? H.zc->d : d(W_Z));
+            count_cycle(1, 0);
+        }
+        for (int l = nl - 1; l >= 0; --l) {
+            const AmgLevel &L = H.lv[(size_t)l];
+            PassGeom lg;
+            int64_t slabs;
+            level_geom(L.n, &lg, &slabs);
+            const double *below = l + 1 < nl ? lp(l + 1, zat[l + 1]) : H.zc->d;
+            RAILS_LAUNCH(k_amg_prolong_add, dim3((unsigned)slabs), dim3(256), 0, c->stream, lg, L.P->rowptr, L.P->col, L.P->val, below, lp(l, zat[l]));
+            count_cycle(1, 1);
+            // the post-smoother from z, the adjoint of the pre-smoother: one step with (a, b) = (0, 1 / theta) -- d is finite, k_cheb_init wrote
+            // it whatever S is -- then S steps with the recurrence's coefficients (recomputed: a and b above held the last level's)
+            rails_cheb_coef(L.hi / it->amg_ratio, L.hi, S, &th[l], a, b);
+            RAILS_TRY(smooth_step(l, lfused[l], lg, slabs, 0.0, 1.0 / th[l], &zat[l]));
+            for (int k = 0; k < S; ++k) RAILS_TRY(smooth_step(l, lfused[l], lg, slabs, a[k], b[k], &zat[l]));
+        }
+        return RAILS_OK; // (zat[0] is L_Z again: an odd number of fused steps from L_Z2, or no move at all)
+    }
+    int precondition() { return amg ? vcycle() : polynomial(); }
     int start()
     {
-        if (it->method == RAILS_ITER_CG && K > 0) {
-            RAILS_TRY(polynomial());
+        if (it->method == RAILS_ITER_CG && (K > 0 || amg)) {
+            RAILS_TRY(precondition());
             RAILS_TRY(rails_ws_reserve(c, (size_t)nslab * 2 * g.ncw * sizeof(double)));
             RAILS_LAUNCH(k_cg_init_poly, dim3((unsigned)nslab), dim3(256), 0, c->stream, g, d(W_R), d(W_Z), d(W_P), d(W_X), c->ws);
             it->last_launches++;
@@ -680,7 +884,7 @@ struct Run {
     }
     int iteration()
     {
-        if (it->method == RAILS_ITER_CG && K > 0) {
+        if (it->method == RAILS_ITER_CG && (K > 0 || amg)) {
             // the update without its own z (its partial sums are overwritten below), the polynomial, then r.z and r.r in the layout
             // the scalar step reads; K products in a row without an inner product, a scalar kernel or a read-back between them
             RAILS_TRY(product(W_P, W_Q));
@@ -688,7 +892,7 @@ struct Run {
             RAILS_TRY(scalars(STEP_CG_ALPHA, 1));
             RAILS_LAUNCH((k_cg_update<false>), dim3((unsigned)nslab), dim3(256), 0, c->stream, g, cols, it->dinv, d(W_P), d(W_Q), d(W_X), d(W_R), nullptr, c->ws);
             it->last_launches++;
-            RAILS_TRY(polynomial());
+            RAILS_TRY(precondition());
             RAILS_TRY(dots(2, W_R, W_Z, W_R, W_R));
             RAILS_TRY(scalars(STEP_CG_BETA, 2));
             RAILS_LAUNCH(k_cg_dir, dim3((unsigned)nslab), dim3(256), 0, c->stream, g, cols, d(W_Z), d(W_P));
@@ -781,6 +985,7 @@ extern "C" void rails_iter_destroy(rails_iter *it)
         hipSetDevice(it->ctx->device);
         hipStreamSynchronize(it->ctx->stream);
     }
+    amg_release(it);
     release_work(it);
     hipFree(it->dinv);
     hipFree(it->cols_dev);
@@ -938,6 +1143,7 @@ extern "C" int rails_iter_set(rails_iter *it, const char *name, double value)
     else if (n == "poly_degree") {
         RAILS_REQUIRE(value >= 0.0 && value <= RAILS_CHEB_MAX_DEGREE && value == std::floor(value), "rails_iter_set: poly_degree %g is not a whole number in 0 .. %d", value,
                       RAILS_CHEB_MAX_DEGREE);
+        RAILS_REQUIRE(value == 0.0 || !it->amg, "rails_iter_set: poly_degree %g together with \"amg\": one preconditioner at a time", value);
         RAILS_REQUIRE(value == 0.0 || it->method == RAILS_ITER_CG,
                       "rails_iter_set: poly_degree %g on a BiCGStab object: the polynomial preconditioner is for conjugate gradients (a real spectrum)", value);
         it->poly_degree = (int)value;
@@ -949,12 +1155,136 @@ extern "C" int rails_iter_set(rails_iter *it, const char *name, double value)
         it->eig_max = value;
     } else if (n == "poly_fused")
         it->poly_fused = value != 0.0;
-    else {
-        rails_set_error("rails_iter_set: no setting named '%s' (tolerance, max_iterations, jacobi, check_every, strict, poly_degree, poly_ratio, eig_max, poly_fused)", name);
+    else if (n == "amg") {
+        if (value != 0.0) RAILS_TRY(amg_check(it, "rails_iter_set"));
+        it->amg = value != 0.0;
+    } else if (n == "amg_degree") {
+        RAILS_REQUIRE(value >= 0.0 && value <= 8.0 && value == std::floor(value), "rails_iter_set: amg_degree %g is not a whole number in 0 .. 8", value);
+        it->amg_degree = (int)value;
+    } else if (n == "amg_ratio") {
+        RAILS_REQUIRE(value > 1.0, "rails_iter_set: amg_ratio %g is not above 1", value);
+        it->amg_ratio = value;
+    } else if (n == "amg_theta") {
+        RAILS_REQUIRE(value >= 0.0 && value < 1.0, "rails_iter_set: amg_theta %g is not in [0, 1)", value);
+        if (value != it->amg_theta) amg_release(it);
+        it->amg_theta = value;
+    } else if (n == "amg_coarse") {
+        RAILS_REQUIRE(value >= 1.0 && value <= RAILS_AMG_MAX_COARSE && value == std::floor(value), "rails_iter_set: amg_coarse %g is not a whole number in 1 .. %d", value,
+                      RAILS_AMG_MAX_COARSE);
+        if ((int)value != it->amg_coarse) amg_release(it);
+        it->amg_coarse = (int)value;
+    } else {
+        rails_set_error("rails_iter_set: no setting named '%s' (tolerance, max_iterations, jacobi, check_every, strict, poly_degree, poly_ratio, eig_max, poly_fused, amg, amg_degree, "
+                        "amg_ratio, amg_theta, amg_coarse)", name);
         return RAILS_EINVAL;
     }
     return RAILS_OK;
 }
+
+// Builds (or rebuilds) the multigrid hierarchy from the CSR arrays the operator's handle keeps on the host and uploads it: the level operators, P and R = P' as rectangular operators, the inverse diagonals, the dense inverse.
+extern "C" int rails_iter_amg_setup(rails_ctx *c, rails_iter *it)
+{
+    if (c) hipSetDevice(c->device);
+    RAILS_REQUIRE(c && it, "rails_iter_amg_setup: null argument");
+    RAILS_REQUIRE(c == it->ctx, "rails_iter_amg_setup: the object belongs to another context");
+    RAILS_TRY(amg_check(it, "rails_iter_amg_setup"));
+    amg_release(it);
+    rails_csr *A = it->A;
+    const int64_t m = it->m;
+    // the CSR arrays every stored handle keeps on the host (rails_csr_create); a handle without them would need a copy back from the device
+    RAILS_REQUIRE((int64_t)A->h_rowptr.size() == m + 1 && (int64_t)A->h_val.size() == A->h_rowptr[m] && A->h_col.size() == A->h_val.size(),
+                  "rails_iter_amg_setup: the operator keeps no CSR arrays on the host to build the hierarchy from");
+    const int64_t *rowptr = A->h_rowptr.data();
+    const int32_t *col = A->h_col.data();
+    const double *val = A->h_val.data();
+    const auto t0 = std::chrono::steady_clock::now();
+    rails_amg_hierarchy h;
+    RAILS_TRY(rails_amg_build_host(m, rowptr, col, val, it->amg_theta, it->amg_coarse, &h));
+    const auto t1 = std::chrono::steady_clock::now();
+    Amg *H = new Amg;
+    it->hier = H; // (released by amg_release, also when an upload below fails)
+    H->n_coarse = h.coarse.n_rows;
+    H->coarse_nnz = h.coarse.nnz();
+    H->lv.resize(h.levels.size());
+    int rc = RAILS_OK;
+    hipError_t e = hipSuccess;
+    for (size_t l = 0; l < h.levels.size() && rc == RAILS_OK && e == hipSuccess; ++l) {
+        const rails_amg_level &S = h.levels[l];
+        AmgLevel &L = H->lv[l];
+        L.n = S.A.n_rows;
+        L.nnz = S.A.nnz();
+        L.hi = S.hi;
+        if (l == 0)
+            L.A = A;
+        else
+            rc = rails_csr_create(c, L.n, L.n, S.A.rowptr.data(), S.A.col.data(), S.A.val.data(), &L.A);
+        if (rc == RAILS_OK) rc = rails_csr_create_rect(c, S.P.n_rows, S.P.n_cols, S.P.rowptr.data(), S.P.col.data(), S.P.val.data(), &L.P);
+        if (rc == RAILS_OK) rc = rails_csr_create_rect(c, S.R.n_rows, S.R.n_cols, S.R.rowptr.data(), S.R.col.data(), S.R.val.data(), &L.R);
+        if (rc == RAILS_OK) e = hipMalloc((void **)&L.dinv, (size_t)L.n * sizeof(double));
+        if (rc == RAILS_OK && e == hipSuccess) e = hipMemcpy(L.dinv, S.dinv.data(), (size_t)L.n * sizeof(double), hipMemcpyHostToDevice);
+    }
+    if (rc == RAILS_OK && e == hipSuccess) e = hipMalloc((void **)&H->Ainv, h.coarse_inv.size() * sizeof(double));
+    if (rc == RAILS_OK && e == hipSuccess) e = hipMemcpy(H->Ainv, h.coarse_inv.data(), h.coarse_inv.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (rc != RAILS_OK || e != hipSuccess) {
+        if (rc == RAILS_OK) rails_set_error("rails_iter_amg_setup: device allocation or upload failed: %s", hipGetErrorString(e));
+        amg_release(it);
+        return rc != RAILS_OK ? rc : RAILS_EHIP;
+    }
+    H->host_seconds = std::chrono::duration<double>(t1 - t0).count();
+    H->upload_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+    return RAILS_OK;
+}
+
+// The hierarchy by its matrices, the last (dense) one included: rows, entries and the Gershgorin bound hi of the smoother's interval (0 for
+// the last) of matrix l in rows[l], nnz[l], hi[l], l < n.  Two more entries where cap allows: [n] the last call's cycles, the products
+// inside them (with A_l, P and R) and the launches of the object's own kernels inside them; [n + 1] the set-up's host time and its upload
+// time in microseconds, and in hi[n + 1] the operator complexity (the entries of all matrices over those of the first).  Returns n, 0
+// when no hierarchy has been built; at most cap entries are written.
+extern "C" int rails_iter_amg_info(const rails_iter *it, int64_t *rows, int64_t *nnz, double *hi, int cap)
+{
+    RAILS_REQUIRE(it && cap >= 0, "rails_iter_amg_info: bad argument");
+    const Amg *H = it->hier;
+    if (!H) return 0;
+    const int n = (int)H->lv.size() + 1;
+    double total = (double)H->coarse_nnz;
+    for (const AmgLevel &L : H->lv) total += (double)L.nnz;
+    for (int l = 0; l < n + 2 && l < cap; ++l) {
+        int64_t r, z;
+        double v;
+        if (l < n - 1) {
+            r = H->lv[(size_t)l].n;
+            z = H->lv[(size_t)l].nnz;
+            v = H->lv[(size_t)l].hi;
+        } else if (l == n - 1) {
+            r = H->n_coarse;
+            z = H->coarse_nnz;
+            v = 0.0;
+        } else if (l == n) {
+            r = it->last_cycles;
+            z = it->last_cycle_products;
+            v = (double)it->last_cycle_launches;
+        } else {
+            r = (int64_t)(H->host_seconds * 1e6);
+            z = (int64_t)(H->upload_seconds * 1e6);
+            v = total / (double)(H->lv.empty() ? H->coarse_nnz : H->lv[0].nnz);
+        }
+        if (rows) rows[l] = r;
+        if (nnz) nnz[l] = z;
+        if (hi) hi[l] = v;
+    }
+    return n;
+}
+
+namespace {
+
+// before a solve or an application with "amg" on: the hierarchy when there is none yet, the level panels at the work panels' width
+int amg_prepare(rails_ctx *c, rails_iter *it)
+{
+    if (!it->hier) RAILS_TRY(rails_iter_amg_setup(c, it));
+    return amg_grow(c, it);
+}
+
+} // namespace
 
 extern "C" int rails_iter_solve(rails_ctx *c, rails_iter *it, int trans, const rails_panel *X, int xc0, int nc, rails_panel *Y, int yc0)
 {
@@ -973,9 +1303,11 @@ extern "C" int rails_iter_solve(rails_ctx *c, rails_iter *it, int trans, const r
     RAILS_REQUIRE(xc0 >= 0 && nc >= 0 && xc0 + nc <= X->cap && yc0 >= 0 && yc0 + nc <= Y->cap, "rails_iter_solve: column windows outside the panels");
     if (X->d == Y->d) RAILS_REQUIRE(xc0 + nc <= yc0 || yc0 + nc <= xc0, "rails_iter_solve: X and Y windows alias");
     it->last_dots = it->last_launches = it->last_products = it->last_poly = it->last_fused = it->last_allreduces = it->last_halo = 0;
+    it->last_cycles = it->last_cycle_products = it->last_cycle_launches = 0;
     it->last.clear();
     if (nc == 0) return RAILS_OK;
     RAILS_TRY(grow_work(c, it, std::min(nc, RAILS_ITER_GROUP)));
+    if (it->amg) RAILS_TRY(amg_prepare(c, it));
     RAILS_TRY(grow_cols(c, it, nc));
     int32_t *status = (int32_t *)it->pinned;
     Run run;
@@ -985,6 +1317,7 @@ extern "C" int rails_iter_solve(rails_ctx *c, rails_iter *it, int trans, const r
     run.jac = it->jacobi && it->dinv;
     run.tol2 = it->tol * it->tol;
     RAILS_TRY(poly_setup(run, "rails_iter_solve"));
+    run.amg = it->amg != 0;
     for (int g0 = 0; g0 < nc; g0 += RAILS_ITER_GROUP) {
         const int w = std::min(RAILS_ITER_GROUP, nc - g0);
         set_group(run, w);
@@ -1037,10 +1370,12 @@ extern "C" int rails_iter_precondition(rails_ctx *c, rails_iter *it, const rails
     RAILS_REQUIRE(xc0 >= 0 && nc >= 0 && xc0 + nc <= X->cap && yc0 >= 0 && yc0 + nc <= Y->cap, "rails_iter_precondition: column windows outside the panels");
     if (X->d == Y->d) RAILS_REQUIRE(xc0 + nc <= yc0 || yc0 + nc <= xc0, "rails_iter_precondition: X and Y windows alias");
     it->last_dots = it->last_launches = it->last_products = it->last_poly = it->last_fused = it->last_allreduces = it->last_halo = 0; // the counters count this call
+    it->last_cycles = it->last_cycle_products = it->last_cycle_launches = 0;
     if (nc == 0) return RAILS_OK;
     unsigned want = 1u << W_R | 1u << W_Z | 1u << W_D;
-    if (it->poly_degree > 0) want |= 1u << W_Z2 | 1u << W_Q;
+    if (it->poly_degree > 0 || it->amg) want |= 1u << W_Z2 | 1u << W_Q;
     RAILS_TRY(grow_work(c, it, std::min(nc, RAILS_ITER_GROUP), want));
+    if (it->amg) RAILS_TRY(amg_prepare(c, it));
     Run run;
     run.c = c;
     run.it = it;
@@ -1049,11 +1384,12 @@ extern "C" int rails_iter_precondition(rails_ctx *c, rails_iter *it, const rails
     run.tol2 = 0.0;
     run.cols = nullptr;
     RAILS_TRY(poly_setup(run, "rails_iter_precondition"));
+    run.amg = it->amg != 0;
     for (int g0 = 0; g0 < nc; g0 += RAILS_ITER_GROUP) {
         const int w = std::min(RAILS_ITER_GROUP, nc - g0);
         set_group(run, w);
         RAILS_TRY(rails_panel_copy(c, X, xc0 + g0, w, it->w[W_R], 0));
-        RAILS_TRY(run.polynomial());
+        RAILS_TRY(run.precondition());
         RAILS_TRY(rails_panel_copy(c, it->w[W_Z], 0, w, Y, yc0 + g0));
     }
     RAILS_HIP_CHECK(hipGetLastError());

@@ -28,6 +28,10 @@ class IterativeInverse:
     poly_degree K > 0 (conjugate gradients only): precondition with the Chebyshev polynomial z = p_K(G A) G r, K products per application
     and no inner product between them, fitted to [hi / poly_ratio, hi]; hi is eig_max, or (None) a Gershgorin bound from the CSR arrays --
     an operator that is not a CSR matrix needs eig_max.  poly_ratio None: the library's default.
+    amg=True (conjugate gradients on a CSR matrix, one GPU, not together with poly_degree): precondition with one V-cycle of
+    smoothed-aggregation multigrid, whose iteration count does not grow with the grid: Chebyshev smoothing of degree amg_degree (1) on
+    [hi / amg_ratio, hi] (4) per level, strength threshold amg_theta (0.08), levels until at most amg_coarse (256) rows are left, which
+    are inverted densely.  None: the library's defaults.  The hierarchy is built by the first solve, or by amg_setup().
 
     On a row-partitioned context (Context.set_partition with more than one rank) A is the rank's operator wrapper with its halo plan set,
     the all-reduce hook or the communicator is installed before the object is made, and making it, set(), solve() and precondition() are
@@ -35,7 +39,7 @@ class IterativeInverse:
     (ValueError), and so is trans=True (the transposed product of a row block is single GPU)."""
 
     def __init__(self, ctx, A, method="auto", tol=1e-10, maxit=1000, jacobi=True, strict=False, diag=None, check_every=None, poly_degree=0,
-                 poly_ratio=None, eig_max=None):
+                 poly_ratio=None, eig_max=None, amg=False, amg_degree=None, amg_ratio=None, amg_theta=None, amg_coarse=None):
         self.ctx = ctx
         self._owned = None
         if isinstance(A, HipOperatorWrapper):
@@ -83,6 +87,11 @@ class IterativeInverse:
             self.set("eig_max", eig_max)
         if poly_degree:
             self.set("poly_degree", poly_degree)
+        for name, value in (("amg_degree", amg_degree), ("amg_ratio", amg_ratio), ("amg_theta", amg_theta), ("amg_coarse", amg_coarse)):
+            if value is not None:
+                self.set(name, value)
+        if amg:
+            self.set("amg", 1)
         oh = C.c_void_p()
         check(ctx.lib.rails_csr_create_iter(ctx.h, h, C.byref(oh)), "rails_csr_create_iter")
         self.op = HipOperatorWrapper(ctx, None, None, None, _handle=_Handle(ctx, oh))
@@ -91,7 +100,8 @@ class IterativeInverse:
     def set(self, name, value):
         """"tolerance", "max_iterations", "jacobi", "check_every", "strict"; the polynomial preconditioner: "poly_degree" (0 .. 64, 0 is
         off; conjugate gradients only), "poly_ratio" (hi / lo of its interval, above 1), "eig_max" (hi; 0: the Gershgorin bound),
-        "poly_fused" (0: never the fused step kernel) (rails_iter_set)"""
+        "poly_fused" (0: never the fused step kernel); the multigrid preconditioner: "amg" (1: on), "amg_degree" (0 .. 8), "amg_ratio"
+        (above 1), "amg_theta" (in [0, 1)), "amg_coarse" (1 .. 1024) (rails_iter_set)"""
         check(self.ctx.lib.rails_iter_set(self.h, name.encode(), float(value)), "rails_iter_set")
 
     def solve(self, X, Y=None, trans=False):
@@ -104,13 +114,32 @@ class IterativeInverse:
         return Y
 
     def precondition(self, X, Y=None):
-        """Y = p_K(G A) G X, the preconditioner of the solve on its own (K = poly_degree; 0: G X), for a HipMultiVectorWrapper X of m rows
-        (a new Y when None).  Queues its work and does not synchronise."""
+        """Y = p_K(G A) G X, the preconditioner of the solve on its own (K = poly_degree; 0: G X; with amg on: one V-cycle), for a
+        HipMultiVectorWrapper X of m rows (a new Y when None).  Queues its work and does not synchronise."""
         if Y is None:
             Y = HipMultiVectorWrapper(self.ctx, self.m, X.n)
         assert Y.n == X.n
         check(self.ctx.lib.rails_iter_precondition(self.ctx.h, self.h, X.panel.h, X.c0, X.n, Y.panel.h, Y.c0), "rails_iter_precondition")
         return Y
+
+    def amg_setup(self):
+        """builds (or rebuilds) the multigrid hierarchy now and uploads it (rails_iter_amg_setup); returns amg_info()"""
+        check(self.ctx.lib.rails_iter_amg_setup(self.ctx.h, self.h), "rails_iter_amg_setup")
+        return self.amg_info()
+
+    def amg_info(self):
+        """the hierarchy and the last call (rails_iter_amg_info): "levels" (matrices, the dense last one included; 0: none built), per
+        matrix "rows", "nnz" and "hi", "operator_complexity", the last call's "cycles", "cycle_products" and "cycle_launches", and the
+        "host_seconds" and "upload_seconds" of the set-up"""
+        cap = 20
+        rows, nnz, hi = (C.c_int64 * cap)(), (C.c_int64 * cap)(), (C.c_double * cap)()
+        n = self.ctx.lib.rails_iter_amg_info(self.h, rows, nnz, hi, cap)
+        check(min(n, 0), "rails_iter_amg_info")
+        if n == 0:
+            return {"levels": 0, "rows": [], "nnz": [], "hi": [], "operator_complexity": 0.0, "cycles": 0, "cycle_products": 0, "cycle_launches": 0,
+                    "host_seconds": 0.0, "upload_seconds": 0.0}
+        return {"levels": n, "rows": list(rows[:n]), "nnz": list(nnz[:n]), "hi": list(hi[:n]), "operator_complexity": hi[n + 1], "cycles": int(rows[n]),
+                "cycle_products": int(nnz[n]), "cycle_launches": int(hi[n]), "host_seconds": rows[n + 1] * 1e-6, "upload_seconds": nnz[n + 1] * 1e-6}
 
     def solve_host(self, X, trans=False):
         """the same on a host array (m x nc): upload, solve, download"""

@@ -2,7 +2,7 @@
 
     python -m rails_amd.main [params.xml] [--dir DIR] [--A A.mtx] [--B B.mtx] [--M M.mtx] [--V V.mtx] [--T T.mtx]
                                [--eigs K] [--variance FILE] [--sparse-B] [--warm-start V.mtx | --start-space S.mtx] [--restart-upon-start]
-                               [--inverse {lu,cg,bicgstab,iterative}] [--inverse-tol T] [--inverse-poly K]
+                               [--inverse {lu,cg,bicgstab,iterative}] [--inverse-tol T] [--inverse-poly K] [--inverse-amg]
     python -m torch.distributed.run --nproc-per-node N -m rails_amd.main ... [--backend {nccl,gloo}] [--one-device]
                                                                                   (one rank per GPU, rows partitioned)
 
@@ -21,7 +21,10 @@ keeps the rows of the Schur complement.
 factorised on the host and applied on the device, `cg` / `bicgstab` an iteration on the device to the relative tolerance `--inverse-tol`
 (rails_amd.IterativeInverse; the reference allows an approximate inverse), `iterative` conjugate gradients when A equals its transpose and
 BiCGStab otherwise.  `--inverse-poly K` preconditions the conjugate gradients with a Chebyshev polynomial of degree K (K products in a
-row without an inner product between them; 0, the default, is off); with an inverse that resolves to BiCGStab the driver refuses it.  A
+row without an inner product between them; 0, the default, is off); with an inverse that resolves to BiCGStab the driver refuses it.
+`--inverse-amg` preconditions them with one V-cycle of smoothed-aggregation multigrid instead (rails_amd.IterativeInverse(amg=True): an
+iteration count that does not grow with the grid); the driver refuses it together with `--inverse-poly`, with an inverse that resolves to
+BiCGStab, with the sparse LU and on more than one rank.  A
 Schur-complement problem keeps the inverse of its Schur operator.  On more than one rank the sparse LU is not available (a factorisation
 does not partition by rows): name one of the iterative inverses there.  Each rank then builds its inverse from its own row block, the
 inner products of the iteration are all-reduced, and `iterative` decides symmetry on the whole matrix, which every rank has read.  No run
@@ -77,6 +80,8 @@ def main(argv=None):
     ap.add_argument("--inverse-tol", type=float, default=1e-10, metavar="T", help="relative tolerance of an iterative inverse (per column)")
     ap.add_argument("--inverse-poly", type=int, default=0, metavar="K", help="degree of the Chebyshev polynomial preconditioner of a conjugate-gradients inverse "
                                                                             "(K products per application; 0: off)")
+    ap.add_argument("--inverse-amg", action="store_true", help="precondition a conjugate-gradients inverse with a smoothed-aggregation multigrid V-cycle "
+                                                             "(one rank; not together with --inverse-poly)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend of a run on several ranks; gloo = rehearsal of the "
                                                                                 "multi-process path (collectives staged through host memory)")
     ap.add_argument("--one-device", action="store_true", help="every rank uses device 0 (rehearsal on a machine with one GPU)")
@@ -224,6 +229,14 @@ def main(argv=None):
     # "Projection method" above 1 (opts.projection_method, matlab/RAILSsolver.m:7-24): the driver builds the inverse it needs
     method = next((float(v) for k, v in params.items() if k.lower() == "projection method"), 1.0)
     inverse = None
+    if method > 1 and args.inverse_amg:  # refused before anything is built
+        if args.inverse_poly:
+            raise SystemExit("--inverse-amg together with --inverse-poly %d: one preconditioner at a time" % args.inverse_poly)
+        if world > 1:
+            raise SystemExit("--inverse-amg on %d ranks: the multigrid preconditioner is single GPU" % world)
+        if args.inverse == "lu" or schur is not None:
+            raise SystemExit("--inverse-amg: the multigrid preconditioner is for a conjugate-gradients inverse (--inverse cg or iterative), and the inverse chosen is "
+                             "a sparse LU")
     if method > 1:
         if world > 1 and args.inverse == "lu":
             raise SystemExit("'Projection method' %g on %d ranks: the sparse LU inverse runs on one rank; use --inverse iterative (or cg, bicgstab), "
@@ -253,11 +266,19 @@ def main(argv=None):
                 raise SystemExit("--inverse-poly %d: the polynomial preconditioner is for conjugate gradients, and the inverse chosen is %s" % (
                     args.inverse_poly, inverse.method))
             inverse.set("poly_degree", args.inverse_poly)
+        if isinstance(inverse, rails_amd.IterativeInverse) and args.inverse_amg:
+            if inverse.method != "cg":
+                raise SystemExit("--inverse-amg: the multigrid preconditioner is for conjugate gradients, and the inverse chosen is %s" % inverse.method)
+            inverse.set("amg", 1)
+            amg = inverse.amg_setup()
         solver.set_inverse(inverse)
         if isinstance(inverse, rails_amd.IterativeInverse):
             _log(rank, "Projection method %g: A^-1 is an iterative solve on the device, method %s, Jacobi, tolerance %g" % (method, inverse.method, args.inverse_tol))
             if args.inverse_poly:
                 _log(rank, "its preconditioner: a Chebyshev polynomial of degree %d in the Jacobi-scaled matrix" % args.inverse_poly)
+            if args.inverse_amg:
+                _log(rank, "its preconditioner: a smoothed-aggregation multigrid V-cycle, %d levels of %s rows, operator complexity %.2f, set up in %.3f s" % (
+                    amg["levels"], " / ".join(str(r) for r in amg["rows"]), amg["operator_complexity"], amg["host_seconds"] + amg["upload_seconds"]))
         else:
             _log(rank, "Projection method %g: A^-1 is %s; nnz(L+U) %d, factorised in %.2f s" % (method, what, inverse.nnz, time.time() - t0))
 
@@ -282,6 +303,10 @@ def main(argv=None):
         if args.inverse_poly:  # what the object itself counted in its last solve, not what was asked for
             _log(rank, "its last solve: %d applications of the polynomial, %d products with A, %d of them in fused steps" % (
                 st["poly_applications"], st["products"], st["fused_launches"]))
+        if args.inverse_amg:
+            amg = inverse.amg_info()
+            _log(rank, "its last solve: %d inner iterations at most, %d multigrid cycles, %d products and %d launches inside them" % (
+                st["max_iterations_of_a_column"], amg["cycles"], amg["cycle_products"], amg["cycle_launches"]))
     if Nsp is not None:
         _log(rank, "nullspace: %d of %d columns kept" % (solver.nullspace_rank, Nsp.shape[1]))
     if S0 is not None:
