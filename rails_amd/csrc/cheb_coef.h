@@ -1,6 +1,6 @@
 // cheb_coef.h -- the host arithmetic of the Chebyshev polynomial preconditioner of the iterative A^-1 operator (itsolve.hip): the
-// coefficients of the recurrence, the Gershgorin bound on the spectrum of G A, and the rule for which operators the fused step kernel
-// (k_cheb_step_csr) takes.  No HIP in here: the library compiles it for the host, tests/cpp/cheb_coef_host.cpp stands alone on it, and
+// coefficients of the recurrence, the Gershgorin bound on the spectrum of G A, the rule for which operators the fused step kernel
+// (k_cheb_step_csr) takes, and the z panel a sweep starts in.  No HIP in here: the library compiles it for the host, tests/cpp/cheb_coef_host.cpp stands alone on it, and
 // tests/cheb_reference.py restates it in numpy.
 //
 // z = p_K(G A) G r with the spectrum of G A in (0, hi] and the polynomial fitted to [lo, hi]:
@@ -69,5 +69,10 @@ inline bool rails_cheb_fused_ghost_eligible(bool stored_csr, int64_t m, int64_t 
     if (ld * 8 >= (int64_t)1 << 24 || ldg * 8 >= (int64_t)1 << 24) return false;
     return (uint64_t)m * (uint64_t)ld * 8u < 0xffffff00ull && (uint64_t)n_ghost * (uint64_t)ldg * 8u < 0xffffff00ull;
 }
+
+// The z panel a sweep starts in, 0 the primary and 1 the other one, when `steps` steps follow its start: a fused step reads one z panel and
+// writes the other (every block reads rows that other blocks own), so an odd number of them starts in the other panel and the last one
+// writes the primary; an unfused step updates z in place, in the primary.
+inline int rails_cheb_start_panel(bool fused, int steps) { return fused ? steps & 1 : 0; }
 
 #endif

@@ -1,4 +1,4 @@
-// csr_row_gather.inc -- the row gather the kernels of itsolve.hip share (included there, inside its anonymous namespace, after it_v2, ld2
+// csr_row_gather.inc -- the row gather the kernels of itsolve.hip share (included by iter_kernels.inc, so inside itsolve.hip's anonymous namespace, after it_v2, ld2
 // and st2): t = (A Zin)_row for the rows of one block by k_spmm_narrow's scheme (spmm.hip), then epilogue(row, offset of the thread's
 // pair in a work panel, t, full) in the same thread.  k_cheb_step_csr (the fused Chebyshev step) and k_amg_residual_csr (the multigrid
 // cycle's residual) differ in their epilogues only.

@@ -5,7 +5,10 @@
 // Chebyshev polynomial in the Jacobi-scaled operator ("poly_degree", cheb_coef.h), whose steps -- a product and its
 // recurrence update -- are one kernel each for a stored CSR operator (k_cheb_step_csr); or, instead, with one V-cycle of smoothed-
 // aggregation multigrid ("amg", amg_host.h for the set-up on the host, Run::vcycle below) that smooths with the
-// same kernels and adds three of its own (k_amg_residual_csr, k_amg_prolong_add, k_amg_coarse_dense).
+// same kernels and adds three of its own (k_amg_residual_csr, k_amg_prolong_add, k_amg_coarse_dense).  This file is the host code; the
+// kernels are iter_kernels.inc, the geometry of a pass is iter_geom.h.  Both preconditioners are Chebyshev sweeps (struct Sweep,
+// Run::sweep_start, Run::sweep_step); what a call needs of them -- coefficients, the choice of the fused step, geometry -- is its plan,
+// made before anything is queued (begin_call, plan_call, plan_group), and every refusal is there.
 //
 // Every column is a system of its own with its own scalars (rails_iter_col, iter_scalars.h) in a device block the object owns: no block
 // method, no small matrix on the host.  The iteration runs on work panels of the object (ordinary panels, window at column 0, so the
@@ -35,6 +38,7 @@
 #include "amg_host.h"
 #include "cheb_coef.h"
 #include "iter_agree.h"
+#include "iter_geom.h"
 #include "iter_scalars.h"
 
 namespace {
@@ -42,431 +46,17 @@ namespace {
 constexpr int RAILS_ITER_GROUP = 32; // columns per group: the widest panel every SpMM kernel takes in one chunk
 // default of "poly_ratio" (hi / lo): the smallest worst case of products relative to plain CG over the table of DESIGN.md section 15
 constexpr double RAILS_ITER_POLY_RATIO = 10.0;
+using PassGeom = rails_pass_geom; // (the name the kernels use)
 
-typedef double it_v2 __attribute__((ext_vector_type(2)));
-
-struct PassGeom {
-    int ncw;     // columns of the group
-    int ld;      // row stride of every work panel
-    int tx_bits; // TX = 1 << tx_bits threads along the column pairs, TY = 256 / TX along the rows
-    int64_t m, rows_per_slab;
-};
-
-enum { STEP_CG_INIT = 0, STEP_CG_ALPHA, STEP_CG_BETA, STEP_BI_INIT, STEP_BI_ALPHA, STEP_BI_OMEGA, STEP_BI_END };
-
-__device__ __forceinline__ it_v2 ld2(const double *p) { return *reinterpret_cast<const it_v2 *>(p); }
-__device__ __forceinline__ void st2(double *p, it_v2 v, bool has1)
-{
-    if (has1)
-        *reinterpret_cast<it_v2 *>(p) = v;
-    else
-        p[0] = v.x; // the last column of an odd width: its neighbour is padding and stays as it is
-}
-// y + a x where a != 0, y itself where a == 0 (a stopped column: not even a non-finite x may reach y)
-__device__ __forceinline__ it_v2 axpy_sel(it_v2 a, it_v2 x, it_v2 y)
-{
-    it_v2 o;
-    o.x = a.x != 0.0 ? fma(a.x, x.x, y.x) : y.x;
-    o.y = a.y != 0.0 ? fma(a.y, x.y, y.y) : y.y;
-    return o;
-}
-
-// The shape every pass shares.  body(row, offset of the pair in a work panel, has1, acc) streams one row of one column pair and adds to
-// acc[0 .. NQ); the partial sums of block b land in partial[(b * NQ + q) * ncw + column].
-template <int NQ, class Body>
-__device__ __forceinline__ void iter_pass(const PassGeom &g, double *__restrict__ partial, Body body)
-{
-    __shared__ double sh[NQ > 0 ? NQ : 1][256][2];
-    const int TX = 1 << g.tx_bits, TY = 256 >> g.tx_bits;
-    const int tx = threadIdx.x & (TX - 1), ty = threadIdx.x >> g.tx_bits;
-    const int c = 2 * tx;
-    const bool has0 = c < g.ncw, has1 = c + 1 < g.ncw;
-    const int64_t r_begin = (int64_t)blockIdx.x * g.rows_per_slab;
-    const int64_t r_end = r_begin + g.rows_per_slab < g.m ? r_begin + g.rows_per_slab : g.m;
-    it_v2 acc[NQ > 0 ? NQ : 1];
-#pragma unroll
-    for (int q = 0; q < (NQ > 0 ? NQ : 1); ++q) acc[q] = (it_v2){0.0, 0.0};
-    if (has0) {
-#pragma unroll 4
-        for (int64_t r = r_begin + ty; r < r_end; r += TY) body(r, r * g.ld + c, has1, acc);
-    }
-    if (NQ == 0) return;
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-        sh[q][threadIdx.x][0] = acc[q].x;
-        sh[q][threadIdx.x][1] = acc[q].y;
-    }
-    __syncthreads();
-    for (int half = TY >> 1; half > 0; half >>= 1) { // row class ty += row class ty + half: a tree of fixed shape
-        if (ty < half) {
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                sh[q][threadIdx.x][0] += sh[q][threadIdx.x + (half << g.tx_bits)][0];
-                sh[q][threadIdx.x][1] += sh[q][threadIdx.x + (half << g.tx_bits)][1];
-            }
-        }
-        __syncthreads();
-    }
-    if (ty == 0 && has0) {
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            double *dst = partial + ((int64_t)blockIdx.x * NQ + q) * g.ncw + c;
-            dst[0] = sh[q][tx][0];
-            if (has1) dst[1] = sh[q][tx][1];
-        }
-    }
-}
-
-#define ITER_COEF(name, field)                                                                                                                 \
-    const int cc__##name = 2 * (threadIdx.x & ((1 << g.tx_bits) - 1));                                                                          \
-    const it_v2 name = {cc__##name < g.ncw ? cols[cc__##name].field : 0.0, cc__##name + 1 < g.ncw ? cols[cc__##name + 1].field : 0.0}
-
-// CG start (r = b is in R): z = D^-1 r, p = z, x = 0; partial sums of r.z and r.r
-template <bool JAC>
-__global__ __launch_bounds__(256) void k_cg_init(PassGeom g, const double *__restrict__ dinv, const double *__restrict__ R, double *__restrict__ Z,
-                                                 double *__restrict__ P, double *__restrict__ Xw, double *__restrict__ partial)
-{
-    iter_pass<2>(g, partial, [&](int64_t row, int64_t o, bool has1, it_v2 *acc) {
-        const it_v2 r = ld2(R + o);
-        it_v2 z = r;
-        if (JAC) {
-            z = r * dinv[row];
-            st2(Z + o, z, has1);
-        }
-        st2(P + o, z, has1);
-        st2(Xw + o, (it_v2){0.0, 0.0}, has1);
-        acc[0] += r * z;
-        acc[1] += r * r;
-    });
-}
-
-// BiCGStab start (r = b is in R): r^ = r, x = p = v = 0; partial sums of r.r twice (rho = r^.r = b.b)
-__global__ __launch_bounds__(256) void k_bi_init(PassGeom g, const double *__restrict__ R, double *__restrict__ RH, double *__restrict__ P,
-                                                 double *__restrict__ V, double *__restrict__ Xw, double *__restrict__ partial)
-{
-    iter_pass<2>(g, partial, [&](int64_t, int64_t o, bool has1, it_v2 *acc) {
-        const it_v2 r = ld2(R + o), zero = {0.0, 0.0};
-        st2(RH + o, r, has1);
-        st2(P + o, zero, has1);
-        st2(V + o, zero, has1);
-        st2(Xw + o, zero, has1);
-        acc[0] += r * r;
-        acc[1] += r * r;
-    });
-}
-
-// per-column inner products of one or two panel pairs: a1.b1 [, a2.b2]
-template <int NP>
-__global__ __launch_bounds__(256) void k_iter_dots(PassGeom g, const double *__restrict__ A1, const double *__restrict__ B1, const double *A2,
-                                                   const double *B2, double *__restrict__ partial)
-{
-    iter_pass<NP>(g, partial, [&](int64_t, int64_t o, bool, it_v2 *acc) {
-        acc[0] += ld2(A1 + o) * ld2(B1 + o);
-        if (NP == 2) acc[1] += ld2(A2 + o) * ld2(B2 + o);
-    });
-}
-
-// CG: x += alpha p, r -= alpha q, z = D^-1 r; partial sums of r.z and r.r
-template <bool JAC>
-__global__ __launch_bounds__(256) void k_cg_update(PassGeom g, const rails_iter_col *__restrict__ cols, const double *__restrict__ dinv,
-                                                   const double *__restrict__ P, const double *__restrict__ Q, double *__restrict__ Xw,
-                                                   double *__restrict__ R, double *__restrict__ Z, double *__restrict__ partial)
-{
-    ITER_COEF(alpha, alpha);
-    iter_pass<2>(g, partial, [&](int64_t row, int64_t o, bool has1, it_v2 *acc) {
-        const it_v2 x = axpy_sel(alpha, ld2(P + o), ld2(Xw + o));
-        const it_v2 r = axpy_sel(-alpha, ld2(Q + o), ld2(R + o));
-        st2(Xw + o, x, has1);
-        st2(R + o, r, has1);
-        it_v2 z = r;
-        if (JAC) {
-            z = r * dinv[row];
-            st2(Z + o, z, has1);
-        }
-        acc[0] += r * z;
-        acc[1] += r * r;
-    });
-}
-
-// CG: p = z + beta p (Z is R without the preconditioner)
-__global__ __launch_bounds__(256) void k_cg_dir(PassGeom g, const rails_iter_col *__restrict__ cols, const double *__restrict__ Z, double *__restrict__ P)
-{
-    ITER_COEF(beta, beta);
-    iter_pass<0>(g, nullptr, [&](int64_t, int64_t o, bool has1, it_v2 *) { st2(P + o, axpy_sel(beta, ld2(P + o), ld2(Z + o)), has1); });
-}
-
-// BiCGStab: p = r + beta (p - omega v), p^ = D^-1 p
-template <bool JAC>
-__global__ __launch_bounds__(256) void k_bi_dir(PassGeom g, const rails_iter_col *__restrict__ cols, const double *__restrict__ dinv,
-                                                const double *__restrict__ R, const double *__restrict__ V, double *__restrict__ P,
-                                                double *__restrict__ PH)
-{
-    ITER_COEF(beta, beta);
-    ITER_COEF(omega, omega);
-    iter_pass<0>(g, nullptr, [&](int64_t row, int64_t o, bool has1, it_v2 *) {
-        const it_v2 p = axpy_sel(beta, axpy_sel(-omega, ld2(V + o), ld2(P + o)), ld2(R + o));
-        st2(P + o, p, has1);
-        if (JAC) st2(PH + o, p * dinv[row], has1);
-    });
-}
-
-// BiCGStab: s = r - alpha v (kept in R), s^ = D^-1 s
-template <bool JAC>
-__global__ __launch_bounds__(256) void k_bi_s(PassGeom g, const rails_iter_col *__restrict__ cols, const double *__restrict__ dinv,
-                                              const double *__restrict__ V, double *__restrict__ R, double *__restrict__ SH)
-{
-    ITER_COEF(alpha, alpha);
-    iter_pass<0>(g, nullptr, [&](int64_t row, int64_t o, bool has1, it_v2 *) {
-        const it_v2 s = axpy_sel(-alpha, ld2(V + o), ld2(R + o));
-        st2(R + o, s, has1);
-        if (JAC) st2(SH + o, s * dinv[row], has1);
-    });
-}
-
-// BiCGStab: x += alpha p^ + omega s^, r = s - omega t; partial sums of r^.r and r.r.  Without the preconditioner PH is P and SH is R.
-__global__ __launch_bounds__(256) void k_bi_update(PassGeom g, const rails_iter_col *__restrict__ cols, const double *PH, const double *SH,
-                                                   const double *__restrict__ T, const double *__restrict__ RH, double *__restrict__ Xw, double *R,
-                                                   double *__restrict__ partial)
-{
-    ITER_COEF(alpha, alpha);
-    ITER_COEF(omega, omega);
-    iter_pass<2>(g, partial, [&](int64_t, int64_t o, bool has1, it_v2 *acc) {
-        const it_v2 x = axpy_sel(omega, ld2(SH + o), axpy_sel(alpha, ld2(PH + o), ld2(Xw + o)));
-        const it_v2 r = axpy_sel(-omega, ld2(T + o), ld2(R + o));
-        st2(Xw + o, x, has1);
-        st2(R + o, r, has1);
-        acc[0] += ld2(RH + o) * r;
-        acc[1] += r * r;
-    });
-}
-
-// ---- the Chebyshev polynomial preconditioner z = p_K(G A) G r (cheb_coef.h): G is the Jacobi diagonal's inverse (gvec) or the scalar gs
-// = +-1; the coefficients are the same for every column and come as kernel arguments ----
-
-__device__ __forceinline__ double cheb_g(const double *__restrict__ gvec, double gs, int64_t row) { return gvec ? gvec[row] : gs; }
-
-// d = z = (g r) / theta
-__global__ __launch_bounds__(256) void k_cheb_init(PassGeom g, const double *__restrict__ gvec, double gs, double theta, const double *__restrict__ R,
-                                                   double *__restrict__ D, double *__restrict__ Z)
-{
-    iter_pass<0>(g, nullptr, [&](int64_t row, int64_t o, bool has1, it_v2 *) {
-        const it_v2 d = (ld2(R + o) * cheb_g(gvec, gs, row)) / theta;
-        st2(D + o, d, has1);
-        st2(Z + o, d, has1);
-    });
-}
-
-// the unfused step, after Q = A z: d = a d + b g (r - q), z += d
-__global__ __launch_bounds__(256) void k_cheb_pass(PassGeom g, const double *__restrict__ gvec, double gs, double a, double b, const double *__restrict__ Q,
-                                                   const double *__restrict__ R, double *__restrict__ D, double *__restrict__ Z)
-{
-    iter_pass<0>(g, nullptr, [&](int64_t row, int64_t o, bool has1, it_v2 *) {
-        const it_v2 res = (ld2(R + o) - ld2(Q + o)) * cheb_g(gvec, gs, row);
-        const it_v2 d = ld2(D + o) * a + res * b;
-        st2(D + o, d, has1);
-        st2(Z + o, ld2(Z + o) + d, has1);
-    });
-}
-
-// The fused step for a stored CSR operator: t = (A Zin)_row by k_spmm_narrow's row gather (spmm.hip: LPR lanes own a row and two adjacent
-// columns each, 64 rows per block, the block's (col, val) run staged in LDS, 32-bit byte offsets; one entry at a time for a block whose run
-// is longer than the LDS buffer and for the lane of an odd last column), then in the same thread d = a d + b g (r - t) in place and
-// Zout = Zin + d.  Zin and Zout are different panels: every block reads rows of Zin that other blocks own.  All panels are work panels of
-// the object: window at column 0, one row stride, rows 16-byte aligned.  No atomics, no inner products.
-//
-// GHOST, a row-partitioned operator: column c >= m is row c - m of the operator's ghost buffer Zg (row stride ldg doubles), which the
-// object fills before the step with the rows of Zin the neighbours own (rails_halo_exchange, an even number of columns, so that ghost rows
-// are 16-byte aligned like panel rows) -- the select between two bases and two strides k_spmm_narrow<RPG, true, LPR> makes.  The epilogue
-// is the same: local rows only.
-#include "csr_row_gather.inc"
-
-template <int RPG, int LPR, bool GHOST>
-__global__ __launch_bounds__(256) void k_cheb_step_csr(int64_t m, const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
-                                                       const double *__restrict__ val, const double *__restrict__ Zin, int ld, int nc, int64_t blocks_per_xcd,
-                                                       const double *__restrict__ gvec, double gs, double a, double b, const double *__restrict__ R,
-                                                       double *__restrict__ D, double *__restrict__ Zout, const double *__restrict__ Zg, int ldg)
-{
-    csr_row_gather<RPG, LPR, GHOST>(m, rowptr, col, val, Zin, ld, nc, blocks_per_xcd, Zg, ldg, [&](int64_t row, int64_t o, it_v2 acc, bool full) {
-        // the epilogue on this thread's own two entries of the row (the pad column beside an odd last column is read, never written)
-        const it_v2 res = (ld2(R + o) - acc) * cheb_g(gvec, gs, row);
-        const it_v2 d = ld2(D + o) * a + res * b;
-        st2(D + o, d, full);
-        st2(Zout + o, ld2(Zin + o) + d, full);
-    });
-}
-
-// ---- the multigrid cycle's own kernels.  All panels are work panels: window at column 0, one row stride ld, rows
-// 16-byte aligned, a zeroed pad column beside an odd width ----
-
-// Q = R - A Z by the fused step's row gather
-template <int RPG, int LPR>
-__global__ __launch_bounds__(256) void k_amg_residual_csr(int64_t m, const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
-                                                          const double *__restrict__ val, const double *__restrict__ Z, int ld, int nc, int64_t blocks_per_xcd,
-                                                          const double *__restrict__ R, double *__restrict__ Q)
-{
-    csr_row_gather<RPG, LPR, false>(m, rowptr, col, val, Z, ld, nc, blocks_per_xcd, nullptr, 0,
-                                    [&](int64_t, int64_t o, it_v2 acc, bool full) { st2(Q + o, ld2(R + o) - acc, full); });
-}
-
-// the unfused residual, after Q = A Z: Q = R - Q
-__global__ __launch_bounds__(256) void k_amg_residual_pass(PassGeom g, const double *__restrict__ R, double *__restrict__ Q)
-{
-    iter_pass<0>(g, nullptr, [&](int64_t, int64_t o, bool has1, it_v2 *) { st2(Q + o, ld2(R + o) - ld2(Q + o), has1); });
-}
-
-// Z += P Zc in the passes' thread layout (a pair of columns per thread): a gather over the row of P, its entries added in stored order.
-// Rows of at most 8 entries -- all of them on a 2D grid -- load their entries and the rows of Zc they name first and add then; a longer
-// row (3D, wide bands: 13 to 26 entries) takes a plain loop.  The same sum either way.  Zc has the row stride of Z.
-__global__ __launch_bounds__(256) void k_amg_prolong_add(PassGeom g, const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
-                                                         const double *__restrict__ val, const double *__restrict__ Zc, double *__restrict__ Z)
-{
-    iter_pass<0>(g, nullptr, [&](int64_t row, int64_t o, bool has1, it_v2 *) {
-        const int c = (int)(o - row * g.ld);
-        const int64_t p0 = rowptr[row], p1 = rowptr[row + 1];
-        it_v2 acc = (it_v2){0.0, 0.0};
-        if (p1 - p0 <= 8) {
-            it_v2 x[8];
-            double av[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (p0 + u < p1) { // nothing is read past the end of the row: an empty row reads nothing at all
-                    av[u] = val[p0 + u];
-                    x[u] = ld2(Zc + (int64_t)col[p0 + u] * g.ld + c);
-                }
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (p0 + u < p1) {
-                    acc.x = __builtin_fma(av[u], x[u].x, acc.x);
-                    acc.y = __builtin_fma(av[u], x[u].y, acc.y);
-                }
-        } else {
-            for (int64_t q = p0; q < p1; ++q) {
-                const it_v2 x = ld2(Zc + (int64_t)col[q] * g.ld + c);
-                const double av = val[q];
-                acc.x = __builtin_fma(av, x.x, acc.x);
-                acc.y = __builtin_fma(av, x.y, acc.y);
-            }
-        }
-        st2(Z + o, ld2(Z + o) + acc, has1);
-    });
-}
-
-// Z = Ainv R on the last level: Ainv is n x n (n <= 1024), column-major; row i of the result adds Ainv(i, k) R(k, :) for k = 0 .. n - 1 in
-// that order.  The passes' thread layout, no atomics.
-__global__ __launch_bounds__(256) void k_amg_coarse_dense(PassGeom g, const double *__restrict__ Ainv, const double *__restrict__ R, double *__restrict__ Z)
-{
-    iter_pass<0>(g, nullptr, [&](int64_t row, int64_t o, bool has1, it_v2 *) {
-        const int c = (int)(o - row * g.ld);
-        it_v2 acc = (it_v2){0.0, 0.0};
-        for (int64_t k = 0; k < g.m; ++k) {
-            const double av = Ainv[row + k * g.m];
-            const it_v2 x = ld2(R + k * g.ld + c);
-            acc.x = __builtin_fma(av, x.x, acc.x);
-            acc.y = __builtin_fma(av, x.y, acc.y);
-        }
-        st2(Z + o, acc, has1);
-    });
-}
-
-// CG with the polynomial, start (r = b in R, z = p(A) r in Z): p = z, x = 0; partial sums of r.z and r.r
-__global__ __launch_bounds__(256) void k_cg_init_poly(PassGeom g, const double *__restrict__ R, const double *__restrict__ Z, double *__restrict__ P,
-                                                      double *__restrict__ Xw, double *__restrict__ partial)
-{
-    iter_pass<2>(g, partial, [&](int64_t, int64_t o, bool has1, it_v2 *acc) {
-        const it_v2 r = ld2(R + o), z = ld2(Z + o);
-        st2(P + o, z, has1);
-        st2(Xw + o, (it_v2){0.0, 0.0}, has1);
-        acc[0] += r * z;
-        acc[1] += r * r;
-    });
-}
-
-// sums[e] = sum over the blocks of partial[block][e], e < n <= 64, in a fixed order: 16 interleaved strands, then the strands 0..15
-__device__ __forceinline__ void iter_reduce(const double *__restrict__ partial, int64_t nslab, int n, double *sums)
-{
-    __shared__ double sh[16][64];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    double s = 0.0;
-    if (tx < n)
-        for (int64_t t = ty; t < nslab; t += 16) s += partial[t * n + tx];
-    sh[ty][tx] = s;
-    __syncthreads();
-    if (ty == 0) {
-        double r = 0.0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) r += sh[k][tx];
-        sums[tx] = tx < n ? r : 0.0;
-    }
-    __syncthreads();
-}
-
-// the scalar step of column j from the reduced sums (q0 = sums[j], q1 = sums[ncw + j])
-__device__ __forceinline__ void iter_compute(int step, rails_iter_col &c, double q0, double q1, double tol2, int maxit, double sign)
-{
-    switch (step) {
-    case STEP_CG_INIT: rails_iter_start(c, q1, q0, maxit); break;
-    case STEP_CG_ALPHA: rails_iter_cg_alpha(c, q0, sign); break;
-    case STEP_CG_BETA: rails_iter_cg_beta(c, q0, q1, tol2, maxit); break;
-    case STEP_BI_INIT: rails_iter_start(c, q1, q0, maxit); break;
-    case STEP_BI_ALPHA: rails_iter_bi_alpha(c, q0); break;
-    case STEP_BI_OMEGA: rails_iter_bi_omega(c, q0, q1); break;
-    default: rails_iter_bi_end(c, q0, q1, tol2, maxit); break;
-    }
-}
-
-// the columns' scalar step from the reduced sums, then the count (thread 0 of the one workgroup)
-__device__ __forceinline__ void iter_columns(int step, const double *sums, int ncw, int nq, rails_iter_col *cols, int32_t *status, double tol2, int maxit,
-                                             double sign)
-{
-    if ((int)threadIdx.x < ncw) {
-        rails_iter_col c = cols[threadIdx.x];
-        iter_compute(step, c, sums[threadIdx.x], nq == 2 ? sums[ncw + threadIdx.x] : 0.0, tol2, maxit, sign);
-        cols[threadIdx.x] = c;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && (step == STEP_CG_INIT || step == STEP_BI_INIT || step == STEP_CG_BETA || step == STEP_BI_END)) {
-        int active = 0, bad = 0;
-        for (int j = 0; j < ncw; ++j) {
-            active += (cols[j].flags & RAILS_ITER_ACTIVE) ? 1 : 0;
-            bad += (cols[j].flags & RAILS_ITER_NONFINITE) ? 1 : 0;
-        }
-        status[0] = active;
-        if (step == STEP_CG_INIT || step == STEP_BI_INIT) status[1] = bad;
-    }
-}
-
-// one workgroup: reduce, compute, count.  status[0] = active columns, status[1] = columns whose right-hand side is not finite (start only)
-__global__ __launch_bounds__(1024) void k_iter_scalars(int step, const double *__restrict__ partial, int64_t nslab, int ncw, int nq,
-                                                       rails_iter_col *cols, int32_t *status, double tol2, int maxit, double sign)
-{
-    __shared__ double sums[64];
-    iter_reduce(partial, nslab, nq * ncw, sums);
-    iter_columns(step, sums, ncw, nq, cols, status, tol2, maxit, sign);
-}
-
-// The scalar step of a context that reduces (a row partition, an all-reduce hook, a communicator), in three stream-ordered steps:
-// k_iter_reduce sums this rank's partial sums exactly as k_iter_scalars does and writes the nq * ncw <= 64 sums to a buffer of the
-// object, rails_allreduce_dev adds them over the ranks, k_iter_compute goes on from there.  Every rank then computes from the same sums,
-// so the columns' scalars, flags and the active count are the same bits on every rank.
-__global__ __launch_bounds__(1024) void k_iter_reduce(const double *__restrict__ partial, int64_t nslab, int n, double *__restrict__ out)
-{
-    __shared__ double sums[64];
-    iter_reduce(partial, nslab, n, sums);
-    if ((int)threadIdx.x < n) out[threadIdx.x] = sums[threadIdx.x];
-}
-
-__global__ __launch_bounds__(64) void k_iter_compute(int step, const double *__restrict__ sums, int ncw, int nq, rails_iter_col *cols, int32_t *status,
-                                                     double tol2, int maxit, double sign)
-{
-    iter_columns(step, sums, ncw, nq, cols, status, tol2, maxit, sign);
-}
+#include "iter_kernels.inc"
 
 // CG: x r p q [z]; BiCGStab: x r p v(=Q) [p^(=Z)] r^ t [s^]; the polynomial: z, its direction d, the second z of the fused step's ping-pong
 enum { W_X = 0, W_R, W_P, W_Q, W_Z, W_RH, W_T, W_SH, W_D, W_Z2, W_COUNT };
 
 // The multigrid hierarchy on the device (amg_host.h builds it on the host).  Level 0 works in the object's own work panels (r = W_R, z =
 // W_Z / W_Z2, d = W_D, q = W_Q) on the object's operator; the levels below own their operators and five panels of the same row stride;
-// the last matrix is its dense inverse with two panels (none when there is no level: W_R and W_Z then).
+// the last matrix is its dense inverse with two panels (none when there is no level: W_R and W_Z then).  A call reaches every level's
+// panels through its Sweep (plan_call), level 0's like the others.
 enum { L_R = 0, L_Z, L_Z2, L_D, L_Q, L_COUNT };
 struct AmgLevel {
     int64_t n = 0, nnz = 0;
@@ -649,6 +239,22 @@ int grow_cols(rails_ctx *c, rails_iter *it, int nc)
     return RAILS_OK;
 }
 
+// A Chebyshev sweep on an operator: z = p(G A) G r by d = z = G r / theta, then steps d = a d + b G (r - A z), z += d.  The polynomial
+// preconditioner is one sweep on the object's operator in the object's panels; the multigrid cycle smooths with one per level.  What does
+// not depend on the group is filled in by plan_call, the geometry by plan_group.
+struct Sweep {
+    rails_csr *A;
+    int64_t n;
+    const double *gvec; // G: the inverse of a diagonal, or the scalar gs = +-1 where this is null
+    double gs;
+    rails_panel *r, *z[2], *d, *q; // z[0] holds the result; z[1] is the other panel of the fused step's ping-pong, q holds A z unfused
+    bool fused = false, ghost = false; // ghost: the fused step in its ghost-row form, with an exchange of the object's own before it
+    double theta = 1.0, a[RAILS_CHEB_MAX_DEGREE], b[RAILS_CHEB_MAX_DEGREE];
+    PassGeom g;
+    int64_t slabs = 0;
+    int at = 0; // the z panel that holds z now
+};
+
 struct Run {
     rails_ctx *c;
     rails_iter *it;
@@ -658,272 +264,213 @@ struct Run {
     rails_iter_col *cols;
     bool jac;
     double tol2;
-    // the polynomial: degree (0: off), theta and the coefficient pairs, whether its steps run on the fused kernel
+    // the preconditioner beyond Jacobi: the polynomial's degree (0: off) or the multigrid cycle (K is 0 then); sw[0] is the polynomial's
+    // sweep, or sw[l] the smoother of level l; the last level's passes run on gc
     int K = 0;
-    bool fused = false, ghost = false; // ghost: the fused step in its ghost-row form, with an exchange of the object's own before it
-    double theta = 1.0, ca[RAILS_CHEB_MAX_DEGREE], cb[RAILS_CHEB_MAX_DEGREE];
-    bool amg = false; // the multigrid cycle is the preconditioner (K is 0 then)
+    bool amg = false, other = false; // other: K > 0 or amg
+    bool cycle = false;              // inside a cycle: the cycle's counters count too
+    Sweep sw[RAILS_AMG_MAX_LEVELS]; // (about 1 KB each, 17 KB on the stack of a call: one struct for the polynomial, degree up to 64, and the levels, up to 8)
+    PassGeom gc;
+    int64_t slabs_c = 0;
 
     double *d(int k) const { return it->w[k]->d; }
+    // every kernel of the object is launched, and counted, here
+    template <class Kern, class... Args>
+    void launch(Kern kernel, int64_t blocks, int threads, Args... args)
+    {
+        RAILS_LAUNCH(kernel, dim3((unsigned)blocks), dim3((unsigned)threads), 0, c->stream, args...);
+        it->last_launches++;
+        if (cycle) it->last_cycle_launches++;
+    }
+    void count_product()
+    {
+        it->last_products++;
+        if (cycle) it->last_cycle_products++;
+    }
+    // a pass on the geometry pg, one block per slab
+    template <class Kern, class... Args>
+    void pass(const PassGeom &pg, int64_t slabs, Kern kernel, Args... args)
+    {
+        launch(kernel, slabs, 256, pg, args...);
+    }
+    // a pass of the group that writes partial sums: they go to the context workspace, the kernel's last argument
+    template <class Kern, class... Args>
+    int pass_sums(Kern kernel, Args... args)
+    {
+        RAILS_TRY(rails_ws_reserve(c, (size_t)nslab * 2 * g.ncw * sizeof(double)));
+        pass(g, nslab, kernel, args..., c->ws);
+        return RAILS_OK;
+    }
+    // a kernel on the shared row gather in its 8-lane form up to 16 columns, in its 16-lane form above
+    template <class Kern>
+    Kern lanes(Kern k8, Kern k16) const
+    {
+        return g.ncw <= 16 ? k8 : k16;
+    }
+    // such a kernel over a sweep's matrix: 64 rows per block, the blocks dealt over the 8 XCDs.  `rest` is what follows the gather's own
+    // arguments.  One product.
+    template <class Kern, class... Rest>
+    void gather(Kern kernel, const Sweep &s, const double *zin, Rest... rest)
+    {
+        const int64_t bpx = ((s.n + 63) / 64 + 7) / 8;
+        launch(kernel, bpx * 8, 256, s.n, s.A->rowptr, s.A->col, s.A->val, zin, g.ld, g.ncw, bpx, rest...);
+        count_product();
+    }
     int scalars(int step, int nq)
     {
         // (with the polynomial r.z carries the sign of the operator itself, as with Jacobi)
-        const double sign = (jac || K > 0 || amg) ? 1.0 : it->defsign;
+        const double sign = (jac || other) ? 1.0 : it->defsign;
         if (!it->reduces) {
-            RAILS_LAUNCH(k_iter_scalars, dim3(1), dim3(1024), 0, c->stream, step, c->ws, nslab, g.ncw, nq, cols, it->status_dev, tol2, it->maxit, sign);
-            it->last_launches++;
+            launch(k_iter_scalars, 1, 1024, step, c->ws, nslab, g.ncw, nq, cols, it->status_dev, tol2, it->maxit, sign);
             return RAILS_OK;
         }
-        RAILS_LAUNCH(k_iter_reduce, dim3(1), dim3(1024), 0, c->stream, c->ws, nslab, nq * g.ncw, it->sums_dev);
+        launch(k_iter_reduce, 1, 1024, c->ws, nslab, nq * g.ncw, it->sums_dev);
         RAILS_TRY(rails_allreduce_dev(c, it->sums_dev, (size_t)(nq * g.ncw)));
         it->last_allreduces++;
-        RAILS_LAUNCH(k_iter_compute, dim3(1), dim3(64), 0, c->stream, step, it->sums_dev, g.ncw, nq, cols, it->status_dev, tol2, it->maxit, sign);
-        it->last_launches += 2;
+        launch(k_iter_compute, 1, 64, step, it->sums_dev, g.ncw, nq, cols, it->status_dev, tol2, it->maxit, sign);
         return RAILS_OK;
     }
-    int product(int from, int to)
+    int product(rails_csr *A, int tr, rails_panel *from, rails_panel *to)
     {
-        it->last_products++;
-        return rails_spmm(c, it->A, it->method == RAILS_ITER_CG ? 0 : trans, it->w[from], 0, g.ncw, it->w[to], 0); // CG: a symmetric operator
+        count_product();
+        return rails_spmm(c, A, tr, from, 0, g.ncw, to, 0);
     }
+    int product(int from, int to) { return product(it->A, it->method == RAILS_ITER_CG ? 0 : trans, it->w[from], it->w[to]); } // CG: a symmetric operator
     int dots(int np, int a1, int b1, int a2, int b2)
     {
-        RAILS_TRY(rails_ws_reserve(c, (size_t)nslab * 2 * g.ncw * sizeof(double)));
-        if (np == 1)
-            RAILS_LAUNCH((k_iter_dots<1>), dim3((unsigned)nslab), dim3(256), 0, c->stream, g, d(a1), d(b1), d(a1), d(b1), c->ws);
-        else
-            RAILS_LAUNCH((k_iter_dots<2>), dim3((unsigned)nslab), dim3(256), 0, c->stream, g, d(a1), d(b1), d(a2), d(b2), c->ws);
-        it->last_launches++;
         it->last_dots += np * g.ncw;
+        return pass_sums(np == 1 ? k_iter_dots<1> : k_iter_dots<2>, d(a1), d(b1), d(a2), d(b2));
+    }
+
+    // ---- the sweep.  The fused steps read one z panel and write the other, and start in the one that makes the last of them write z[0]
+    // (rails_cheb_start_panel); the unfused ones work in z[0] with A z in q.
+    void sweep_start(Sweep &s, int steps)
+    {
+        s.at = rails_cheb_start_panel(s.fused, steps);
+        pass(s.g, s.slabs, k_cheb_init, s.gvec, s.gs, s.theta, s.r->d, s.d->d, s.z[s.at]->d);
+    }
+    int sweep_step(Sweep &s, double a, double b)
+    {
+        rails_panel *zin = s.z[s.at];
+        if (!s.fused) {
+            RAILS_TRY(product(s.A, 0, zin, s.q));
+            pass(s.g, s.slabs, k_cheb_pass, s.gvec, s.gs, a, b, s.q->d, s.r->d, s.d->d, zin->d);
+            return RAILS_OK;
+        }
+        int nce = 0;
+        if (s.ghost) {
+            // one exchange per step, as the unfused step's rails_spmm makes one: ranks that choose differently stay in step.  An even
+            // number of columns, so that ghost rows are as aligned as panel rows: at an odd width the panel's column ncw travels too.
+            // That is the pad column (zeroed at allocation, never written) when the group is as wide as the panels, and a column a
+            // wider group has used otherwise; on the receiving side nobody reads it, since the lane of an odd last column takes its
+            // one-entry path -- what it holds reaches no result, as with the pair loads of every pass (section 14's last test)
+            nce = (g.ncw + 1) & ~1;
+            RAILS_TRY(rails_halo_exchange(c, s.A, zin->d, g.ld, nce));
+            it->last_halo++;
+        }
+        s.at ^= 1;
+        gather(s.ghost ? lanes(k_cheb_step_csr<2, 8, true>, k_cheb_step_csr<4, 16, true>) : lanes(k_cheb_step_csr<2, 8, false>, k_cheb_step_csr<4, 16, false>), s, zin->d, s.gvec,
+               s.gs, a, b, (const double *)s.r->d, s.d->d, s.z[s.at]->d, (const double *)(s.ghost ? s.A->ext : nullptr), nce);
+        it->last_fused++;
         return RAILS_OK;
     }
-#define ITER_PASS_LAUNCH(kernel_jac, kernel_plain, ...)                                                                                      \
-    do {                                                                                                                                     \
-        RAILS_TRY(rails_ws_reserve(c, (size_t)nslab * 2 * g.ncw * sizeof(double)));                                                          \
-        if (jac)                                                                                                                             \
-            RAILS_LAUNCH(kernel_jac, dim3((unsigned)nslab), dim3(256), 0, c->stream, __VA_ARGS__);                                          \
-        else                                                                                                                                 \
-            RAILS_LAUNCH(kernel_plain, dim3((unsigned)nslab), dim3(256), 0, c->stream, __VA_ARGS__);                                        \
-        it->last_launches++;                                                                                                                 \
-    } while (0)
-
-    // W_Z = p_K(G A) G W_R (K = 0: G W_R).  The fused steps read one z panel and write the other, and start in the one that makes the
-    // last of them write W_Z; the unfused ones work in W_Z with A z in W_Q.
+    // W_Z = p_K(G A) G W_R (K = 0: G W_R)
     int polynomial()
     {
-        const double *gvec = jac ? it->dinv : nullptr;
-        const double gs = it->defsign;
-        const dim3 grid((unsigned)nslab), block(256);
-        int zin = (fused && (K & 1)) ? W_Z2 : W_Z;
-        RAILS_LAUNCH(k_cheb_init, grid, block, 0, c->stream, g, gvec, gs, theta, d(W_R), d(W_D), d(zin));
-        it->last_launches++;
         it->last_poly++;
-        const rails_csr *A = it->A;
-        const int64_t bpx = ((it->m + 63) / 64 + 7) / 8;
-        for (int k = 0; k < K; ++k) {
-            if (!fused) {
-                RAILS_TRY(product(W_Z, W_Q));
-                RAILS_LAUNCH(k_cheb_pass, grid, block, 0, c->stream, g, gvec, gs, ca[k], cb[k], d(W_Q), d(W_R), d(W_D), d(W_Z));
-                it->last_launches++;
-                continue;
-            }
-            const int zout = zin == W_Z ? W_Z2 : W_Z;
-            if (ghost) {
-                // one exchange per step, as the unfused step's rails_spmm makes one: ranks that choose differently stay in step.  An even
-                // number of columns, so that ghost rows are as aligned as panel rows: at an odd width the panel's column ncw travels too.
-                // That is the pad column (zeroed at allocation, never written) when the group is as wide as the panels, and a column a
-                // wider group has used otherwise; on the receiving side nobody reads it, since the lane of an odd last column takes its
-                // one-entry path -- what it holds reaches no result, as with the pair loads of every pass (section 14's last test)
-                const int nce = (g.ncw + 1) & ~1;
-                RAILS_TRY(rails_halo_exchange(c, it->A, d(zin), g.ld, nce));
-                it->last_halo++;
-                if (g.ncw <= 16)
-                    RAILS_LAUNCH((k_cheb_step_csr<2, 8, true>), dim3((unsigned)(bpx * 8)), block, 0, c->stream, it->m, A->rowptr, A->col, A->val, d(zin), g.ld,
-                                 g.ncw, bpx, gvec, gs, ca[k], cb[k], d(W_R), d(W_D), d(zout), A->ext, nce);
-                else
-                    RAILS_LAUNCH((k_cheb_step_csr<4, 16, true>), dim3((unsigned)(bpx * 8)), block, 0, c->stream, it->m, A->rowptr, A->col, A->val, d(zin), g.ld,
-                                 g.ncw, bpx, gvec, gs, ca[k], cb[k], d(W_R), d(W_D), d(zout), A->ext, nce);
-            } else if (g.ncw <= 16)
-                RAILS_LAUNCH((k_cheb_step_csr<2, 8, false>), dim3((unsigned)(bpx * 8)), block, 0, c->stream, it->m, A->rowptr, A->col, A->val, d(zin), g.ld, g.ncw, bpx,
-                             gvec, gs, ca[k], cb[k], d(W_R), d(W_D), d(zout), nullptr, 0);
-            else
-                RAILS_LAUNCH((k_cheb_step_csr<4, 16, false>), dim3((unsigned)(bpx * 8)), block, 0, c->stream, it->m, A->rowptr, A->col, A->val, d(zin), g.ld, g.ncw, bpx,
-                             gvec, gs, ca[k], cb[k], d(W_R), d(W_D), d(zout), nullptr, 0);
-            it->last_launches++;
-            it->last_products++;
-            it->last_fused++;
-            zin = zout;
-        }
+        sweep_start(sw[0], K);
+        for (int k = 0; k < K; ++k) RAILS_TRY(sweep_step(sw[0], sw[0].a[k], sw[0].b[k]));
         return RAILS_OK;
     }
     // ---- the multigrid V-cycle: W_Z = M W_R.  Down: smooth from zero, residual, restrict; the dense inverse at
-    // the bottom; up: prolong and correct, smooth from z.  Nothing in here synchronises, allocates or reads back.
-    rails_panel *lpanel(int l, int which) const
-    {
-        static const int own[L_COUNT] = {W_R, W_Z, W_Z2, W_D, W_Q};
-        return l == 0 ? it->w[own[which]] : it->hier->lv[(size_t)l].w[which];
-    }
-    double *lp(int l, int which) const { return lpanel(l, which)->d; }
-    // a kernel on the shared row gather over level L's matrix: 64 rows per block, the blocks dealt over the 8 XCDs; its 8-lane form up to
-    // 16 columns, its 16-lane form above.  `rest` is what follows the gather's own arguments.
-    template <class K8, class K16, class... Rest>
-    void launch_gather(K8 k8, K16 k16, const AmgLevel &L, const double *zin, Rest... rest)
-    {
-        const int64_t bpx = ((L.n + 63) / 64 + 7) / 8;
-        if (g.ncw <= 16)
-            RAILS_LAUNCH(k8, dim3((unsigned)(bpx * 8)), dim3(256), 0, c->stream, L.n, L.A->rowptr, L.A->col, L.A->val, zin, g.ld, g.ncw, bpx, rest...);
-        else
-            RAILS_LAUNCH(k16, dim3((unsigned)(bpx * 8)), dim3(256), 0, c->stream, L.n, L.A->rowptr, L.A->col, L.A->val, zin, g.ld, g.ncw, bpx, rest...);
-    }
-    // the passes' geometry on n rows (set_group's rule)
-    void level_geom(int64_t n, PassGeom *lg, int64_t *slabs) const
-    {
-        const int TY = 256 >> g.tx_bits;
-        int64_t ns = std::max<int64_t>(1, std::min<int64_t>(1024, n / ((int64_t)TY * 8)));
-        const int64_t rps = (n + ns - 1) / ns;
-        *slabs = (n + rps - 1) / rps;
-        *lg = PassGeom{g.ncw, g.ld, g.tx_bits, n, rps};
-    }
-    void count_cycle(long launches, long products)
-    {
-        it->last_launches += launches;
-        it->last_cycle_launches += launches;
-        it->last_products += products;
-        it->last_cycle_products += products;
-    }
-    // one smoother step on level l: d = a d + b g (r - A z), z += d; *z names the panel that holds z and follows the fused step's ping-pong
-    int smooth_step(int l, bool lfused, const PassGeom &lg, int64_t slabs, double a, double b, int *z)
-    {
-        const AmgLevel &L = it->hier->lv[(size_t)l];
-        if (!lfused) {
-            RAILS_TRY(rails_spmm(c, L.A, 0, lpanel(l, *z), 0, g.ncw, lpanel(l, L_Q), 0));
-            RAILS_LAUNCH(k_cheb_pass, dim3((unsigned)slabs), dim3(256), 0, c->stream, lg, L.dinv, 1.0, a, b, lp(l, L_Q), lp(l, L_R), lp(l, L_D), lp(l, *z));
-            count_cycle(1, 1);
-            return RAILS_OK;
-        }
-        const int zout = *z == L_Z ? L_Z2 : L_Z;
-        launch_gather(k_cheb_step_csr<2, 8, false>, k_cheb_step_csr<4, 16, false>, L, lp(l, *z), (const double *)L.dinv, 1.0, a, b, (const double *)lp(l, L_R), lp(l, L_D),
-                      lp(l, zout), (const double *)nullptr, 0);
-        count_cycle(1, 1);
-        it->last_fused++;
-        *z = zout;
-        return RAILS_OK;
-    }
+    // the bottom; up: prolong and correct, smooth from z.  Nothing in here synchronises, allocates, reads back or refuses: the
+    // coefficients, the choice of the fused step and the geometry of every level are the plan of the call.
     int vcycle()
     {
         Amg &H = *it->hier;
         const int nl = (int)H.lv.size(), S = it->amg_degree;
-        int zat[RAILS_AMG_MAX_LEVELS];
-        bool lfused[RAILS_AMG_MAX_LEVELS];
-        double th[RAILS_AMG_MAX_LEVELS], a[9], b[9];
         it->last_cycles++;
         for (int l = 0; l < nl; ++l) {
-            const AmgLevel &L = H.lv[(size_t)l];
-            PassGeom lg;
-            int64_t slabs;
-            level_geom(L.n, &lg, &slabs);
-            RAILS_REQUIRE(rails_cheb_coef(L.hi / it->amg_ratio, L.hi, S, &th[l], a, b), "rails_iter: no smoother of degree %d on [%g, %g] (level %d)", S, L.hi / it->amg_ratio, L.hi, l);
-            lfused[l] = it->poly_fused && rails_cheb_fused_eligible(true, 0, L.n, g.ld);
-            // every fused step moves z to the other panel, and there are 2 S + 1 of them: the top level starts where its last one writes W_Z
-            zat[l] = lfused[l] ? L_Z2 : L_Z;
-            RAILS_LAUNCH(k_cheb_init, dim3((unsigned)slabs), dim3(256), 0, c->stream, lg, L.dinv, 1.0, th[l], lp(l, L_R), lp(l, L_D), lp(l, zat[l]));
-            count_cycle(1, 0);
-            for (int k = 0; k < S; ++k) RAILS_TRY(smooth_step(l, lfused[l], lg, slabs, a[k], b[k], &zat[l]));
-            if (lfused[l]) {
-                launch_gather(k_amg_residual_csr<2, 8>, k_amg_residual_csr<4, 16>, L, lp(l, zat[l]), (const double *)lp(l, L_R), lp(l, L_Q));
+            Sweep &s = sw[l];
+            sweep_start(s, 2 * S + 1); // S steps here, 1 + S on the way up
+            for (int k = 0; k < S; ++k) RAILS_TRY(sweep_step(s, s.a[k], s.b[k]));
+            rails_panel *z = s.z[s.at];
+            if (s.fused) {
+                gather(lanes(k_amg_residual_csr<2, 8>, k_amg_residual_csr<4, 16>), s, z->d, (const double *)s.r->d, s.q->d);
             } else {
-                RAILS_TRY(rails_spmm(c, L.A, 0, lpanel(l, zat[l]), 0, g.ncw, lpanel(l, L_Q), 0));
-                RAILS_LAUNCH(k_amg_residual_pass, dim3((unsigned)slabs), dim3(256), 0, c->stream, lg, lp(l, L_R), lp(l, L_Q));
+                RAILS_TRY(product(s.A, 0, z, s.q));
+                pass(s.g, s.slabs, k_amg_residual_pass, s.r->d, s.q->d);
             }
-            count_cycle(1, 1);
-            RAILS_TRY(rails_spmm(c, L.R, 0, lpanel(l, L_Q), 0, g.ncw, l + 1 < nl ? lpanel(l + 1, L_R) : H.rc, 0)); // r_{l+1} = P' q
-            count_cycle(0, 1);
+            RAILS_TRY(product(H.lv[(size_t)l].R, 0, s.q, l + 1 < nl ? sw[l + 1].r : H.rc)); // r_{l+1} = P' q
         }
-        {
-            PassGeom lg;
-            int64_t slabs;
-            level_geom(H.n_coarse, &lg, &slabs);
-            RAILS_LAUNCH(k_amg_coarse_dense, dim3((unsigned)slabs), dim3(256), 0, c->stream, lg, H.Ainv, nl ? H.rc->d : d(W_R), nl ? H.zc->d : d(W_Z));
-            count_cycle(1, 0);
-        }
+        pass(gc, slabs_c, k_amg_coarse_dense, H.Ainv, nl ? H.rc->d : d(W_R), nl ? H.zc->d : d(W_Z));
         for (int l = nl - 1; l >= 0; --l) {
-            const AmgLevel &L = H.lv[(size_t)l];
-            PassGeom lg;
-            int64_t slabs;
-            level_geom(L.n, &lg, &slabs);
-            const double *below = l + 1 < nl ? lp(l + 1, zat[l + 1]) : H.zc->d;
-            RAILS_LAUNCH(k_amg_prolong_add, dim3((unsigned)slabs), dim3(256), 0, c->stream, lg, L.P->rowptr, L.P->col, L.P->val, below, lp(l, zat[l]));
-            count_cycle(1, 1);
+            Sweep &s = sw[l];
+            const rails_csr *P = H.lv[(size_t)l].P;
+            pass(s.g, s.slabs, k_amg_prolong_add, P->rowptr, P->col, P->val, l + 1 < nl ? sw[l + 1].z[0]->d : H.zc->d, s.z[s.at]->d);
+            count_product();
             // the post-smoother from z, the adjoint of the pre-smoother: one step with (a, b) = (0, 1 / theta) -- d is finite, k_cheb_init wrote
-            // it whatever S is -- then S steps with the recurrence's coefficients (recomputed: a and b above held the last level's)
-            rails_cheb_coef(L.hi / it->amg_ratio, L.hi, S, &th[l], a, b);
-            RAILS_TRY(smooth_step(l, lfused[l], lg, slabs, 0.0, 1.0 / th[l], &zat[l]));
-            for (int k = 0; k < S; ++k) RAILS_TRY(smooth_step(l, lfused[l], lg, slabs, a[k], b[k], &zat[l]));
+            // it whatever S is -- then S steps with the recurrence's coefficients.  It ends in z[0], where the level above looks for it.
+            RAILS_TRY(sweep_step(s, 0.0, 1.0 / s.theta));
+            for (int k = 0; k < S; ++k) RAILS_TRY(sweep_step(s, s.a[k], s.b[k]));
         }
-        return RAILS_OK; // (zat[0] is L_Z again: an odd number of fused steps from L_Z2, or no move at all)
+        return RAILS_OK;
     }
-    int precondition() { return amg ? vcycle() : polynomial(); }
+    int precondition()
+    {
+        cycle = amg; // (off again however the cycle ends)
+        const int rc = amg ? vcycle() : polynomial();
+        cycle = false;
+        return rc;
+    }
     int start()
     {
-        if (it->method == RAILS_ITER_CG && (K > 0 || amg)) {
+        if (it->method != RAILS_ITER_CG) {
+            RAILS_TRY(pass_sums(k_bi_init, d(W_R), d(W_RH), d(W_P), d(W_Q), d(W_X)));
+            it->last_dots += 2 * g.ncw;
+            return scalars(STEP_BI_INIT, 2);
+        }
+        if (other) {
             RAILS_TRY(precondition());
-            RAILS_TRY(rails_ws_reserve(c, (size_t)nslab * 2 * g.ncw * sizeof(double)));
-            RAILS_LAUNCH(k_cg_init_poly, dim3((unsigned)nslab), dim3(256), 0, c->stream, g, d(W_R), d(W_Z), d(W_P), d(W_X), c->ws);
-            it->last_launches++;
-            it->last_dots += 2 * g.ncw;
-            return scalars(STEP_CG_INIT, 2);
-        }
-        if (it->method == RAILS_ITER_CG) {
-            ITER_PASS_LAUNCH((k_cg_init<true>), (k_cg_init<false>), g, it->dinv, d(W_R), jac ? d(W_Z) : nullptr, d(W_P), d(W_X), c->ws);
-            it->last_dots += 2 * g.ncw;
-            return scalars(STEP_CG_INIT, 2);
-        }
-        ITER_PASS_LAUNCH(k_bi_init, k_bi_init, g, d(W_R), d(W_RH), d(W_P), d(W_Q), d(W_X), c->ws);
+            RAILS_TRY(pass_sums(k_cg_init_poly, d(W_R), d(W_Z), d(W_P), d(W_X)));
+        } else
+            RAILS_TRY(pass_sums(jac ? k_cg_init<true> : k_cg_init<false>, it->dinv, d(W_R), jac ? d(W_Z) : nullptr, d(W_P), d(W_X)));
         it->last_dots += 2 * g.ncw;
-        return scalars(STEP_BI_INIT, 2);
+        return scalars(STEP_CG_INIT, 2);
     }
     int iteration()
     {
-        if (it->method == RAILS_ITER_CG && (K > 0 || amg)) {
-            // the update without its own z (its partial sums are overwritten below), the polynomial, then r.z and r.r in the layout
-            // the scalar step reads; K products in a row without an inner product, a scalar kernel or a read-back between them
-            RAILS_TRY(product(W_P, W_Q));
-            RAILS_TRY(dots(1, W_P, W_Q, W_P, W_Q));
-            RAILS_TRY(scalars(STEP_CG_ALPHA, 1));
-            RAILS_LAUNCH((k_cg_update<false>), dim3((unsigned)nslab), dim3(256), 0, c->stream, g, cols, it->dinv, d(W_P), d(W_Q), d(W_X), d(W_R), nullptr, c->ws);
-            it->last_launches++;
-            RAILS_TRY(precondition());
-            RAILS_TRY(dots(2, W_R, W_Z, W_R, W_R));
-            RAILS_TRY(scalars(STEP_CG_BETA, 2));
-            RAILS_LAUNCH(k_cg_dir, dim3((unsigned)nslab), dim3(256), 0, c->stream, g, cols, d(W_Z), d(W_P));
-            it->last_launches++;
-            return RAILS_OK;
-        }
         if (it->method == RAILS_ITER_CG) {
-            const int z = jac ? W_Z : W_R;
             RAILS_TRY(product(W_P, W_Q));
             RAILS_TRY(dots(1, W_P, W_Q, W_P, W_Q));
             RAILS_TRY(scalars(STEP_CG_ALPHA, 1));
-            ITER_PASS_LAUNCH((k_cg_update<true>), (k_cg_update<false>), g, cols, it->dinv, d(W_P), d(W_Q), d(W_X), d(W_R), jac ? d(W_Z) : nullptr, c->ws);
-            it->last_dots += 2 * g.ncw;
+            if (other) {
+                // the update without its own z (its partial sums are overwritten below), the polynomial, then r.z and r.r in the layout
+                // the scalar step reads; K products in a row without an inner product, a scalar kernel or a read-back between them
+                RAILS_TRY(pass_sums(k_cg_update<false>, cols, it->dinv, d(W_P), d(W_Q), d(W_X), d(W_R), nullptr));
+                RAILS_TRY(precondition());
+                RAILS_TRY(dots(2, W_R, W_Z, W_R, W_R));
+            } else {
+                RAILS_TRY(pass_sums(jac ? k_cg_update<true> : k_cg_update<false>, cols, it->dinv, d(W_P), d(W_Q), d(W_X), d(W_R), jac ? d(W_Z) : nullptr));
+                it->last_dots += 2 * g.ncw;
+            }
             RAILS_TRY(scalars(STEP_CG_BETA, 2));
-            ITER_PASS_LAUNCH(k_cg_dir, k_cg_dir, g, cols, d(z), d(W_P));
+            pass(g, nslab, k_cg_dir, cols, d(other || jac ? W_Z : W_R), d(W_P));
             return RAILS_OK;
         }
         const int ph = jac ? W_Z : W_P, sh = jac ? W_SH : W_R;
-        ITER_PASS_LAUNCH((k_bi_dir<true>), (k_bi_dir<false>), g, cols, it->dinv, d(W_R), d(W_Q), d(W_P), jac ? d(W_Z) : nullptr);
+        pass(g, nslab, jac ? k_bi_dir<true> : k_bi_dir<false>, cols, it->dinv, d(W_R), d(W_Q), d(W_P), jac ? d(W_Z) : nullptr);
         RAILS_TRY(product(ph, W_Q)); // v = A p^
         RAILS_TRY(dots(1, W_RH, W_Q, W_RH, W_Q));
         RAILS_TRY(scalars(STEP_BI_ALPHA, 1));
-        ITER_PASS_LAUNCH((k_bi_s<true>), (k_bi_s<false>), g, cols, it->dinv, d(W_Q), d(W_R), jac ? d(W_SH) : nullptr);
+        pass(g, nslab, jac ? k_bi_s<true> : k_bi_s<false>, cols, it->dinv, d(W_Q), d(W_R), jac ? d(W_SH) : nullptr);
         RAILS_TRY(product(sh, W_T)); // t = A s^
         RAILS_TRY(dots(2, W_T, W_R, W_T, W_T));
         RAILS_TRY(scalars(STEP_BI_OMEGA, 2));
-        ITER_PASS_LAUNCH(k_bi_update, k_bi_update, g, cols, d(ph), d(sh), d(W_T), d(W_RH), d(W_X), d(W_R), c->ws);
+        RAILS_TRY(pass_sums(k_bi_update, cols, d(ph), d(sh), d(W_T), d(W_RH), d(W_X), d(W_R)));
         it->last_dots += 2 * g.ncw;
         return scalars(STEP_BI_END, 2);
     }
-#undef ITER_PASS_LAUNCH
 };
 
 // the upper end of the polynomial's interval: "eig_max", else the Gershgorin bound that goes with the preconditioner in effect (0: none)
@@ -933,47 +480,61 @@ double poly_hi(const rails_iter *it)
     return (it->jacobi && it->dinv) ? it->hi_jacobi : it->hi_plain;
 }
 
-// degree, interval and coefficients of a run; the work panels must be there (the fused kernel's rule looks at their row stride)
-int poly_setup(Run &run, const char *who)
+// The plan of a call, made before anything is queued: the sweeps (operator, panels, interval, coefficients, whether the steps run on the
+// fused kernel) of the polynomial or of every multigrid level.  Every refusal of a preconditioner is here.  The work panels and the
+// hierarchy must be there (the fused kernel's rule looks at the panels' row stride).
+int plan_call(Run &run, const char *who)
 {
     rails_iter *it = run.it;
+    rails_csr *A = it->A;
+    const int ld = it->w[W_R]->ld;
     run.K = it->poly_degree;
-    run.fused = false;
-    run.theta = 1.0;
+    run.amg = it->amg != 0;
+    run.other = run.K > 0 || run.amg;
+    run.sw[0] = Sweep{A, it->m, run.jac ? it->dinv : nullptr, it->defsign, it->w[W_R], {it->w[W_Z], it->w[W_Z2]}, it->w[W_D], it->w[W_Q]};
+    if (run.amg) {
+        const Amg &H = *it->hier;
+        for (size_t l = 0; l < H.lv.size(); ++l) {
+            const AmgLevel &L = H.lv[l];
+            Sweep &s = run.sw[l];
+            if (l > 0) s = Sweep{L.A, L.n, L.dinv, 1.0, L.w[L_R], {L.w[L_Z], L.w[L_Z2]}, L.w[L_D], L.w[L_Q]};
+            s.gvec = L.dinv; // (level 0: the object's operator in the object's panels, with the hierarchy's diagonal)
+            s.gs = 1.0;
+            RAILS_REQUIRE(rails_cheb_coef(L.hi / it->amg_ratio, L.hi, it->amg_degree, &s.theta, s.a, s.b), "rails_iter: no smoother of degree %d on [%g, %g] (level %d)",
+                          it->amg_degree, L.hi / it->amg_ratio, L.hi, (int)l);
+            s.fused = it->poly_fused && rails_cheb_fused_eligible(true, 0, L.n, ld);
+        }
+        return RAILS_OK;
+    }
     if (run.K == 0) return RAILS_OK;
+    Sweep &s = run.sw[0];
     const double hi = poly_hi(it);
     RAILS_REQUIRE(hi > 0.0 && rails_iter_finite(hi),
                   "%s: poly_degree %d needs an upper bound on the spectrum: the operator keeps no CSR arrays on the host to take one from, set \"eig_max\"", who, run.K);
-    RAILS_REQUIRE(rails_cheb_coef(hi / it->poly_ratio, hi, run.K, &run.theta, run.ca, run.cb), "%s: no polynomial of degree %d on [%g, %g]", who, run.K,
-                  hi / it->poly_ratio, hi);
-    const rails_csr *A = it->A;
+    RAILS_REQUIRE(rails_cheb_coef(hi / it->poly_ratio, hi, run.K, &s.theta, s.a, s.b), "%s: no polynomial of degree %d on [%g, %g]", who, run.K, hi / it->poly_ratio, hi);
     const bool stored = A->kind == rails_csr::STORED && !A->rect && A->rowptr && A->col && A->val;
     // an operator that exchanges (rows to send or ghost rows to receive: rails_spmm's own condition, so that a step issues an exchange in
     // the fused form exactly when it does in the unfused one -- a rank that only sends, or only receives, takes part; a rank whose plan is
     // empty issues none in either form) takes the ghost-row form; its ghost buffer's row stride is the group's width rounded up to even,
     // at most RAILS_ITER_GROUP
-    run.ghost = A->n_ghost > 0 || A->n_send > 0;
-    if (run.ghost)
-        run.fused = it->poly_fused && rails_cheb_fused_ghost_eligible(stored, it->m, A->n_ghost, it->w[W_Z]->ld, RAILS_ITER_GROUP);
+    s.ghost = A->n_ghost > 0 || A->n_send > 0;
+    if (s.ghost)
+        s.fused = it->poly_fused && rails_cheb_fused_ghost_eligible(stored, it->m, A->n_ghost, ld, RAILS_ITER_GROUP);
     else
-        run.fused = it->poly_fused && rails_cheb_fused_eligible(stored, A->n_ghost, it->m, it->w[W_Z]->ld);
+        s.fused = it->poly_fused && rails_cheb_fused_eligible(stored, A->n_ghost, it->m, ld);
     return RAILS_OK;
 }
 
-// the passes' geometry for a group of w columns
-void set_group(Run &run, int w)
+// what of the plan depends on the width w of a group: the geometry of its passes (iter_geom.h), every sweep's and the last level's
+void plan_group(Run &run, int w)
 {
     const rails_iter *it = run.it;
-    const int pairs = (w + 1) / 2;
-    int tx_bits = 0;
-    while ((1 << tx_bits) < pairs) ++tx_bits; // <= 4
-    const int TY = 256 >> tx_bits;
-    // slabs of at least 8 rows per thread, at most 1024 of them (k_colnorms2's rule)
-    int64_t nslab = std::max<int64_t>(1, std::min<int64_t>(1024, it->m / ((int64_t)TY * 8)));
-    const int64_t rps = (it->m + nslab - 1) / nslab;
-    nslab = (it->m + rps - 1) / rps;
-    run.g = PassGeom{w, it->w[W_R]->ld, tx_bits, it->m, rps};
-    run.nslab = nslab;
+    const int ld = it->w[W_R]->ld;
+    const int nl = run.amg ? (int)it->hier->lv.size() : 0;
+    for (int l = 0; l < std::max(1, nl); ++l) run.sw[l].g = rails_iter_pass_geom(run.sw[l].n, w, ld, &run.sw[l].slabs);
+    run.g = run.sw[0].g; // (level 0 has the operator's rows)
+    run.nslab = run.sw[0].slabs;
+    if (run.amg) run.gc = rails_iter_pass_geom(it->hier->n_coarse, w, ld, &run.slabs_c);
 }
 
 } // namespace
@@ -1284,43 +845,52 @@ int amg_prepare(rails_ctx *c, rails_iter *it)
     return amg_grow(c, it);
 }
 
+// What rails_iter_solve (`solve`) and rails_iter_precondition begin with: the checks of the arguments, the counters of the call at zero,
+// the work panels (`also`: panels wanted beside those the method uses), the hierarchy, the columns' scalars, and the plan in `run`.
+// Nothing is queued before it has returned.  With nc == 0 nothing is allocated or planned.
+//
+// Collective on a context that reduces.  The rule that keeps the ranks from deadlocking: every decision that changes how many
+// collectives are issued -- a refusal, the group loop, the number of iterations queued, the early exit, the non-finite right-hand side's
+// RAILS_EINVAL -- is a function of the arguments and settings every rank passes alike (nc, trans, max_iterations, check_every) and of
+// all-reduced data (the columns' scalars and the counts in `status`, the same bits on every rank), never of this rank's rows.
+int begin_call(rails_ctx *c, rails_iter *it, const char *who, bool solve, int trans, const rails_panel *X, int xc0, int nc, rails_panel *Y, int yc0, unsigned also, Run &run)
+{
+    RAILS_REQUIRE(c && it && X && Y, "%s: null argument", who);
+    RAILS_REQUIRE(c == it->ctx, "%s: the object belongs to another context", who);
+    RAILS_REQUIRE(!trans || (it->A->n_ghost == 0 && it->A->n_send == 0 && it->A->ncols_ext == it->A->m),
+                  "%s: the transposed solve of a row-partitioned operator (ghost rows) is not available: rails_spmm's transposed product is single GPU", who);
+    RAILS_REQUIRE(X->m == it->m && Y->m == it->m, "%s: the operator has %lld rows, X %lld, Y %lld", who, (long long)it->m, (long long)X->m, (long long)Y->m);
+    RAILS_REQUIRE(xc0 >= 0 && nc >= 0 && xc0 + nc <= X->cap && yc0 >= 0 && yc0 + nc <= Y->cap, "%s: column windows outside the panels", who);
+    if (X->d == Y->d) RAILS_REQUIRE(xc0 + nc <= yc0 || yc0 + nc <= xc0, "%s: X and Y windows alias", who);
+    it->last_dots = it->last_launches = it->last_products = it->last_poly = it->last_fused = it->last_allreduces = it->last_halo = 0;
+    it->last_cycles = it->last_cycle_products = it->last_cycle_launches = 0;
+    if (solve) it->last.clear();
+    if (nc == 0) return RAILS_OK;
+    RAILS_TRY(grow_work(c, it, std::min(nc, RAILS_ITER_GROUP), also));
+    if (it->amg) RAILS_TRY(amg_prepare(c, it));
+    if (solve) RAILS_TRY(grow_cols(c, it, nc));
+    run.c = c;
+    run.it = it;
+    run.trans = trans ? 1 : 0;
+    run.jac = it->jacobi && it->dinv;
+    run.tol2 = solve ? it->tol * it->tol : 0.0;
+    run.cols = nullptr;
+    return plan_call(run, who);
+}
+
 } // namespace
 
 extern "C" int rails_iter_solve(rails_ctx *c, rails_iter *it, int trans, const rails_panel *X, int xc0, int nc, rails_panel *Y, int yc0)
 {
     if (c) hipSetDevice(c->device);
     rails_slow_guard slow__(c, "rails_iter_solve", nc, it ? it->m : 0);
-    RAILS_REQUIRE(c && it && X && Y, "rails_iter_solve: null argument");
-    RAILS_REQUIRE(c == it->ctx, "rails_iter_solve: the object belongs to another context");
-    // Collective on a context that reduces.  The rule that keeps the ranks from deadlocking: every decision that changes how many
-    // collectives are issued -- a refusal, the group loop, the number of iterations queued, the early exit, the non-finite right-hand side's
-    // RAILS_EINVAL -- is a function of the arguments and settings every rank passes alike (nc, trans, max_iterations, check_every) and of
-    // all-reduced data (the columns' scalars and the counts in `status`, the same bits on every rank), never of this rank's rows.
-    RAILS_REQUIRE(!trans || (it->A->n_ghost == 0 && it->A->n_send == 0 && it->A->ncols_ext == it->A->m),
-                  "rails_iter_solve: the transposed solve of a row-partitioned operator (ghost rows) is not available: rails_spmm's transposed product is single GPU");
-    RAILS_REQUIRE(X->m == it->m && Y->m == it->m, "rails_iter_solve: the operator has %lld rows, X %lld, Y %lld", (long long)it->m, (long long)X->m,
-                  (long long)Y->m);
-    RAILS_REQUIRE(xc0 >= 0 && nc >= 0 && xc0 + nc <= X->cap && yc0 >= 0 && yc0 + nc <= Y->cap, "rails_iter_solve: column windows outside the panels");
-    if (X->d == Y->d) RAILS_REQUIRE(xc0 + nc <= yc0 || yc0 + nc <= xc0, "rails_iter_solve: X and Y windows alias");
-    it->last_dots = it->last_launches = it->last_products = it->last_poly = it->last_fused = it->last_allreduces = it->last_halo = 0;
-    it->last_cycles = it->last_cycle_products = it->last_cycle_launches = 0;
-    it->last.clear();
-    if (nc == 0) return RAILS_OK;
-    RAILS_TRY(grow_work(c, it, std::min(nc, RAILS_ITER_GROUP)));
-    if (it->amg) RAILS_TRY(amg_prepare(c, it));
-    RAILS_TRY(grow_cols(c, it, nc));
-    int32_t *status = (int32_t *)it->pinned;
     Run run;
-    run.c = c;
-    run.it = it;
-    run.trans = trans ? 1 : 0;
-    run.jac = it->jacobi && it->dinv;
-    run.tol2 = it->tol * it->tol;
-    RAILS_TRY(poly_setup(run, "rails_iter_solve"));
-    run.amg = it->amg != 0;
+    RAILS_TRY(begin_call(c, it, "rails_iter_solve", true, trans, X, xc0, nc, Y, yc0, 0, run));
+    if (nc == 0) return RAILS_OK;
+    int32_t *status = (int32_t *)it->pinned;
     for (int g0 = 0; g0 < nc; g0 += RAILS_ITER_GROUP) {
         const int w = std::min(RAILS_ITER_GROUP, nc - g0);
-        set_group(run, w);
+        plan_group(run, w);
         run.cols = it->cols_dev + g0;
         RAILS_TRY(rails_panel_copy(c, X, xc0 + g0, w, it->w[W_R], 0));
         RAILS_TRY(run.start());
@@ -1363,31 +933,12 @@ extern "C" int rails_iter_solve(rails_ctx *c, rails_iter *it, int trans, const r
 extern "C" int rails_iter_precondition(rails_ctx *c, rails_iter *it, const rails_panel *X, int xc0, int nc, rails_panel *Y, int yc0)
 {
     if (c) hipSetDevice(c->device);
-    RAILS_REQUIRE(c && it && X && Y, "rails_iter_precondition: null argument");
-    RAILS_REQUIRE(c == it->ctx, "rails_iter_precondition: the object belongs to another context");
-    RAILS_REQUIRE(X->m == it->m && Y->m == it->m, "rails_iter_precondition: the operator has %lld rows, X %lld, Y %lld", (long long)it->m, (long long)X->m,
-                  (long long)Y->m);
-    RAILS_REQUIRE(xc0 >= 0 && nc >= 0 && xc0 + nc <= X->cap && yc0 >= 0 && yc0 + nc <= Y->cap, "rails_iter_precondition: column windows outside the panels");
-    if (X->d == Y->d) RAILS_REQUIRE(xc0 + nc <= yc0 || yc0 + nc <= xc0, "rails_iter_precondition: X and Y windows alias");
-    it->last_dots = it->last_launches = it->last_products = it->last_poly = it->last_fused = it->last_allreduces = it->last_halo = 0; // the counters count this call
-    it->last_cycles = it->last_cycle_products = it->last_cycle_launches = 0;
-    if (nc == 0) return RAILS_OK;
-    unsigned want = 1u << W_R | 1u << W_Z | 1u << W_D;
-    if (it->poly_degree > 0 || it->amg) want |= 1u << W_Z2 | 1u << W_Q;
-    RAILS_TRY(grow_work(c, it, std::min(nc, RAILS_ITER_GROUP), want));
-    if (it->amg) RAILS_TRY(amg_prepare(c, it));
     Run run;
-    run.c = c;
-    run.it = it;
-    run.trans = 0;
-    run.jac = it->jacobi && it->dinv;
-    run.tol2 = 0.0;
-    run.cols = nullptr;
-    RAILS_TRY(poly_setup(run, "rails_iter_precondition"));
-    run.amg = it->amg != 0;
+    RAILS_TRY(begin_call(c, it, "rails_iter_precondition", false, 0, X, xc0, nc, Y, yc0, 1u << W_R | 1u << W_Z | 1u << W_D, run));
+    if (nc == 0) return RAILS_OK;
     for (int g0 = 0; g0 < nc; g0 += RAILS_ITER_GROUP) {
         const int w = std::min(RAILS_ITER_GROUP, nc - g0);
-        set_group(run, w);
+        plan_group(run, w);
         RAILS_TRY(rails_panel_copy(c, X, xc0 + g0, w, it->w[W_R], 0));
         RAILS_TRY(run.precondition());
         RAILS_TRY(rails_panel_copy(c, it->w[W_Z], 0, w, Y, yc0 + g0));

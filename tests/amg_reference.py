@@ -1,5 +1,5 @@
 """A numpy/scipy restatement of the smoothed-aggregation multigrid preconditioner of the iterative A^-1 operator (rails_amd/csrc/amg_host.h
-and amg_host.cpp for the set-up; itsolve.hip: Run::vcycle, k_amg_residual_csr, k_amg_coarse_dense, k_amg_prolong_add for the cycle),
+and amg_host.cpp for the set-up; itsolve.hip: Run::vcycle, iter_kernels.inc: k_amg_residual_csr, k_amg_coarse_dense, k_amg_prolong_add for the cycle),
 written from the rules and not by calling the library: strength, the three aggregation passes, the smoothed prolongation, the Galerkin
 product, the stop rules, the dense coarsest inverse; the V(1,1)-cycle with the Chebyshev smoother of tests/cheb_reference.py in float64
 and in longdouble; conjugate gradients preconditioned with the cycle (the rules of tests/iter_reference.py).  Not a test module:

@@ -143,6 +143,19 @@ int main()
         CHECK(!rails_cheb_fused_eligible(true, 0, 16, 0));
     }
 
+    // the z panel a sweep starts in: following the ping-pong of the steps from there ends in the primary panel (0); unfused steps never
+    // leave it
+    for (int steps = 0; steps <= 17; ++steps) {
+        for (int fused = 0; fused <= 1; ++fused) {
+            int at = rails_cheb_start_panel(fused != 0, steps);
+            CHECK(at == 0 || at == 1);
+            if (!fused) CHECK(at == 0);
+            for (int k = 0; k < steps; ++k)
+                if (fused) at ^= 1; // a fused step reads one panel and writes the other
+            CHECK(at == 0);
+        }
+    }
+
     std::printf("%d checks, %d failed\n", checks, failed);
     if (!failed) std::printf("ALL PASSED\n");
     return failed ? 1 : 0;

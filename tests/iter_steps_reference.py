@@ -1,5 +1,5 @@
 """Step-by-step restatement of the iterative A^-1 operator's recurrences (rails_amd/csrc/itsolve.hip, iter_scalars.h), the case list, the
-bounds and a plain restatement of set_group's pass geometry.  Not a test module: tests/test_iter_steps_host.py checks it on the CPU (the
+bounds and a plain restatement of the pass geometry (iter_geom.h).  Not a test module: tests/test_iter_steps_host.py checks it on the CPU (the
 bounds' conditions, the geometry table, seeded mistakes), tests/test_gpu_iter_steps.py compares the device against it.
 
 Why step by step.  A Krylov iteration corrects itself: x and r move with the same alpha, so a wrong inner product costs a converged solve a
@@ -64,7 +64,7 @@ def rhs(m, w):
 
 # ------------------------------------------------------------------------------------------------------------------ the geometry
 def geometry(m, w):
-    """set_group of itsolve.hip for a group of w <= 32 columns of m rows: (TY, slabs, rows per slab, rows of the last slab)"""
+    """rails_iter_pass_geom of iter_geom.h for a group of w <= 32 columns of m rows: (TY, slabs, rows per slab, rows of the last slab)"""
     assert 1 <= w <= GROUP
     pairs = (w + 1) // 2
     tx_bits = 0
