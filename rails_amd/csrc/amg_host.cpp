@@ -1,5 +1,5 @@
 // amg_host.cpp -- host set-up of the smoothed-aggregation multigrid preconditioner (amg_host.h has the rules).  No HIP:
-// tests/cpp/amg_host.cpp links this object with sprhs_host.o (the stable transpose) and host_numerics.o (the LAPACK pass-throughs).
+// tests/cpp/amg_host.cpp links this object with sprhs_host.o (the stable transpose) and host_lapack.o (the LAPACK pass-throughs).
 #include "amg_host.h"
 
 #include <algorithm>

@@ -1,5 +1,5 @@
 // amg_host.cpp -- the host set-up of the smoothed-aggregation multigrid preconditioner (rails_amd/csrc/amg_host.cpp) on its own: no HIP,
-// no library, linked against amg_host.o, sprhs_host.o and host_numerics.o only, so it can also be built with -fsanitize=address,undefined
+// no library, linked against amg_host.o, sprhs_host.o and host_lapack.o only, so it can also be built with -fsanitize=address,undefined
 // and run as it is.  Run by tests/test_amg_host.py.
 //
 //   amg_host dump IN OUT THETA COARSE   builds the hierarchy of the matrix in IN twice, requires the two to be the same bytes, and writes

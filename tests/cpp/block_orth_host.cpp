@@ -1,5 +1,5 @@
 // The host arithmetic of the coordinate back end's block orthogonalisation (rails/BlockOrthHost.hpp), checked without a GPU.  Built by
-// rails_amd/csrc/Makefile from that header and host_numerics.o alone (no HIP, no library), run by tests/test_block_orth_host.py.
+// rails_amd/csrc/Makefile from that header and host_lapack.o alone (no HIP, no library), run by tests/test_block_orth_host.py.
 //
 // Every expected value is formed here, in long double where that is cheap, never by the header; inputs come from an integer hash.
 #include <cmath>
@@ -12,7 +12,7 @@
 
 #include "rails/BlockOrthHost.hpp"
 
-void rails_set_error(const char *fmt, ...) // (host_numerics.o reports a missing LAPACK through it)
+void rails_set_error(const char *fmt, ...) // (host_lapack.o reports a missing LAPACK through it)
 {
     va_list ap;
     va_start(ap, fmt);

@@ -203,7 +203,7 @@ def test_host_sb03md_smith_route_is_verified_and_falls_back():
 def test_host_sb03md_builds_on_the_call_before_inside_a_restart_cycle():
     """Inside a restart cycle the solver's projected matrix grows by bordering (V'AV keeps its leading block, src/LyapunovSolver.hpp:146-160):
     the factored ADI route of rails_sb03md then keeps its shifts and EXTENDS the inverses / LU factors of M - p I of the call before instead
-    of recomputing them (host_numerics.cpp, AdiCache).  The same projected equations, solved in the order a run meets them, have to come
+    of recomputing them (lyap_dense.cpp, AdiCache).  The same projected equations, solved in the order a run meets them, have to come
     out as Bartels-Stewart gives them whether a call inherited or not; a border that moves the spectrum, an unrelated matrix and a smaller
     one must not be served from the cache."""
     import scipy.linalg as sl

@@ -1,5 +1,5 @@
 """The host set-up of the smoothed-aggregation multigrid preconditioner, no GPU: the stand-alone program tests/cpp/amg_host.cpp (linked
-against amg_host.o, sprhs_host.o and host_numerics.o alone) builds the hierarchies of the shared problems, and its aggregates and sparsity
+against amg_host.o, sprhs_host.o and host_lapack.o alone) builds the hierarchies of the shared problems, and its aggregates and sparsity
 patterns must equal those of the restatement tests/amg_reference.py exactly, its values and the dense inverse within the restatement's own
 float64 error against longdouble; two builds must give the same bytes (checked inside the program); the stop rules, the cap of 1024 rows
 and every refusal; and the restatement's preconditioned iteration counts, a fifth of Jacobi's at most."""

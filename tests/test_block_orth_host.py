@@ -1,6 +1,6 @@
 """The host arithmetic of the coordinate back end's block orthogonalisation (rails_amd/include/rails/BlockOrthHost.hpp), checked on the
 CPU by a stand-alone program (tests/cpp/block_orth_host.cpp, built by rails_amd/csrc/Makefile into rails_amd/lib/block_orth_host from the
-header and host_numerics.o only: no HIP, no library).
+header and host_lapack.o only: no HIP, no library).
 
 The program makes its inputs from an integer hash and its expected values in long double arithmetic of its own: the scaled Cholesky
 factor, the triangular inverse and product, the DGKS rule, the overlapped form's prediction and re-base end to end (with the device's
