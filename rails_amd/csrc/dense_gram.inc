@@ -1,4 +1,4 @@
-// dense_gram.inc -- the body of the row-split Gram kernels k_gram and k_gram2 (dense.hip), included once in each.  The kernel supplies its
+// dense_gram.inc -- the body of the row-split Gram kernels k_gram and k_gram2 (dense_gram.hip), included once in each.  The kernel supplies its
 // parameters (a, Y, ldy, b, m, rows_per_slab, ngj, partial) and the left operand Xo, a OneSeg or a TwoSeg.
     __shared__ double red[TI * TJ * 256];
     const int lane = threadIdx.x & 63;

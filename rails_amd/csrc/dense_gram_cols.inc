@@ -1,4 +1,4 @@
-// dense_gram_cols.inc -- the body of the wide-X Gram kernels k_gram_cols and k_gram_cols2 (dense.hip), included once in each.  The kernel
+// dense_gram_cols.inc -- the body of the wide-X Gram kernels k_gram_cols and k_gram_cols2 (dense_gram.hip), included once in each.  The kernel
 // supplies its parameters (a, Y, ldy, b, m, rows_per_slab, partial) and the left operand Xo, a OneSeg or a TwoSeg.
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;

@@ -1,4 +1,4 @@
-// dense_panel_gemm.inc -- the body of the panel GEMM kernels k_panel_gemm and k_panel_gemm2 (dense.hip), included once in each.  The kernel
+// dense_panel_gemm.inc -- the body of the panel GEMM kernels k_panel_gemm and k_panel_gemm2 (dense_gemm.hip), included once in each.  The kernel
 // supplies its parameters (alpha, k = the columns of X, C, r, beta, Yp, ldy, m), the left operand Xo (a OneSeg or a TwoSeg) and
 // RAILS_PG_VEC4(c): may columns c .. c + 3 of a row be fetched as two 16-byte loads (aligned rows, one segment, inside the operand).
     constexpr int RL = 16 * TR + 4; // LDS row length (doubles): +4 keeps the 4 k-groups on disjoint banks

@@ -19,7 +19,7 @@
 // depend on check_every.
 //
 // Passes: thread (tx, ty) of a block owns the column pair 2 tx, 2 tx + 1 and every TY-th row of its block's slab (k_colnorms2's shape,
-// dense.hip), adds its rows in increasing order, the TY row classes meet in an LDS tree of fixed shape, the per-block partial sums go to
+// dense_gram.hip), adds its rows in increasing order, the TY row classes meet in an LDS tree of fixed shape, the per-block partial sums go to
 // the context workspace, and the one-workgroup kernel k_iter_scalars sums them over the blocks in a fixed order (iter_reduce) and then
 // computes the scalars (iter_compute).  No floating-point atomics: two runs give the same bits.
 //

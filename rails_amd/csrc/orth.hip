@@ -20,7 +20,7 @@
 // rails_orthogonalize_range (further down) is the rank-revealing form for a start space: columns that may be dependent, any number of
 // them, dropped instead of replaced; it shares project_block with the two above and never takes their column-wise paths.
 //
-// This file is the algorithm only: every kernel it launches is in dense.hip, where the one- and two-segment forms share one body.
+// This file is the algorithm only: every kernel it launches is in dense_gram.hip and dense_gemm.hip, where the one- and two-segment forms share one body.
 #include "rails_internal.h"
 
 #include <cmath>

@@ -80,7 +80,7 @@ struct rails_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t ev_h2d = nullptr; // recorded after an asynchronous upload out of `pinned`; waited for before the host writes there again
     bool h2d_pending = false;
-    // deferred small results (dense.hip: rails_gram_deferred ...): slots of `defer_slot` doubles on the device with a pinned mirror
+    // deferred small results (dense_deferred.hip: rails_gram_deferred ...): slots of `defer_slot` doubles on the device with a pinned mirror
     double *defer_dev = nullptr, *defer_pin = nullptr;
     size_t defer_slot = 0;
     int defer_nslots = 0;
@@ -252,7 +252,6 @@ inline int spmm_env(const char *name, int def)
 
 // ---- helpers implemented in ctx.hip ----
 int rails_ws_reserve(rails_ctx *ctx, size_t bytes);
-void rails_library_gemm_release(rails_ctx *ctx);
 int rails_small_reserve(rails_ctx *ctx, size_t bytes);
 int rails_pinned_reserve(rails_ctx *ctx, size_t bytes);
 // host -> pinned -> device staging without a stream synchronisation: begin_write waits until the previous upload out of the
@@ -294,12 +293,13 @@ bool planes_last_interior(const rails_csr *A);
 int rails_spmm_tiled(rails_ctx *c, rails_csr *A, const double *X, int ldx, const double *Xg, int ldg, double *Y, int ldy, int nc, bool vec2,
                      int x_room, bool *done);
 void rails_tiled_release(rails_csr *A);
-// dense.hip: partial Gram into device memory (no host copy / all-reduce): C_dev (a x b col-major, ldc = a)
+// dense_gram.hip: partial Gram into device memory (no host copy / all-reduce): C_dev (a x b col-major, ldc = a)
 int rails_gram_dev(rails_ctx *ctx, const double *X, int ldx, const double *Y, int ldy, int64_t m, int a, int b,
                    double *C_dev);
+// dense_gemm.hip: Y = beta Y + alpha X C with C on the device (k x r, packed)
 int rails_panel_gemm_dev(rails_ctx *ctx, double alpha, const double *X, int ldx, int k, const double *C_dev,
                          int r, double beta, double *Y, int ldy, int64_t m);
-// dense.hip: local column sums of squares of nc <= 512 columns into device memory (no all-reduce, no host copy)
+// dense_gram.hip: local column sums of squares of nc <= 512 columns into device memory (no all-reduce, no host copy)
 int rails_colnorms2_dev(rails_ctx *ctx, const double *X, int ldx, int64_t m, int nc, double *out_dev);
 // the same with the left operand in two panels, [X1 X2] with a1 + a2 columns (b, r <= 32; Y += alpha [X1 X2] C)
 int rails_gram2_dev(rails_ctx *ctx, const double *X1, int ldx1, int a1, const double *X2, int ldx2, int a2, const double *Y, int ldy, int64_t m,

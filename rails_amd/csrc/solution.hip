@@ -5,7 +5,7 @@
 //
 // One pass over U and no m x k temporary: a wave owns 16 rows.  Its 16 x k row tile is the A operand of v_mfma_f64_16x16x4 (lane l supplies
 // U[row l&15][column 4s + (l>>4)]), S streams through LDS in chunks of 32 of its rows as the B operand -- the double buffer fed by LDS-DMA
-// that k_panel_gemm_wide (dense.hip) uses, in the same packed layout, row length 16 TR + 4 doubles so that the four row groups of a wave
+// that k_panel_gemm_wide (dense_gemm.hip) uses, in the same packed layout, row length 16 TR + 4 doubles so that the four row groups of a wave
 // read different banks -- and the product tile P = U_tile S stays in the accumulators (TR <= 16 column tiles, 64 doubles per lane).  The
 // epilogue multiplies it with U_tile again where it sits: lane l holds P[row (l>>4) + 4v][column 16t + (l&15)], reads the matching entries of U
 // (the lines the wave has just read: L2 / L0 hits), sums its own columns and the 16 lanes of a row group are added by four xor-shuffles, a

@@ -1,6 +1,6 @@
 // solution_capi.cpp -- the solution object of include/rails_solution.h, X = U S U', in terms of the library's own entry points: every
 // reduction over rows is a rails_gram (so it holds under a row partition), the small algebra is on the host, the m x k work is the
-// kernels of dense.hip, orth.hip and solution.hip.  rails_solution_from_solver lives in solver_capi.cpp (it reads the solver object).
+// kernels of dense_*.hip, orth.hip and solution.hip.  rails_solution_from_solver lives in solver_capi.cpp (it reads the solver object).
 #include <algorithm>
 #include <cmath>
 #include <cstring>

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-kernel register / occupancy report of one HIP source (compile only: works without a GPU).
 usage: python scripts/kernel_resources.py rails_amd/csrc/spmm.hip [name filter] [extra hipcc flags...]
-(one source per call: spmm.hip has the row kernels, spmm_tiled.hip the LDS-staged ones)"""
+(one source per call: spmm.hip has the row kernels, spmm_tiled.hip the LDS-staged ones; dense_gram.hip, dense_gemm.hip and
+dense_deferred.hip the dense kernels)"""
 import os
 import re
 import subprocess

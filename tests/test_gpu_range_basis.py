@@ -1,4 +1,4 @@
-"""rails_orthogonalize_range and rails_panel_colnorms2 (include/rails_hip.h, rails_amd/csrc/orth.hip, dense.hip): the rank-revealing
+"""rails_orthogonalize_range and rails_panel_colnorms2 (include/rails_hip.h, rails_amd/csrc/orth.hip, dense_gram.hip): the rank-revealing
 orthonormal range basis of a start space against a longdouble in-order Gram-Schmidt with two passes that drops a column of which less
 than 1e-8 survives -- the reference's Morth, matlab/RAILSsolver.m:567-580.
 
