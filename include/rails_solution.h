@@ -26,6 +26,9 @@ int rails_panel_move_rows(rails_ctx *ctx, const rails_panel *X, int xc0, int nc,
  * fp64 MFMA path, no m x k temporary (rails_amd/csrc/solution.hip).  S host column-major k x k, leading dimension lds (need not be
  * symmetric: the form is that of S as given).  k <= 512.  Out may be U's panel when column oc0 lies outside the window.  Asynchronous. */
 int rails_panel_rowquad(rails_ctx *ctx, const rails_panel *U, int c0, int k, const double *S_host, int lds, rails_panel *Out, int oc0);
+/* What the context's last rails_panel_rowquad launched: *nslices slices of S (0 for k = 0, for a panel without rows, or before any call) and, for
+ * the first min(cap, *nslices) of them, the template parameter TR of k_panel_rowquad<TR> (2, 4, 8, 12 or 16 column tiles of 16). */
+int rails_panel_rowquad_last_plan(const rails_ctx *ctx, int *nslices, int *tr, int cap);
 
 /* U = columns [c0, c0+k) of the panel; copy != 0: the object keeps a device copy of them, copy == 0: it borrows the panel (the caller
  * keeps it alive and unchanged).  S_host column-major k x k, leading dimension lds; it is copied and symmetrised ((S + S')/2). */

@@ -97,6 +97,8 @@ struct rails_ctx {
     // template parameter of the last launch of k_update_gram<NBW, .>, k_gram_cols[2]<TI, ., .> and k_panel_gemm_wide<TR> (rails_dense_last_tiles); 0: none yet
     int last_update_gram_nbw = 0, last_gram_cols_ti = 0, last_gemm_wide_tr = 0;
     int last_update_gram_form = 0; // the fused update + second projection's last launch: 1 k_update_gram, 2 k_update_gram_p (rails_dense_last_update_gram_form); 0: none yet
+    // slices of the last rails_panel_rowquad and the template parameter of k_panel_rowquad<TR> each one launched (rails_panel_rowquad_last_plan); 0 slices: none yet, or k = 0
+    int last_rowquad_nslices = 0, last_rowquad_tr[2] = {0, 0};
 };
 
 // the busy meter (see rails_ctx): RAILS_LAUNCH brackets a launch, rails_stream_sync reads what has been bracketed since the last one

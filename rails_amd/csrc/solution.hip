@@ -148,6 +148,7 @@ int launch_rowquad(rails_ctx *c, const double *U, int ldu, int k, const double *
     const size_t lds = (size_t)2 * 32 * RL * sizeof(double);
     RAILS_HIP_CHECK(hipFuncSetAttribute((const void *)k_panel_rowquad<TR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     RAILS_LAUNCH((k_panel_rowquad<TR>), dim3((unsigned)((m + 127) / 128)), dim3(512), lds, c->stream, U, ldu, k, st, j0, r, out, ldo, m, vec_ok, accumulate);
+    c->last_rowquad_tr[c->last_rowquad_nslices++] = TR; // k <= 512: two slices at most
     return RAILS_OK;
 }
 
@@ -164,6 +165,7 @@ extern "C" int rails_panel_rowquad(rails_ctx *c, const rails_panel *U, int c0, i
     RAILS_REQUIRE(U->m == Out->m, "rails_panel_rowquad: row mismatch %lld vs %lld", (long long)U->m, (long long)Out->m);
     RAILS_REQUIRE(k == 0 || (S_host && lds >= k), "rails_panel_rowquad: bad small matrix (leading dimension %d < %d)", lds, k);
     if (U->d == Out->d) RAILS_REQUIRE(oc0 < c0 || oc0 >= c0 + k, "rails_panel_rowquad: the output column lies inside the input window");
+    c->last_rowquad_nslices = 0;
     if (U->m == 0) return RAILS_OK;
     if (k == 0) return rails_panel_fill(c, Out, oc0, 1, 0.0);
     // S goes to the device once, through the pinned staging buffer into the context's small buffer (re-used in stream order)
@@ -197,6 +199,15 @@ extern "C" int rails_panel_rowquad(rails_ctx *c, const rails_panel *U, int c0, i
     }
     RAILS_HIP_CHECK(hipGetLastError());
     c->n_rowquad++;
+    return RAILS_OK;
+}
+
+// what the context's last rails_panel_rowquad launched: the number of slices and the TR of k_panel_rowquad<TR> for the first `cap` of them
+extern "C" int rails_panel_rowquad_last_plan(const rails_ctx *c, int *nslices, int *tr, int cap)
+{
+    RAILS_REQUIRE(c && nslices && (tr || cap <= 0), "rails_panel_rowquad_last_plan: null argument");
+    *nslices = c->last_rowquad_nslices;
+    for (int q = 0; q < cap && q < c->last_rowquad_nslices; ++q) tr[q] = c->last_rowquad_tr[q];
     return RAILS_OK;
 }
 

@@ -7,11 +7,16 @@ summation; 8 k eps leaves a factor 4 for the MFMA's internal summation order and
 
 Object bound: eigenvalues within 1e-11 max|lambda| and residuals within 1e-11 |X|_2, the bound this project uses for device
 orthogonalisation against the oracle (tests/test_gpu_kernels.py).  U has condition about 1e2; test_object_bound_holds_for_numpy_on_the_host
-(no GPU) confirms that the same computation in numpy -- QR, then a small symmetric eigensolve -- stays inside it for the chosen seed."""
+(no GPU) confirms that the same computation in numpy -- QR, then a small symmetric eigensolve -- stays inside it for the chosen seed.
+
+variance, block, apply and trace of the object are also held to componentwise bounds against longdouble references at m = 300, k = 40
+(tests/solution_reference.py states and derives them; tests/test_solution_reference_host.py shows numpy in double meets them)."""
 import ctypes as C
 
 import numpy as np
 import pytest
+
+import solution_reference as R
 
 EPS = 2.0 ** -52
 
@@ -158,3 +163,119 @@ def test_eigs_truncates_a_rank_deficient_solution():
     small.close()
     sol.close()
     ctx.close()
+
+
+# ---- the object at derived bounds (tests/solution_reference.py) ---------------------------------------------------------------------------
+
+
+@pytest.fixture(scope="module")
+def small_object():
+    import rails_amd
+
+    ctx = rails_amd.Context(device=0, seed=3)
+    U, S = R.object_problem()
+    sol = rails_amd.Solution(ctx, U, S)
+    assert np.array_equal(sol.S(), S)  # S is symmetric: the object's (S + S')/2 is S itself
+    yield ctx, sol, U, S
+    sol.close()
+    ctx.close()
+
+
+def _err(got, want):
+    return np.abs(np.asarray(got - want, dtype=np.float64))
+
+
+@pytest.mark.gpu
+def test_object_variance_trace_and_blocks_at_derived_bounds(small_object):
+    import rails_amd
+
+    ctx, sol, U, S = small_object
+    m, k = U.shape
+    err, bound = _err(sol.variance(), R.rowquad(U, S)), R.rowquad_bound(U, S)
+    print("variance: max |err| / bound = %.3g" % (err / bound).max())
+    assert np.all(err <= bound)
+    terr, tbound = abs(float(sol.trace() - R.trace(U, S))), R.trace_bound(U, S)
+    print("trace: |err| / bound = %.3g" % (terr / tbound))
+    assert terr <= tbound
+    for rows, cols in R.block_cases(m):
+        got = sol.block(rows, cols)
+        err, bound = _err(got, R.block(U, S, rows, cols)), R.block_bound(U, S, rows, cols)
+        print("block %s x %s: max |err| / bound = %.3g" % (rows, cols, (err / bound).max()))
+        assert got.shape == (len(rows), len(cols)) and np.all(err <= bound)
+    rows = R.block_cases(m)[0][0]
+    assert np.all(_err(sol.block(rows), R.block(U, S, rows, rows)) <= R.block_bound(U, S, rows, rows))
+    for bad in ([0, m], [-1]):
+        with pytest.raises(rails_amd.RailsError):
+            sol.block(bad)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nc", R.APPLY_NC)
+@pytest.mark.parametrize("wc0,yc0", [(3, 2), (2, 5)])
+def test_object_apply_on_windows_at_the_derived_bound(small_object, nc, wc0, yc0):
+    """W and Y are windows, at an odd and an even offset each, of wider panels; nc = 257 takes rails_panel_gemm_wide"""
+    import rails_amd
+    from rails_amd.wrappers import HipMultiVectorWrapper as MV
+
+    ctx, sol, U, S = small_object
+    m = U.shape[0]
+    W = R.apply_rhs(m, nc)
+    wide = np.full((m, wc0 + nc + 3), np.nan)  # nothing outside the window is read
+    wide[:, wc0:wc0 + nc] = W
+    Wd, Yd = MV(ctx, data=wide), MV(ctx, data=np.full((m, yc0 + nc + 2), 7.0))
+    rails_amd._lib.check(ctx.lib.rails_solution_apply(sol.h, Wd.panel.h, wc0, nc, Yd.panel.h, yc0), "rails_solution_apply")
+    got = Yd.to_host()
+    err, bound = _err(got[:, yc0:yc0 + nc], R.apply(U, S, W)), R.apply_bound(U, S, W)
+    print("apply nc = %d, W at %d, Y at %d: max |err| / bound = %.3g" % (nc, wc0, yc0, (err / bound).max()))
+    assert np.all(err <= bound)
+    assert np.all(got[:, :yc0] == 7.0) and np.all(got[:, yc0 + nc:] == 7.0)  # the columns around Y are untouched
+
+
+@pytest.mark.gpu
+def test_object_apply_no_columns_and_refusals(small_object):
+    from rails_amd.wrappers import HipMultiVectorWrapper as MV
+
+    ctx, sol, U, S = small_object
+    m, k = U.shape
+    Wd, Yd = MV(ctx, data=R.apply_rhs(m, 16)), MV(ctx, data=np.full((m, 4), 7.0))
+    assert ctx.lib.rails_solution_apply(sol.h, Wd.panel.h, 3, 0, Yd.panel.h, 1) == 0  # nc = 0: nothing happens
+    assert np.all(Yd.to_host() == 7.0)
+    own = sol.U()
+    before = R.bits(own.to_host())
+    assert ctx.lib.rails_solution_apply(sol.h, Wd.panel.h, 0, 16, own.panel.h, 0) != 0  # Y is the solution's own panel
+    assert ctx.lib.rails_solution_apply(sol.h, Wd.panel.h, 0, 16, Yd.panel.h, 0) != 0  # 16 columns into a capacity of 4
+    assert ctx.lib.rails_solution_apply(sol.h, Wd.panel.h, 1, 16, Yd.panel.h, 0) != 0  # W's window leaves its capacity
+    short = MV(ctx, data=np.zeros((m - 1, 16)))
+    assert ctx.lib.rails_solution_apply(sol.h, short.panel.h, 0, 16, short.panel.h, 0) != 0  # row mismatch
+    assert np.array_equal(R.bits(own.to_host()), before) and np.all(Yd.to_host() == 7.0)
+
+
+@pytest.mark.gpu
+def test_borrowed_window_agrees_bitwise_with_a_copy(small_object):
+    """copy=False on columns [3, 3 + k) of a wider panel and copy=True (its own aligned panel) hold the same numbers: the same bits out"""
+    import rails_amd
+    from rails_amd.wrappers import HipMultiVectorWrapper as MV
+
+    ctx, _, U, S = small_object
+    m, k = U.shape
+    wide = np.random.default_rng(8).standard_normal((m, 3 + k + 2))
+    wide[:, 3:3 + k] = U
+    Wd = MV(ctx, data=wide)
+    view = Wd.view(3, 3 + k - 1)
+    assert (view.c0, view.n) == (3, k)
+    borrowed, copied = rails_amd.Solution(ctx, view, S, copy=False), rails_amd.Solution(ctx, view, S, copy=True)
+    c0 = C.c_int(-1)
+    assert ctx.lib.rails_solution_panel(borrowed.h, C.byref(c0)) == Wd.panel.h.value and c0.value == 3
+    assert ctx.lib.rails_solution_panel(copied.h, C.byref(c0)) != Wd.panel.h.value and c0.value == 0
+    assert np.array_equal(R.bits(borrowed.U().to_host()), R.bits(U)) and np.array_equal(R.bits(copied.U().to_host()), R.bits(U))
+    assert np.array_equal(R.bits(borrowed.variance()), R.bits(copied.variance()))
+    assert np.all(_err(borrowed.variance(), R.rowquad(U, S)) <= R.rowquad_bound(U, S))
+    assert borrowed.trace() == copied.trace()
+    for nc in (16, 257):
+        W = R.apply_rhs(m, nc)
+        assert np.array_equal(R.bits(borrowed.apply(W)), R.bits(copied.apply(W))), nc
+    rows, cols = R.block_cases(m)[0]
+    assert np.array_equal(R.bits(borrowed.block(rows, cols)), R.bits(copied.block(rows, cols)))
+    assert np.array_equal(R.bits(Wd.to_host()), R.bits(wide))  # the borrowed panel is unchanged, its other columns included
+    borrowed.close()
+    copied.close()
