@@ -16,6 +16,8 @@
 // :419-426) stay on the device; the host reads H back once at the end.
 #include "rails_internal.h"
 
+#include "lanczos_plan.h"
+
 #include <algorithm>
 #include <cmath>
 
@@ -27,7 +29,7 @@ struct rails_lanczos_state {
     int L = 0;
     double *small = nullptr; // T, coefficients, reduced sums, state, alphas, betas
     size_t small_bytes = 0;
-    int last_nch = 0, last_unroll = 0, last_nblocks = 0; // what the last lz_run launched (rails_lanczos_last_launch)
+    int last_nch = 0, last_unroll = 0, last_nblocks = 0; // what the last run launched (rails_lanczos_last_launch)
 };
 
 // one state per context: the Lanczos vectors of the context's last run (several contexts may live in one process,
@@ -82,7 +84,7 @@ struct LzArgs {
     double *Qc;
     int step;             // -1 = init pass (r := raw q_0)
     const double *coef;   // [k (for AV) | k (for MV) | p (for B)]
-    const double *state;  // alpha, beta_prev, inv_beta, done, steps
+    const double *state;  // the slots of lz::State
     double *partial;      // [nblocks][2k+p+1]
 };
 
@@ -208,12 +210,12 @@ struct LzBt {
     double *item_partial;
     const double *r;     // the vector of this pass (m entries at least)
     double *out;         // sums + 2k
-    const double *state; // [3]: the run has stopped
+    const double *state; // [lz::DONE]: the run has stopped
 };
 
 __global__ __launch_bounds__(256) void k_sprhs_bt(LzBt b)
 {
-    if (b.state[3] != 0.0) return;
+    if (b.state[lz::DONE] != 0.0) return;
     if ((int)blockIdx.x < b.nshort) {
         const int j = blockIdx.x * 256 + threadIdx.x;
         if (j >= b.p) return;
@@ -243,7 +245,7 @@ __global__ __launch_bounds__(256) void k_sprhs_bt(LzBt b)
 
 __global__ __launch_bounds__(256) void k_sprhs_bt_long(LzBt b)
 {
-    if (b.state[3] != 0.0) return;
+    if (b.state[lz::DONE] != 0.0) return;
     const int lane = threadIdx.x & 63;
     const int64_t l = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (l >= b.n_long) return; // wave-uniform
@@ -262,7 +264,7 @@ __global__ __launch_bounds__(1024) void k_lz_small(const double *__restrict__ su
 {
     __shared__ double sh[1024];
     __shared__ double part1[4][256], part2[4][256];
-    if (state[3] != 0.0) return;
+    if (state[lz::DONE] != 0.0) return;
     const int tid = threadIdx.x;
     const int jr = tid & 255, q = tid >> 8; // output row within a group of 256, quarter of the inner index
     const double rr = sums[2 * k + p];
@@ -271,8 +273,8 @@ __global__ __launch_bounds__(1024) void k_lz_small(const double *__restrict__ su
     if (!init && beta < 1e-14) { // src/LyapunovSolver.hpp:419-426
         if (tid == 0) {
             betas[step] = beta;
-            state[3] = 1.0;
-            state[4] = (double)(step + 1);
+            state[lz::DONE] = 1.0;
+            state[lz::STEPS] = (double)(step + 1);
         }
         return;
     }
@@ -319,13 +321,13 @@ __global__ __launch_bounds__(1024) void k_lz_small(const double *__restrict__ su
     }
     if (tid == 0) {
         const double alpha_next = sh[0];
-        state[0] = alpha_next;
-        state[1] = init ? 0.0 : beta;
-        state[2] = inv;
+        state[lz::ALPHA] = alpha_next;
+        state[lz::BETA_PREV] = init ? 0.0 : beta;
+        state[lz::INV_BETA] = inv;
         alphas[step + 1] = alpha_next;
         if (!init) {
             betas[step] = beta;
-            state[4] = (double)(step + 1);
+            state[lz::STEPS] = (double)(step + 1);
         }
     }
 }
@@ -380,227 +382,278 @@ __global__ void k_lz_random(double *__restrict__ q, int64_t m, int64_t mpad, uin
     }
 }
 
-// sp != nullptr: the pass of the sparse form
-template <int NCH, int U>
-void launch_pass_u(rails_ctx *c, const LzArgs &a, const LzSparse *sp, int *nblocks_io, bool size_only)
+// ------------------------------------------------------------------------------------------------------------ the host side ---
+// What a call decides without computing is lanczos_plan.h's.  Below: the stages of a run, in the order lz_stages takes them.
+
+// the pass kernels: one row per row of lz::kPass, both forms of each.  The occupancy query and the launch both go through this table.
+struct PassKernels {
+    void (*sparse)(LzArgs, LzSparse);
+    void (*dense)(LzArgs);
+};
+#define RAILS_LZ_PASS_KERNELS(N, U) {k_lanczos_pass_sparse<N, U>, k_lanczos_pass<N, U>},
+const PassKernels kPassKernels[lz::kPassCount] = {RAILS_LZ_PASS_TABLE(RAILS_LZ_PASS_KERNELS)};
+#undef RAILS_LZ_PASS_KERNELS
+
+// one call of any of the three forms (what does not apply to a form is null or 0)
+struct LzCall {
+    lz::Form form;
+    const rails_panel *AV;
+    int avc0;
+    const rails_panel *MV;
+    int mvc0;
+    int k;
+    const double *T;
+    int ldt;
+    const rails_panel *B; // DenseB, StartOnly
+    int bc0;
+    int p;
+    const rails_sprhs *SR; // SparseB
+    int L;
+    double *H;
+    int ldh;
+    int *steps_out;
+    double *start_sums; // StartOnly
+};
+
+// ---- stage 1: the checks (lanczos_plan.h: lz::check).  Nothing is read through a pointer before the null check has seen it.
+int lz_check(const rails_ctx *c, const LzCall &q)
 {
-    if (size_only) { // grid = resident blocks only (every block walks the row groups with a grid stride)
-        int occ = 0;
-        const hipError_t e = sp ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_lanczos_pass_sparse<NCH, U>, 256, 0)
-                                : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_lanczos_pass<NCH, U>, 256, 0);
-        if (e != hipSuccess || occ < 1) occ = 2;
-        if (occ > 4) occ = 4;
-        *nblocks_io = c->num_cu * occ;
-        return;
+    const bool sparse = q.form == lz::Form::SparseB;
+    lz::Call s;
+    s.form = q.form;
+    s.have_inputs = c && q.AV && q.MV && (sparse ? q.SR != nullptr : q.B != nullptr);
+    s.have_outputs = q.H && q.steps_out;
+    s.have_T = q.T != nullptr;
+    s.k = q.k, s.p = q.p, s.L = q.L, s.ldh = q.ldh, s.ldt = q.ldt;
+    s.avc0 = q.avc0, s.mvc0 = q.mvc0, s.bc0 = q.bc0;
+    if (s.have_inputs) {
+        s.av_cap = q.AV->cap, s.mv_cap = q.MV->cap, s.b_cap = sparse ? 0 : q.B->cap;
+        s.av_m = q.AV->m, s.mv_m = q.MV->m, s.b_m = sparse ? q.SR->m : q.B->m;
     }
-    if (sp)
-        RAILS_LAUNCH((k_lanczos_pass_sparse<NCH, U>), dim3(*nblocks_io), dim3(256), 0, c->stream, a, *sp);
-    else
-        RAILS_LAUNCH((k_lanczos_pass<NCH, U>), dim3(*nblocks_io), dim3(256), 0, c->stream, a);
+    const lz::Verdict v = lz::check(s);
+    RAILS_REQUIRE(v.ok, "%s", v.text);
+    return RAILS_OK;
 }
 
-int lz_unroll()
+// ---- stage 2: the plan
+int lz_unroll_setting() // RAILS_LZ_UNROLL, read once per process
 {
-    static int u = -1;
-    if (u < 0) {
-        const char *e = getenv("RAILS_LZ_UNROLL");
-        u = e ? atoi(e) : 4;
-        if (u != 1 && u != 2 && u != 4) u = 4;
-    }
+    static const int u = lz::unroll_setting(getenv("RAILS_LZ_UNROLL"));
     return u;
 }
 
-int pass_unroll(int nch)
+// blocks of a pass kernel that fit a CU at once: a query, nothing is launched.  false: the query failed.
+bool lz_occupancy(int pass, bool sparse, int *occ)
 {
-    int u = lz_unroll();
-    return (nch >= 3 && u > 2) ? 2 : u;
+    *occ = 0;
+    const void *kernel = sparse ? (const void *)kPassKernels[pass].sparse : (const void *)kPassKernels[pass].dense;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, kernel, 256, 0) == hipSuccess;
 }
 
-void launch_pass(rails_ctx *c, const LzArgs &a, const LzSparse *sp, int nch, int *nblocks_io, bool size_only)
+int lz_plan(const rails_ctx *c, const LzCall &q, lz::Plan *pl)
 {
-    const int u = pass_unroll(nch);
-#define RAILS_LZ_CASE(N, UU) \
-    if (nch == N && u == UU) return launch_pass_u<N, UU>(c, a, sp, nblocks_io, size_only);
-    RAILS_LZ_CASE(1, 1) RAILS_LZ_CASE(1, 2) RAILS_LZ_CASE(1, 4) RAILS_LZ_CASE(2, 1) RAILS_LZ_CASE(2, 2) RAILS_LZ_CASE(2, 4)
-    RAILS_LZ_CASE(3, 1) RAILS_LZ_CASE(3, 2) RAILS_LZ_CASE(4, 1) RAILS_LZ_CASE(4, 2)
-#undef RAILS_LZ_CASE
+    lz::plan_pass(*pl, q.k, lz_unroll_setting());
+    RAILS_REQUIRE(pl->pass >= 0, "rails_resid_lanczos: no pass kernel <%d, %d>: not in the table of instantiations", pl->nch, pl->unroll);
+    int occ = 0;
+    const bool ok = lz_occupancy(pl->pass, q.form == lz::Form::SparseB, &occ);
+    *pl = lz::plan(q.form, q.AV->m, q.k, q.p, q.L, c->num_cu, lz_unroll_setting(), ok, occ);
+    return RAILS_OK;
 }
 
-} // namespace
-
-static int lz_run(rails_ctx *c, const rails_panel *AV, int avc0, const rails_panel *MV, int mvc0, int k, const double *T_host, int ldt,
-                  const rails_panel *B, int bc0, int p, int L, double *H_host, int ldh, int *steps_out, double *start_sums_host,
-                  const rails_sprhs *SR = nullptr)
+// ---- stage 3: the buffers
+// One of the state's two device buffers, made to hold `need` bytes by allocating `alloc` of them.  The stream is synchronised before the
+// old buffer is freed.  A failed allocation leaves no buffer: pointer null, size 0.  (Neither buffer counts in n_dev_alloc.)
+int lz_grow(rails_ctx *c, double **buf, size_t *bytes, size_t need, size_t alloc)
 {
-    // SR: B is a sparse right-hand side (rails_resid_lanczos_sparse; B == nullptr, bc0 == 0, p == SR->p)
-    const bool only_start = (start_sums_host != nullptr);
-    RAILS_REQUIRE(c && AV && MV && (B || SR) && (only_start || (H_host && steps_out)), "rails_resid_lanczos: null argument");
-    RAILS_REQUIRE(k >= 0 && p >= 0 && L >= 1 && (only_start || ldh >= L + 1), "rails_resid_lanczos: bad sizes k=%d p=%d L=%d ldh=%d", k, p, L, ldh);
-    RAILS_REQUIRE(avc0 >= 0 && avc0 + k <= AV->cap && mvc0 >= 0 && mvc0 + k <= MV->cap && bc0 >= 0 && (SR || bc0 + p <= B->cap),
-                  "rails_resid_lanczos: column windows outside capacity");
-    RAILS_REQUIRE(AV->m == MV->m && AV->m == (SR ? SR->m : B->m), "rails_resid_lanczos: row mismatch");
-    RAILS_REQUIRE(((avc0 | mvc0 | bc0) & 1) == 0, "rails_resid_lanczos: column windows must start at even columns");
-    RAILS_REQUIRE(k <= 512 && (SR || p <= 128), "rails_resid_lanczos: fused kernel supports k <= 512, p <= 128 (got %d, %d)", k, p);
-    RAILS_REQUIRE(k == 0 || only_start || (T_host && ldt >= k), "rails_resid_lanczos: bad T");
-    const int64_t m = AV->m;
-    const int64_t mpad = (m + 63) / 64 * 64;
-    rails_lanczos_state &S = lz_state(c);
-    // Lanczos vectors
-    size_t qbytes = (size_t)(L + 2) * (size_t)std::max<int64_t>(mpad, 64) * sizeof(double);
-    if (qbytes > S.qc_bytes) {
-        RAILS_HIP_CHECK(rails_stream_sync(c));
-        if (S.Qc) RAILS_HIP_CHECK(hipFree(S.Qc));
-        S.Qc = nullptr;
-        S.qc_bytes = 0;
-        hipError_t e = hipMalloc((void **)&S.Qc, qbytes);
-        if (e != hipSuccess) {
-            rails_set_error("rails_resid_lanczos: hipMalloc(%zu) failed: %s", qbytes, hipGetErrorString(e));
-            return RAILS_ENOMEM;
-        }
-        S.qc_bytes = qbytes;
+    if (need <= *bytes) return RAILS_OK;
+    RAILS_HIP_CHECK(rails_stream_sync(c));
+    double *old = *buf;
+    *buf = nullptr;
+    *bytes = 0;
+    if (old) RAILS_HIP_CHECK(hipFree(old));
+    const hipError_t e = hipMalloc((void **)buf, alloc);
+    if (e != hipSuccess) {
+        *buf = nullptr;
+        rails_set_error("rails_resid_lanczos: hipMalloc(%zu) failed: %s", alloc, hipGetErrorString(e));
+        return RAILS_ENOMEM;
     }
-    S.m = m;
-    S.mpad = std::max<int64_t>(mpad, 64);
-    S.L = L;
-    S.steps = 0;
-    const int ncoef = 2 * k + p + 1;
-    const int npart = SR ? 2 * k + 1 : ncoef; // entries of a block's partial sums: c'_B of a sparse B is not made by the pass
-    int64_t ngroups = S.mpad / 64;
-    const int nch = std::min(4, std::max(1, (k + 127) / 128));
-    int nblocks = 0;
-    {
-        LzArgs dummy;
-        LzSparse sdummy;
-        launch_pass(c, dummy, SR ? &sdummy : nullptr, nch, &nblocks, true);
+    *bytes = alloc;
+    return RAILS_OK;
+}
+
+// the Lanczos vectors at their exact size, the small block at twice its need (L varies from trip to trip), the blocks' partial sums
+int lz_reserve(rails_ctx *c, rails_lanczos_state &S, const lz::Plan &pl)
+{
+    S.steps = 0; // the vectors of the run before are given up, whatever happens below
+    RAILS_TRY(lz_grow(c, &S.Qc, &S.qc_bytes, pl.vector_bytes, pl.vector_bytes));
+    RAILS_TRY(lz_grow(c, &S.small, &S.small_bytes, pl.small.total * sizeof(double), 2 * pl.small.total * sizeof(double)));
+    RAILS_TRY(rails_ws_reserve(c, pl.ws_bytes));
+    S.m = pl.m;
+    S.mpad = pl.mpad;
+    S.L = pl.L;
+    S.last_nch = pl.nch;
+    S.last_unroll = pl.unroll;
+    S.last_nblocks = pl.nblocks;
+    return RAILS_OK;
+}
+
+// ---- stage 4: T and zeros into the small block, the raw q_0 into Lanczos vector 0
+int lz_begin(rails_ctx *c, const rails_lanczos_state &S, const LzCall &q, const lz::Plan &pl)
+{
+    // rails_pinned_begin_write without rails_pinned_end_write: the upload out of the pinned buffer needs no event of its own, because
+    // every path from here (lz_read_start, lz_read_H, an error return aside) synchronises the stream before the call returns
+    RAILS_TRY(rails_pinned_begin_write(c, pl.pinned_bytes));
+    if (pl.form != lz::Form::StartOnly && q.k) { // T -> device (contiguous k x k)
+        for (int j = 0; j < q.k; ++j) memcpy(c->pinned + (size_t)j * q.k, q.T + (size_t)j * q.ldt, sizeof(double) * q.k);
+        RAILS_HIP_CHECK(hipMemcpyAsync(S.small + pl.small.T, c->pinned, (size_t)q.k * q.k * sizeof(double), hipMemcpyHostToDevice, c->stream));
     }
-    nblocks = (int)std::min<int64_t>((ngroups + 3) / 4, (int64_t)nblocks);
-    if (nblocks < 1) nblocks = 1;
-    S.last_nch = nch;
-    S.last_unroll = pass_unroll(nch);
-    S.last_nblocks = nblocks;
-    // small device block: T | coef | sums | state(8) | alphas(L+2) | betas(L+2)
-    size_t nsmall = (size_t)k * k + ncoef + ncoef + 8 + 2 * (size_t)(L + 2);
-    if (nsmall * sizeof(double) > S.small_bytes) {
-        RAILS_HIP_CHECK(rails_stream_sync(c));
-        if (S.small) RAILS_HIP_CHECK(hipFree(S.small));
-        S.small = nullptr;
-        RAILS_HIP_CHECK(hipMalloc((void **)&S.small, nsmall * sizeof(double) * 2));
-        S.small_bytes = nsmall * sizeof(double) * 2;
-    }
-    double *dT = S.small;
-    double *dcoef = dT + (size_t)k * k;
-    double *dsums = dcoef + ncoef;
-    double *dstate = dsums + ncoef;
-    double *dalpha = dstate + 8;
-    double *dbeta = dalpha + (L + 2);
-    RAILS_TRY(rails_ws_reserve(c, (size_t)nblocks * npart * sizeof(double)));
-    RAILS_TRY(rails_pinned_begin_write(c, std::max<size_t>((size_t)k * k, (size_t)(2 * (L + 2) + 8)) * sizeof(double)));
-    // T -> device (contiguous k x k)
-    if (!only_start) {
-        for (int j = 0; j < k; ++j) memcpy(c->pinned + (size_t)j * k, T_host + (size_t)j * ldt, sizeof(double) * k);
-        if (k) RAILS_HIP_CHECK(hipMemcpyAsync(dT, c->pinned, (size_t)k * k * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    }
-    RAILS_HIP_CHECK(hipMemsetAsync(dcoef, 0, (nsmall - (size_t)k * k) * sizeof(double), c->stream));
+    RAILS_HIP_CHECK(hipMemsetAsync(S.small + pl.small.coef, 0, pl.small.cleared() * sizeof(double), c->stream));
     // start vector: Q.random() consumes one RNG stream (src/LyapunovSolver.hpp:374)
-    {
-        uint64_t stream = c->next_stream++;
-        int grid = (int)std::min<int64_t>((S.mpad + 255) / 256, (int64_t)c->num_cu * 8);
-        RAILS_LAUNCH(k_lz_random, dim3(grid), dim3(256), 0, c->stream, S.Qc, m, S.mpad, c->seed, stream, c->row0);
-    }
-    LzArgs a;
-    a.AV = AV->d + avc0;
-    a.ldav = AV->ld;
-    a.MV = MV->d + mvc0;
-    a.ldmv = MV->ld;
-    a.B = SR ? nullptr : B->d + bc0;
-    a.ldb = SR ? 0 : B->ld;
-    a.k = k;
-    a.p = SR ? 0 : p;
-    a.av_room = AV->ld - avc0;
-    a.mv_room = MV->ld - mvc0;
-    a.b_room = SR ? 0 : B->ld - bc0;
-    a.m = m;
-    a.mpad = S.mpad;
+    const uint64_t stream = c->next_stream++;
+    RAILS_LAUNCH(k_lz_random, dim3(pl.random_grid), dim3(256), 0, c->stream, S.Qc, pl.m, pl.mpad, c->seed, stream, c->row0);
+    return RAILS_OK;
+}
+
+// ---- stage 5: the kernels' arguments, each struct filled here and nowhere else
+LzArgs lz_args(const rails_ctx *c, const rails_lanczos_state &S, const LzCall &q, const lz::Plan &pl)
+{
+    const bool sparse = pl.form == lz::Form::SparseB;
+    LzArgs a{};
+    a.AV = q.AV->d + q.avc0;
+    a.ldav = q.AV->ld;
+    a.MV = q.MV->d + q.mvc0;
+    a.ldmv = q.MV->ld;
+    a.B = sparse ? nullptr : q.B->d + q.bc0;
+    a.ldb = sparse ? 0 : q.B->ld;
+    a.k = pl.k;
+    a.p = sparse ? 0 : pl.p;
+    a.av_room = q.AV->ld - q.avc0;
+    a.mv_room = q.MV->ld - q.mvc0;
+    a.b_room = sparse ? 0 : q.B->ld - q.bc0;
+    a.m = pl.m;
+    a.mpad = pl.mpad;
     a.Qc = S.Qc;
-    a.coef = dcoef;
-    a.state = dstate;
+    a.step = -1;
+    a.coef = S.small + pl.small.coef;
+    a.state = S.small + pl.small.state;
     a.partial = c->ws;
-    LzSparse sp;
-    LzBt bt;
-    if (SR) {
-        sp.rowptr = SR->B->rowptr;
-        sp.col = SR->B->col;
-        sp.val = SR->B->val;
-        sp.gB = dcoef + 2 * k;
-        bt.t_rowptr = SR->Bt->rowptr;
-        bt.t_col = SR->Bt->col;
-        bt.t_val = SR->Bt->val;
-        bt.p = p;
-        bt.nshort = (p + 255) / 256;
-        bt.item_beg = SR->item_beg;
-        bt.item_len = SR->item_len;
-        bt.n_items = SR->n_items;
-        bt.long_row = SR->long_row;
-        bt.long_item0 = SR->long_item0;
-        bt.n_long = SR->n_long;
-        bt.item_partial = SR->item_partial;
-        bt.out = dsums + 2 * k;
-        bt.state = dstate;
+    return a;
+}
+
+LzSparse lz_sparse(const rails_sprhs *SR, const double *gB)
+{
+    LzSparse sp{};
+    sp.rowptr = SR->B->rowptr;
+    sp.col = SR->B->col;
+    sp.val = SR->B->val;
+    sp.gB = gB;
+    return sp;
+}
+
+LzBt lz_bt(const rails_sprhs *SR, const lz::BtGrids &g, double *out, const double *state)
+{
+    LzBt bt{};
+    bt.t_rowptr = SR->Bt->rowptr;
+    bt.t_col = SR->Bt->col;
+    bt.t_val = SR->Bt->val;
+    bt.p = SR->p;
+    bt.nshort = g.nshort;
+    bt.item_beg = SR->item_beg;
+    bt.item_len = SR->item_len;
+    bt.n_items = SR->n_items;
+    bt.long_row = SR->long_row;
+    bt.long_item0 = SR->long_item0;
+    bt.n_long = SR->n_long;
+    bt.item_partial = SR->item_partial;
+    bt.r = nullptr; // per step: the vector the pass has just written
+    bt.out = out;
+    bt.state = state;
+    return bt;
+}
+
+// ---- stage 6: the steps.  Per step: the pass, the reduction of its partials (sparse form: and c'_B = B'r from the vector the pass has
+// just written, the raw q_0 at the start), the all-reduce, and -- but for the start-only form -- k_lz_small.
+int lz_steps(rails_ctx *c, const rails_lanczos_state &S, const LzCall &q, const lz::Plan &pl)
+{
+    const bool sparse = pl.form == lz::Form::SparseB;
+    const PassKernels &pass = kPassKernels[pl.pass];
+    double *dT = S.small + pl.small.T, *dcoef = S.small + pl.small.coef, *dsums = S.small + pl.small.sums, *dstate = S.small + pl.small.state;
+    LzArgs a = lz_args(c, S, q, pl);
+    LzSparse sp{};
+    LzBt bt{};
+    lz::BtGrids g;
+    if (sparse) {
+        g = lz::bt_grids(pl.p, q.SR->n_items, q.SR->n_long);
+        sp = lz_sparse(q.SR, dcoef + 2 * pl.k);
+        bt = lz_bt(q.SR, g, dsums + 2 * pl.k, dstate);
     }
-    for (int step = -1; step < (only_start ? 0 : L); ++step) {
+    for (int step = -1; step < pl.last_step; ++step) {
         a.step = step;
-        launch_pass(c, a, SR ? &sp : nullptr, nch, &nblocks, false);
-        if (SR) { // [c'_AV | c'_MV] and rr from the partials, c'_B = B'r from the vector the pass has just written (the raw q_0 at the start)
-            RAILS_LAUNCH(k_lz_reduce_last_at, dim3((npart + 63) / 64), dim3(1024), 0, c->stream, c->ws, nblocks, npart, dsums, ncoef - 1);
-            bt.r = S.Qc + (size_t)(step + 1) * S.mpad;
-            const int64_t grid = bt.nshort + (bt.n_items + 3) / 4;
-            if (grid > 0) RAILS_LAUNCH(k_sprhs_bt, dim3((unsigned)grid), dim3(256), 0, c->stream, bt);
-            if (bt.n_long > 0) RAILS_LAUNCH(k_sprhs_bt_long, dim3((unsigned)((bt.n_long + 3) / 4)), dim3(256), 0, c->stream, bt);
-        } else
-            RAILS_LAUNCH(k_lz_reduce, dim3((ncoef + 63) / 64), dim3(1024), 0, c->stream, c->ws, nblocks, ncoef, dsums);
-        RAILS_TRY(rails_allreduce_dev(c, dsums, (size_t)ncoef));
-        if (only_start) break;
-        RAILS_LAUNCH(k_lz_small, dim3(1), dim3(1024), 0, c->stream, dsums, dT, k, p, step, dcoef, dstate, dalpha, dbeta);
+        if (sparse) {
+            RAILS_LAUNCH(pass.sparse, dim3(pl.nblocks), dim3(256), 0, c->stream, a, sp);
+            RAILS_LAUNCH(k_lz_reduce_last_at, dim3(pl.partial_grid), dim3(1024), 0, c->stream, c->ws, pl.nblocks, pl.npart, dsums, pl.ncoef - 1);
+            bt.r = S.Qc + (size_t)(step + 1) * pl.mpad;
+            if (g.bt > 0) RAILS_LAUNCH(k_sprhs_bt, dim3((unsigned)g.bt), dim3(256), 0, c->stream, bt);
+            if (g.bt_long > 0) RAILS_LAUNCH(k_sprhs_bt_long, dim3((unsigned)g.bt_long), dim3(256), 0, c->stream, bt);
+        } else {
+            RAILS_LAUNCH(pass.dense, dim3(pl.nblocks), dim3(256), 0, c->stream, a);
+            RAILS_LAUNCH(k_lz_reduce, dim3(pl.partial_grid), dim3(1024), 0, c->stream, c->ws, pl.nblocks, pl.npart, dsums);
+        }
+        RAILS_TRY(rails_allreduce_dev(c, dsums, (size_t)pl.ncoef));
+        if (pl.form == lz::Form::StartOnly) break;
+        RAILS_LAUNCH(k_lz_small, dim3(1), dim3(1024), 0, c->stream, dsums, dT, pl.k, pl.p, step, dcoef, dstate, S.small + pl.small.alphas,
+                     S.small + pl.small.betas);
     }
     RAILS_HIP_CHECK(hipGetLastError());
-    if (only_start) { // [AV^T q0 | MV^T q0 | B^T q0 | q0^T q0], q0 kept (raw) as Lanczos vector 0
-        RAILS_TRY(rails_pinned_reserve(c, (size_t)ncoef * sizeof(double)));
-        RAILS_HIP_CHECK(hipMemcpyAsync(c->pinned, dsums, (size_t)ncoef * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        RAILS_HIP_CHECK(rails_stream_sync(c));
-        memcpy(start_sums_host, c->pinned, (size_t)ncoef * sizeof(double));
-        S.steps = 1;
-        c->n_lanczos_start++;
-        return RAILS_OK;
-    }
-    // read back state, alphas, betas (contiguous)
-    size_t nback = 8 + 2 * (size_t)(L + 2);
-    RAILS_HIP_CHECK(hipMemcpyAsync(c->pinned, dstate, nback * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    return RAILS_OK;
+}
+
+// ---- stage 7, start-only form: [AV^T q0 | MV^T q0 | B^T q0 | q0^T q0], q0 kept (raw) as Lanczos vector 0
+int lz_read_start(rails_ctx *c, rails_lanczos_state &S, const lz::Plan &pl, double *sums_host)
+{
+    RAILS_TRY(rails_pinned_reserve(c, pl.start_pinned_bytes));
+    RAILS_HIP_CHECK(hipMemcpyAsync(c->pinned, S.small + pl.small.sums, (size_t)pl.ncoef * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     RAILS_HIP_CHECK(rails_stream_sync(c));
-    const double *hstate = c->pinned, *halpha = c->pinned + 8, *hbeta = halpha + (L + 2);
-    const bool broke = hstate[3] != 0.0;
-    int steps = broke ? (int)hstate[4] : L;
-    for (int j = 0; j <= L; ++j)
-        for (int i = 0; i <= L; ++i) H_host[i + (size_t)j * ldh] = 0.0; // H = 0.0 (:377)
-    for (int i = 0; i < steps; ++i) {
-        H_host[i + (size_t)i * ldh] = halpha[i]; // :407
-        bool last_broke = broke && (i == steps - 1);
-        if (!last_broke) { // :428-429
-            H_host[(i + 1) + (size_t)i * ldh] = hbeta[i];
-            H_host[i + (size_t)(i + 1) * ldh] = hbeta[i];
-        }
-    }
+    memcpy(sums_host, c->pinned, (size_t)pl.ncoef * sizeof(double));
+    S.steps = 1;
+    c->n_lanczos_start++;
+    return RAILS_OK;
+}
+
+// ---- stage 7, the other forms: state, alphas and betas in one copy (lz::SmallBlock keeps them together), H from them
+int lz_read_H(rails_ctx *c, rails_lanczos_state &S, const lz::Plan &pl, double *H_host, int ldh, int *steps_out)
+{
+    const lz::SmallBlock &b = pl.small;
+    RAILS_HIP_CHECK(hipMemcpyAsync(c->pinned, S.small + b.state, b.read_back() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    RAILS_HIP_CHECK(rails_stream_sync(c));
+    const int steps = lz::assemble_H(H_host, ldh, pl.L, c->pinned, c->pinned + (b.alphas - b.state), c->pinned + (b.betas - b.state));
     S.steps = steps;
     c->n_lanczos++;
     *steps_out = steps;
     return RAILS_OK;
 }
 
+int lz_stages(rails_ctx *c, const LzCall &q)
+{
+    RAILS_TRY(lz_check(c, q));
+    lz::Plan pl;
+    RAILS_TRY(lz_plan(c, q, &pl));
+    rails_lanczos_state &S = lz_state(c);
+    RAILS_TRY(lz_reserve(c, S, pl));
+    RAILS_TRY(lz_begin(c, S, q, pl));
+    RAILS_TRY(lz_steps(c, S, q, pl));
+    if (pl.form == lz::Form::StartOnly) return lz_read_start(c, S, pl, q.start_sums);
+    return lz_read_H(c, S, pl, q.H, q.ldh, q.steps_out);
+}
+
+} // namespace
+
 extern "C" int rails_resid_lanczos(rails_ctx *c, const rails_panel *AV, int avc0, const rails_panel *MV, int mvc0, int k,
                                    const double *T_host, int ldt, const rails_panel *B, int bc0, int p, int L, double *H_host,
                                    int ldh, int *steps_out)
 {
     if (c) hipSetDevice(c->device); // allocations and launches go to the context's device whatever the caller's current device is
-    return lz_run(c, AV, avc0, MV, mvc0, k, T_host, ldt, B, bc0, p, L, H_host, ldh, steps_out, nullptr);
+    return lz_stages(c, LzCall{lz::Form::DenseB, AV, avc0, MV, mvc0, k, T_host, ldt, B, bc0, p, nullptr, L, H_host, ldh, steps_out, nullptr});
 }
 
 extern "C" int rails_resid_lanczos_sparse(rails_ctx *c, const rails_panel *AV, int avc0, const rails_panel *MV, int mvc0, int k,
@@ -609,7 +662,7 @@ extern "C" int rails_resid_lanczos_sparse(rails_ctx *c, const rails_panel *AV, i
     if (c) hipSetDevice(c->device); // allocations and launches go to the context's device whatever the caller's current device is
     RAILS_REQUIRE(c && SR, "rails_resid_lanczos_sparse: null argument");
     RAILS_REQUIRE(c == SR->ctx && c->nranks == 1 && !c->rccl, "rails_resid_lanczos_sparse: single GPU only, on the context the right-hand side was made on");
-    return lz_run(c, AV, avc0, MV, mvc0, k, T_host, ldt, nullptr, 0, SR->p, L, H_host, ldh, steps_out, nullptr, SR);
+    return lz_stages(c, LzCall{lz::Form::SparseB, AV, avc0, MV, mvc0, k, T_host, ldt, nullptr, 0, SR->p, SR, L, H_host, ldh, steps_out, nullptr});
 }
 
 extern "C" int rails_lanczos_start(rails_ctx *c, const rails_panel *AV, int avc0, const rails_panel *MV, int mvc0, int k,
@@ -617,7 +670,7 @@ extern "C" int rails_lanczos_start(rails_ctx *c, const rails_panel *AV, int avc0
 {
     if (c) hipSetDevice(c->device); // allocations and launches go to the context's device whatever the caller's current device is
     RAILS_REQUIRE(sums_host, "rails_lanczos_start: null output");
-    return lz_run(c, AV, avc0, MV, mvc0, k, nullptr, 0, B, bc0, p, 1, nullptr, 0, nullptr, sums_host);
+    return lz_stages(c, LzCall{lz::Form::StartOnly, AV, avc0, MV, mvc0, k, nullptr, 0, B, bc0, p, nullptr, 1, nullptr, 0, nullptr, sums_host});
 }
 
 extern "C" int rails_lanczos_vectors(rails_ctx *c, const double *S_host, int lds, int w, rails_panel *Out, int oc0)
@@ -632,15 +685,17 @@ extern "C" int rails_lanczos_vectors(rails_ctx *c, const double *S_host, int lds
     RAILS_REQUIRE(w == 0 || (S_host && lds >= S.steps), "rails_lanczos_vectors: bad coefficient matrix");
     if (w == 0 || S.m == 0) return RAILS_OK;
     const int steps = S.steps;
-    size_t n = (size_t)steps * w;
-    RAILS_TRY(rails_small_reserve(c, n * sizeof(double)));
-    RAILS_TRY(rails_pinned_begin_write(c, n * sizeof(double)));
+    const lz::VectorsPlan v = lz::vectors_plan(S.m, steps, w);
+    RAILS_TRY(rails_small_reserve(c, v.s_bytes));
+    // rails_pinned_begin_write without rails_pinned_end_write: the stream is synchronised below, before this function returns, so the
+    // upload out of the pinned buffer needs no event of its own
+    RAILS_TRY(rails_pinned_begin_write(c, v.s_bytes));
     for (int j = 0; j < w; ++j) memcpy(c->pinned + (size_t)j * steps, S_host + (size_t)j * lds, sizeof(double) * steps);
-    RAILS_HIP_CHECK(hipMemcpyAsync(c->small, c->pinned, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    for (int j0 = 0; j0 < w; j0 += 16) {
-        int wc = std::min(16, w - j0);
-        RAILS_LAUNCH(k_lz_vectors, dim3((unsigned)((S.m + 255) / 256)), dim3(256), (size_t)steps * 16 * sizeof(double), c->stream,
-                           S.Qc, S.mpad, S.m, steps, c->small + (size_t)j0 * steps, steps, wc, Out->d + oc0 + j0, Out->ld);
+    RAILS_HIP_CHECK(hipMemcpyAsync(c->small, c->pinned, v.s_bytes, hipMemcpyHostToDevice, c->stream));
+    for (int ch = 0; ch < v.nchunks; ++ch) {
+        const int j0 = v.first(ch);
+        RAILS_LAUNCH(k_lz_vectors, dim3(v.grid), dim3(256), lz::vectors_lds_bytes(steps), c->stream, S.Qc, S.mpad, S.m, steps,
+                     c->small + (size_t)j0 * steps, steps, v.width(ch), Out->d + oc0 + j0, Out->ld);
     }
     RAILS_HIP_CHECK(hipGetLastError());
     RAILS_HIP_CHECK(rails_stream_sync(c));

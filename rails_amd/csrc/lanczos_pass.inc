@@ -5,16 +5,16 @@
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const bool init = a.step < 0;
-    const double done = a.state[3];
+    const double done = a.state[lz::DONE];
     const int ncoef = 2 * a.k + a.p + 1;
     double *myp = a.partial + (int64_t)blockIdx.x * ncoef;
     if (done != 0.0) {
         for (int i = threadIdx.x; i < ncoef; i += 256) myp[i] = 0.0;
         return;
     }
-    const double alpha = init ? 0.0 : a.state[0];
-    const double betap = init ? 0.0 : a.state[1];
-    const double invb = init ? 1.0 : a.state[2];
+    const double alpha = init ? 0.0 : a.state[lz::ALPHA];
+    const double betap = init ? 0.0 : a.state[lz::BETA_PREV];
+    const double invb = init ? 1.0 : a.state[lz::INV_BETA];
 
     v2f64 gav[NCH], gmv[NCH], gb;
     bool ok0[NCH], ok1[NCH];

@@ -4,7 +4,9 @@ C ABI, algorithmic bytes / flops (SURVEY.md 8(d) formulas), achieved GB/s and TF
 Run under `rocprofv3 --kernel-trace --stats` for pure kernel durations and under `--pmc SQ_VALU_MFMA_BUSY_CYCLES ...` for the
 MFMA utilisation of the projection kernels (scripts/gpu_kernels.sh).
 
-    python scripts/kernel_bench.py [--m 1000000] [--reps 10] [--pattern banded]"""
+    python scripts/kernel_bench.py [--m 1000000] [--reps 10] [--pattern banded] [--only TEXT]
+
+--only TEXT runs the cases whose name contains TEXT and nothing else (--only lanczos: the two Lanczos lines)."""
 import argparse
 import json
 import os
@@ -21,6 +23,7 @@ def main():
     ap.add_argument("--m", type=int, default=1000000)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--pattern", default="banded")
+    ap.add_argument("--only", default="", help="run only the cases whose name contains this")
     args = ap.parse_args()
     import rails_amd
     from rails_amd import problems as P
@@ -30,7 +33,12 @@ def main():
     ctx = rails_amd.Context(device=0, seed=3)
     lib = ctx.lib
 
+    def wanted(name):
+        return args.only in name
+
     def timed(name, fn, bytes_alg, flops, note=""):
+        if not wanted(name):
+            return
         fn()
         ctx.sync()
         samples = []
@@ -97,14 +105,19 @@ def main():
     timed("lanczos_start k=200 p=16 (projected form: one pass)",
           lambda: lib.rails_lanczos_start(ctx.h, AV.panel.h, 0, V.panel.h, 0, 200, B.panel.h, 0, 16, rails_amd.wrappers._p(sums)), (2 * 200 + 16 + 1) * m * S, 0)
     # ---- orthogonalisation (a7) ---------------------------------------------------------------------------------
+    if not wanted("orthogonalize") and not wanted("spmm"):
+        ctx.close()
+        return
     Vo = panel(184, 216)
     Vo.orthogonalize()
+
     def orth():
         Vo.resize(184)
         Vo.orthogonalized = 184
         Vo.resize(200)
         Vo.view(184, 199).random()
         return Vo.orthogonalize()
+
     timed("orthogonalize k_old=184 w=16 (block CGS2 + CholQR2, incl. the random refill)", orth, (4 * 184 + 6 * 16) * m * S, 2.0 * m * (4 * 184 * 16 + 4 * 16 * 16))
     # ---- SpMM (a2) ----------------------------------------------------------------------------------------------
     if args.pattern == "banded":

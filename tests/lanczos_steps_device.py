@@ -92,7 +92,8 @@ def run_case(ctx, c):
 
 
 def expected_kernel(k):
-    """what launch_pass selects: NCH = ceil(k / 128) in 1..4, U from RAILS_LZ_UNROLL (default 4), at most 2 rows in flight for NCH >= 3"""
+    """the pass kernel a run takes, stated here independently of rails_amd/csrc/lanczos_plan.h: NCH = ceil(k / 128) in 1..4, U from
+    RAILS_LZ_UNROLL (default 4), at most 2 rows in flight for NCH >= 3"""
     nch = min(4, max(1, (k + 127) // 128))
     u = int(os.environ.get("RAILS_LZ_UNROLL", "4"))
     if u not in (1, 2, 4):

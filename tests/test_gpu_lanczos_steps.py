@@ -62,6 +62,31 @@ def test_grid_stride_loop_makes_a_second_trip(ctx):
     assert out["steps"] == c["L"]
 
 
+def _launched(ctx, c):
+    """the launch rails_lanczos_last_launch reports after one run of a case (the run's results are other tests' business)"""
+    parts = R.make_case(c)
+    AV, MVw, B = D.upload(ctx, c, parts)
+    ctx.set_seed(c["seed"], c["stream"])
+    rc, _, steps = D.call(ctx, AV, MVw, B, parts["T"], c["L"])
+    assert rc == 0 and 1 <= steps <= c["L"]
+    return D.last_launch(ctx)
+
+
+def test_grid_follows_the_plan_rule(ctx):
+    """nblocks = max(1, min(ceil(ngroups / 4), num_cu * occ)) with ngroups = max(ceil(m / 64), 1) row groups and occ resident blocks per
+    CU, 1..4 (rails_amd/csrc/lanczos_plan.h): one block up to four groups, two for five, and no more than are resident however many rows"""
+    num_cu = ctx.lib.rails_ctx_num_cu(ctx.h)
+    assert num_cu >= 1
+    for c in R.cases("tiny"):  # m = 1, 63, 64, 65: one or two groups
+        assert _launched(ctx, c)[2] == 1, R.case_id(c)
+    five = dict(R.cases("tiny")[0], name="m300", m=300)  # 320 padded rows: five groups, the fifth in a second block
+    assert _launched(ctx, five)[2] == 2
+    (c,) = R.cases("grid_stride")  # 8196 groups: far more sets of four than blocks fit the device
+    nblocks = _launched(ctx, c)[2]
+    assert nblocks % num_cu == 0 and 1 <= nblocks // num_cu <= 4, (nblocks, num_cu)
+    assert nblocks < (c["m"] + 63) // 64 // 4
+
+
 def test_all_ten_instantiations_in_fresh_processes():
     """RAILS_LZ_UNROLL is read once per process: one child per U runs the "instantiations" cases (both ends of every NCH range), asserts
     the bounds and the kernel that was launched; the children run one after another and nothing is started after one that fails"""
