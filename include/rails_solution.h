@@ -29,6 +29,21 @@ int rails_panel_rowquad(rails_ctx *ctx, const rails_panel *U, int c0, int k, con
 /* What the context's last rails_panel_rowquad launched: *nslices slices of S (0 for k = 0, for a panel without rows, or before any call) and, for
  * the first min(cap, *nslices) of them, the template parameter TR of k_panel_rowquad<TR> (2, 4, 8, 12 or 16 column tiles of 16). */
 int rails_panel_rowquad_last_plan(const rails_ctx *ctx, int *nslices, int *tr, int cap);
+/* out[i] = U[ia[i], c0:c0+k] S U[ib[i], c0:c0+k]'  for i < n  ( = X[ia[i], ib[i]] ).  ia, ib: n LOCAL row indices on the HOST, checked against
+ * U's rows before anything is queued; either may be NULL = the identity (then n <= rows of U).  Out has at least n rows; rows from n on
+ * and every other column are left alone.  S as in rails_panel_rowquad (as given, need not be symmetric), k <= 512.  The kernel is
+ * rails_panel_rowquad's body on gathered rows -- one pass, no n x k temporary, the same slices (reported through
+ * rails_panel_rowquad_last_plan) and the same fixed summation order: a pair's bits do not depend on its place i or on n, and with both
+ * indices the identity they are rails_panel_rowquad's.  Out may be U's panel when column oc0 lies outside the window.  n == 0 or a panel
+ * without rows: nothing is queued; k == 0: zeros in the n rows.  Asynchronous. */
+int rails_panel_rowpair(rails_ctx *ctx, const rails_panel *U, int c0, int k, const double *S_host, int lds, const int32_t *ia, const int32_t *ib, int64_t n,
+                        rails_panel *Out, int oc0);
+/* host[0..n) summed over the ranks of the partition with the context's all-reduce (the one rails_gram uses).  One rank with neither a hook
+ * nor a communicator: returns at once, nothing queued.  Synchronises otherwise. */
+int rails_allreduce_host(rails_ctx *ctx, double *host, int64_t n);
+/* Covariances to correlations: Out[i, oc0+j] /= sqrt(Var[i, vc]) sqrt(rv[j]) for j < q <= 64; 0 wherever either variance is not > 0; exactly 1
+ * where i == rows[j] (an unknown with itself) and its variance is > 0.  rv, rows: q host entries (rows[j] = -1: not a local row).  Asynchronous. */
+int rails_panel_corr_scale(rails_ctx *ctx, rails_panel *Out, int oc0, int q, const rails_panel *Var, int vc, const double *rv_host, const int32_t *rows_host);
 
 /* U = columns [c0, c0+k) of the panel; copy != 0: the object keeps a device copy of them, copy == 0: it borrows the panel (the caller
  * keeps it alive and unchanged).  S_host column-major k x k, leading dimension lds; it is copied and symmetrised ((S + S')/2). */
@@ -58,6 +73,17 @@ int rails_solution_eigs(rails_solution *sol, int want, double tol, double *value
 /* out (nr x nc, column-major, leading dimension ld) = X[rows, cols] (local row indices): the rows are gathered on the device, the small
  * product is done on the host.  For spot checks and sections. */
 int rails_solution_block(rails_solution *sol, const int32_t *rows, int nr, const int32_t *cols, int nc, double *out, int ld);
+/* out[i, c0] = X[ia[i], ib[i]] for i < n (rails_panel_rowpair: LOCAL indices on the host, either may be NULL = the identity; out has at least
+ * n rows).  The covariance of pairs of unknowns at scale: the eddy-flux field of two variables per cell, a section's neighbour covariances. */
+int rails_solution_pairs(rails_solution *sol, const int32_t *ia, const int32_t *ib, int64_t n, rails_panel *out, int c0);
+/* Out[:, oc0+j] = X[:, r_j] for q reference unknowns (correlation == 0), or X[i, r_j] / sqrt(X[i,i] X[r_j,r_j]) (correlation != 0; 0 wherever
+ * either variance is not > 0, exactly 1 at the reference unknown's own row when its variance is > 0).  rows[j]: LOCAL index of reference
+ * unknown j on the rank that owns it, -1 on every other rank (one GPU: all >= 0).  q <= 64.  var_col >= 0: that column of Out (outside
+ * [oc0, oc0+q)) also receives diag(X).  A composition: the q rows are gathered (rails_panel_move_rows), G = S U[r,:]' (k x q) is formed on the
+ * host and summed over the ranks together with an owner count per reference unknown -- one that no rank or several ranks claim is refused
+ * with RAILS_EINVAL on every rank alike, nothing written -- then Out = U G (rails_panel_gemm); correlations add rails_solution_variance,
+ * the q reference variances read from their owners' variance column (summed the same way) and rails_panel_corr_scale.  Synchronises. */
+int rails_solution_maps(rails_solution *sol, const int32_t *rows, int q, int correlation, rails_panel *Out, int oc0, int var_col);
 
 #ifdef __cplusplus
 }

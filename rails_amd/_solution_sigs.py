@@ -10,6 +10,11 @@ SOLUTION_SIGNATURES = {
     "rails_panel_move_rows": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _i32p, C.c_int64, C.c_int, _vp, C.c_int]),
     "rails_panel_rowquad": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _dp, C.c_int, _vp, C.c_int]),
     "rails_panel_rowquad_last_plan": (C.c_int, [_vp, _ip, _ip, C.c_int]),
+    "rails_panel_rowpair": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _dp, C.c_int, _i32p, _i32p, C.c_int64, _vp, C.c_int]),
+    "rails_allreduce_host": (C.c_int, [_vp, _dp, C.c_int64]),
+    "rails_panel_corr_scale": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _dp, _i32p]),
+    "rails_solution_pairs": (C.c_int, [_vp, _i32p, _i32p, C.c_int64, _vp, C.c_int]),
+    "rails_solution_maps": (C.c_int, [_vp, _i32p, C.c_int, C.c_int, _vp, C.c_int, C.c_int]),
     "rails_solution_create": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.POINTER(_vp)]),
     "rails_solution_from_solver": (C.c_int, [_vp, C.POINTER(_vp)]),
     "rails_solution_destroy": (C.c_int, [_vp]),

@@ -13,9 +13,17 @@
 // ones adding to `out` (stream order).  Extra device memory: the packed S (k x (k + 4) doubles at most per slice) and the m results.
 //
 // 8 waves x 16 rows per workgroup; LDS is 2 x 32 x (16 TR + 4) doubles: 66 KiB at k = 128 (two workgroups per CU), 130 KiB at 256.
+//
+//   rails_panel_rowpair   out[i] = sum_{j,l} U[ia_i,j] S[j,l] U[ib_i,l] = X[ia_i, ib_i]
+// is the same body (solution_rowform.inc, included once in each kernel) on gathered rows: the wave's A-operand rows are rows ia[.], the
+// epilogue multiplies the accumulator tile with rows ib[.].  Same slices, instantiations, packed S, double buffer and summation order; the
+// row form is the case ia = ib = identity of it and keeps its code.  The indices are checked on the host and ride behind S in the call's one
+// staged upload.
 #include "rails_internal.h"
 
 #include <algorithm>
+#include <initializer_list>
+#include <type_traits>
 
 namespace {
 
@@ -34,121 +42,139 @@ __global__ void k_pack_s(const double *__restrict__ S, int lds, int k, int r, in
     }
 }
 
+// Which rows of U result i of the shared body (solution_rowform.inc) reads: its own (the row form, n = rows of U) ...
+struct SameRows {
+    int64_t n;
+    __device__ __forceinline__ int64_t a(int64_t i) const { return i; }
+    __device__ __forceinline__ int64_t b(int64_t i) const { return i; }
+};
+// ... or rows ia[i] and ib[i] (the pair form).  The indices were checked on the host.  An identity side (a null array in the call) has its
+// flag clear and its pointer at any readable int32: the load is unconditional and its value unused, so that the body stays free of branches
+// (with one, the compiler issues the epilogue's loads of U a result group at a time around it and runs out of registers at TR = 16).
+struct PairRows {
+    const int32_t *ia, *ib;
+    int64_t n;
+    int use_a, use_b;
+    __device__ __forceinline__ int64_t a(int64_t i) const
+    {
+        const int32_t t = ia[use_a ? i : 0];
+        return use_a ? (int64_t)t : i;
+    }
+    __device__ __forceinline__ int64_t b(int64_t i) const
+    {
+        const int32_t t = ib[use_b ? i : 0];
+        return use_b ? (int64_t)t : i;
+    }
+};
+
 // out[row] (+)= sum_{j < r} (sum_{l < k} U[row, l] St[l, j]) U[row, j0 + j]; U points at the first column of the window, St is the packed slice
 template <int TR>
 __global__ __launch_bounds__(512) void k_panel_rowquad(const double *__restrict__ U, int ldu, int k, const double *__restrict__ St /* packed, kpad x RL */, int j0, int r,
                                                        double *__restrict__ out, int ldo, int64_t m, int vec_ok, int accumulate)
 {
-    constexpr int KC = 32, RL = 16 * TR + 4, CHUNK_B = KC * RL * 8, PIECES = CHUNK_B / 1024;
-    static_assert(CHUNK_B % 1024 == 0, "whole LDS-DMA pieces per chunk");
-    extern __shared__ double Cs[]; // 2 x KC x RL
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int li = lane & 15, kk = lane >> 4;
-    const int64_t r0 = ((int64_t)blockIdx.x * 8 + wave) * 16;
-    const int64_t myrow = r0 + li;
-    const bool rowok = myrow < m;
-    const int nchunks = (k + KC - 1) / KC;
-    const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)Cs;
-    const uint32_t lane16 = (uint32_t)lane * 16u;
-    auto stage = [&](int chunk) { // this wave's pieces of a chunk: piece p goes to wave p % 8
-        const char *src = reinterpret_cast<const char *>(St) + (size_t)chunk * CHUNK_B;
-        const uint32_t dst = lds_base + (uint32_t)((chunk & 1) * CHUNK_B);
-        for (int p = wave; p < PIECES; p += 8) {
-            uint32_t keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(lane16), "s"(src + (size_t)p * 1024), "s"(dst + (uint32_t)(p * 1024)) : "memory");
-        }
-    };
-    v4f64 acc[TR];
-#pragma unroll
-    for (int t = 0; t < TR; ++t) acc[t] = (v4f64){0.0, 0.0, 0.0, 0.0};
-    const double *xrow = U + (rowok ? myrow : m - 1) * ldu; // rows past the end read the last row; their results are never written
-    auto fetch = [&](int kcol, double *xs) {
-        if (vec_ok && kcol + 4 <= k) {
-            v2f64 t0 = *reinterpret_cast<const v2f64 *>(xrow + kcol);
-            v2f64 t1 = *reinterpret_cast<const v2f64 *>(xrow + kcol + 2);
-            xs[0] = t0.x;
-            xs[1] = t0.y;
-            xs[2] = t1.x;
-            xs[3] = t1.y;
-        } else {
-#pragma unroll
-            for (int s = 0; s < 4; ++s) xs[s] = (kcol + s < k) ? xrow[kcol + s] : 0.0;
-        }
-    };
-    double xa[4], xb[4];
-    stage(0);
-    fetch(4 * kk, xa);
-    fetch(16 + 4 * kk, xb);
-    asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
-    __builtin_amdgcn_s_barrier();
-    for (int ci = 0; ci < nchunks; ++ci) {
-        if (ci + 1 < nchunks) stage(ci + 1); // into the buffer every wave left at the barrier above
-        double xc[4], xd[4];
-        fetch((ci + 1) * KC + 4 * kk, xc); // past k: zeros, no load
-        fetch((ci + 1) * KC + 16 + 4 * kk, xd);
-        const double *cb = Cs + (size_t)(ci & 1) * (KC * RL);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const double *crow = &cb[(4 * kk + s) * RL + li];
-#pragma unroll
-            for (int t = 0; t < TR; ++t) acc[t] = mfma_f64(xa[s], crow[16 * t], acc[t]);
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const double *crow = &cb[(16 + 4 * kk + s) * RL + li];
-#pragma unroll
-            for (int t = 0; t < TR; ++t) acc[t] = mfma_f64(xb[s], crow[16 * t], acc[t]);
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            xa[s] = xc[s];
-            xb[s] = xd[s];
-        }
-        // the next chunk has landed (this wave's pieces; then everybody's) and nobody reads this chunk's buffer any more
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" : : : "memory");
-        __builtin_amdgcn_s_barrier();
-    }
-    // P[row kk + 4v][column 16t + li] is in acc[t][v]: times U at the same place, summed over the columns
-    double q[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-        const int64_t row = r0 + kk + 4 * v;
-        const double *urow = U + (row < m ? row : m - 1) * ldu + j0;
-#pragma unroll
-        for (int t = 0; t < TR; ++t) {
-            const int j = 16 * t + li;
-            const double u = urow[j < r ? j : 0]; // columns past the slice: acc is zero there (zero padding of the packed S)
-            q[v] += acc[t][v] * (j < r ? u : 0.0);
-        }
-    }
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-#pragma unroll
-        for (int off = 1; off < 16; off <<= 1) q[v] += __shfl_xor(q[v], off, 64);
-    }
-    if (li == 0) {
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int64_t row = r0 + kk + 4 * v;
-            if (row >= m) continue;
-            double *dst = out + row * ldo;
-            *dst = accumulate ? *dst + q[v] : q[v];
-        }
-    }
+    const SameRows Rw{m};
+#include "solution_rowform.inc"
 }
 
+// out[i] (+)= sum_{j < r} (sum_{l < k} U[ia[i], l] St[l, j]) U[ib[i], j0 + j], i < n: the same body on gathered rows.  The four row pointers of
+// the epilogue cost a few registers more than the row form's one; up to TR = 8 the kernel is told to stay at the row form's four waves per
+// SIMD (two workgroups per CU, which is what the LDS of TR = 8 allows)
 template <int TR>
-int launch_rowquad(rails_ctx *c, const double *U, int ldu, int k, const double *S_dev, int j0, int r, double *out, int ldo, int64_t m, int vec_ok, int accumulate, double *st)
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(TR <= 8 ? 4 : 2))) void k_panel_rowpair(const double *__restrict__ U, int ldu, int k, const double *__restrict__ St /* packed, kpad x RL */, int j0, int r,
+                                                       double *__restrict__ out, int ldo, const int32_t *__restrict__ ia, const int32_t *__restrict__ ib, int64_t n, int use_a,
+                                                       int use_b, int vec_ok, int accumulate)
+{
+    const PairRows Rw{ia, ib, n, use_a, use_b};
+#include "solution_rowform.inc"
+}
+
+__global__ void k_zero_rows(double *__restrict__ out, int ldo, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i * ldo] = 0.0;
+}
+
+// Out[i, j] <- Out[i, j] / (sqrt(var[i]) sqrt(rv[j])), 0 where either variance is not > 0, and exactly 1 where row i IS reference unknown j
+// (rows[j] == i) and its variance is > 0: the covariance map becomes the correlation map
+__global__ void k_corr_scale(double *__restrict__ out, int ldo, int64_t m, int q, const double *__restrict__ var, int ldv, const double *__restrict__ rv,
+                             const int32_t *__restrict__ rows)
+{
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= m * q) return;
+    const int64_t i = e / q;
+    const int j = (int)(e % q);
+    const double vi = var[i * ldv], vj = rv[j];
+    double *dst = out + i * ldo + j;
+    if (!(vi > 0.0) || !(vj > 0.0))
+        *dst = 0.0;
+    else
+        *dst = ((int64_t)rows[j] == i) ? 1.0 : *dst / (sqrt(vi) * sqrt(vj));
+}
+
+// one slice of either form: pack the slice of S, launch the instantiation, note it for rails_panel_rowquad_last_plan
+template <int TR, class Rows>
+int launch_rowquad(rails_ctx *c, const double *U, int ldu, int k, const double *S_dev, int j0, int r, double *out, int ldo, Rows rw, int vec_ok, int accumulate, double *st)
 {
     constexpr int RL = 16 * TR + 4;
     const int kpad = (k + 31) / 32 * 32;
     RAILS_LAUNCH(k_pack_s, dim3((unsigned)std::min<int64_t>(512, ((int64_t)kpad * RL + 255) / 256)), dim3(256), 0, c->stream, S_dev + (size_t)j0 * k, k, k, r, kpad, RL, st);
     const size_t lds = (size_t)2 * 32 * RL * sizeof(double);
-    RAILS_HIP_CHECK(hipFuncSetAttribute((const void *)k_panel_rowquad<TR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    RAILS_LAUNCH((k_panel_rowquad<TR>), dim3((unsigned)((m + 127) / 128)), dim3(512), lds, c->stream, U, ldu, k, st, j0, r, out, ldo, m, vec_ok, accumulate);
+    const dim3 grid((unsigned)((rw.n + 127) / 128));
+    if constexpr (std::is_same<Rows, SameRows>::value) {
+        RAILS_HIP_CHECK(hipFuncSetAttribute((const void *)k_panel_rowquad<TR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        RAILS_LAUNCH((k_panel_rowquad<TR>), grid, dim3(512), lds, c->stream, U, ldu, k, st, j0, r, out, ldo, rw.n, vec_ok, accumulate);
+    } else {
+        RAILS_HIP_CHECK(hipFuncSetAttribute((const void *)k_panel_rowpair<TR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        RAILS_LAUNCH((k_panel_rowpair<TR>), grid, dim3(512), lds, c->stream, U, ldu, k, st, j0, r, out, ldo, rw.ia, rw.ib, rw.n, rw.use_a, rw.use_b, vec_ok, accumulate);
+    }
     c->last_rowquad_tr[c->last_rowquad_nslices++] = TR; // k <= 512: two slices at most
+    return RAILS_OK;
+}
+
+// S (k x k, leading dimension lds) and the pair form's index arrays (n entries each; null: none) go to the device once, through the pinned
+// staging buffer into the context's small buffer (re-used in stream order): S first, then each array on an 8-byte boundary.  *ia_dev and
+// *ib_dev (may be null pointers-to) receive where the arrays will be.
+int stage_small(rails_ctx *c, int k, const double *S_host, int lds, const int32_t *ia, const int32_t *ib, int64_t n, const int32_t **ia_dev, const int32_t **ib_dev)
+{
+    const size_t ns = (size_t)k * k, each = ((size_t)n * sizeof(int32_t) + 7) / 8, na = ia ? each : 0, nb = ib ? each : 0; // in doubles
+    const size_t bytes = (ns + na + nb) * sizeof(double);
+    RAILS_TRY(rails_small_reserve(c, bytes));
+    RAILS_TRY(rails_pinned_begin_write(c, bytes));
+    for (int j = 0; j < k; ++j) memcpy(c->pinned + (size_t)j * k, S_host + (size_t)j * lds, sizeof(double) * k);
+    if (ia) memcpy(c->pinned + ns, ia, (size_t)n * sizeof(int32_t));
+    if (ib) memcpy(c->pinned + ns + na, ib, (size_t)n * sizeof(int32_t));
+    RAILS_HIP_CHECK(hipMemcpyAsync(c->small, c->pinned, bytes, hipMemcpyHostToDevice, c->stream));
+    if (ia_dev) *ia_dev = ia ? reinterpret_cast<const int32_t *>(c->small + ns) : nullptr;
+    if (ib_dev) *ib_dev = ib ? reinterpret_cast<const int32_t *>(c->small + ns + na) : nullptr;
+    return rails_pinned_end_write(c);
+}
+
+// the slices of either form, S already in c->small: equal widths, at most 256 columns of S (16 tiles of 16: the accumulators of a wave), one
+// launch each, the later ones adding to the output column (stream order)
+template <class Rows>
+int rowform_slices(rails_ctx *c, const rails_panel *U, int c0, int k, Rows rw, double *od, int ldo)
+{
+    const int nslices = (k + 255) / 256, width = ((k + nslices - 1) / nslices + 15) / 16 * 16;
+    const size_t st_doubles = (size_t)((k + 31) / 32 * 32) * (16 * 16 + 4);
+    RAILS_TRY(rails_ws_reserve(c, (size_t)nslices * st_doubles * sizeof(double)));
+    const double *Ud = U->d + c0;
+    const int vec_ok = ((((uintptr_t)Ud) & 15) == 0 && (U->ld % 2) == 0) ? 1 : 0;
+    int slice = 0;
+    for (int j0 = 0; j0 < k; j0 += width, ++slice) {
+        const int nc = std::min(width, k - j0), tiles = (nc + 15) / 16, acc = slice > 0 ? 1 : 0;
+        double *st = c->ws + (size_t)slice * st_doubles;
+        if (tiles <= 2)
+            RAILS_TRY((launch_rowquad<2>(c, Ud, U->ld, k, c->small, j0, nc, od, ldo, rw, vec_ok, acc, st)));
+        else if (tiles <= 4)
+            RAILS_TRY((launch_rowquad<4>(c, Ud, U->ld, k, c->small, j0, nc, od, ldo, rw, vec_ok, acc, st)));
+        else if (tiles <= 8)
+            RAILS_TRY((launch_rowquad<8>(c, Ud, U->ld, k, c->small, j0, nc, od, ldo, rw, vec_ok, acc, st)));
+        else if (tiles <= 12)
+            RAILS_TRY((launch_rowquad<12>(c, Ud, U->ld, k, c->small, j0, nc, od, ldo, rw, vec_ok, acc, st)));
+        else
+            RAILS_TRY((launch_rowquad<16>(c, Ud, U->ld, k, c->small, j0, nc, od, ldo, rw, vec_ok, acc, st)));
+    }
+    RAILS_HIP_CHECK(hipGetLastError());
     return RAILS_OK;
 }
 
@@ -168,36 +194,43 @@ extern "C" int rails_panel_rowquad(rails_ctx *c, const rails_panel *U, int c0, i
     c->last_rowquad_nslices = 0;
     if (U->m == 0) return RAILS_OK;
     if (k == 0) return rails_panel_fill(c, Out, oc0, 1, 0.0);
-    // S goes to the device once, through the pinned staging buffer into the context's small buffer (re-used in stream order)
-    const size_t n = (size_t)k * k;
-    RAILS_TRY(rails_small_reserve(c, n * sizeof(double)));
-    RAILS_TRY(rails_pinned_begin_write(c, n * sizeof(double)));
-    for (int j = 0; j < k; ++j) memcpy(c->pinned + (size_t)j * k, S_host + (size_t)j * lds, sizeof(double) * k);
-    RAILS_HIP_CHECK(hipMemcpyAsync(c->small, c->pinned, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    RAILS_TRY(rails_pinned_end_write(c));
-    // slices of equal width, at most 256 columns of S (16 tiles of 16: the accumulators of a wave)
-    const int nslices = (k + 255) / 256, width = ((k + nslices - 1) / nslices + 15) / 16 * 16;
-    const size_t st_doubles = (size_t)((k + 31) / 32 * 32) * (16 * 16 + 4);
-    RAILS_TRY(rails_ws_reserve(c, (size_t)nslices * st_doubles * sizeof(double)));
-    const double *Ud = U->d + c0;
-    const int vec_ok = ((((uintptr_t)Ud) & 15) == 0 && (U->ld % 2) == 0) ? 1 : 0;
-    double *od = Out->d + oc0;
-    int slice = 0;
-    for (int j0 = 0; j0 < k; j0 += width, ++slice) {
-        const int nc = std::min(width, k - j0), tiles = (nc + 15) / 16, acc = slice > 0 ? 1 : 0;
-        double *st = c->ws + (size_t)slice * st_doubles;
-        if (tiles <= 2)
-            RAILS_TRY((launch_rowquad<2>(c, Ud, U->ld, k, c->small, j0, nc, od, Out->ld, U->m, vec_ok, acc, st)));
-        else if (tiles <= 4)
-            RAILS_TRY((launch_rowquad<4>(c, Ud, U->ld, k, c->small, j0, nc, od, Out->ld, U->m, vec_ok, acc, st)));
-        else if (tiles <= 8)
-            RAILS_TRY((launch_rowquad<8>(c, Ud, U->ld, k, c->small, j0, nc, od, Out->ld, U->m, vec_ok, acc, st)));
-        else if (tiles <= 12)
-            RAILS_TRY((launch_rowquad<12>(c, Ud, U->ld, k, c->small, j0, nc, od, Out->ld, U->m, vec_ok, acc, st)));
-        else
-            RAILS_TRY((launch_rowquad<16>(c, Ud, U->ld, k, c->small, j0, nc, od, Out->ld, U->m, vec_ok, acc, st)));
+    RAILS_TRY(stage_small(c, k, S_host, lds, nullptr, nullptr, 0, nullptr, nullptr));
+    RAILS_TRY(rowform_slices(c, U, c0, k, SameRows{U->m}, Out->d + oc0, Out->ld));
+    c->n_rowquad++;
+    return RAILS_OK;
+}
+
+// The pair form, out[i] = X[ia[i], ib[i]]: the row form's kernel body, slices, packed S and summation order on rows gathered through two
+// index arrays.  The indices travel behind S in the one staged upload of the call.
+extern "C" int rails_panel_rowpair(rails_ctx *c, const rails_panel *U, int c0, int k, const double *S_host, int lds, const int32_t *ia, const int32_t *ib, int64_t n,
+                                   rails_panel *Out, int oc0)
+{
+    if (c) hipSetDevice(c->device);
+    rails_slow_guard slow__(c, "rails_panel_rowpair", k, (long long)n);
+    RAILS_REQUIRE(c && U && Out, "rails_panel_rowpair: null argument");
+    RAILS_REQUIRE(k >= 0 && k <= 512, "rails_panel_rowpair: k = %d outside [0, 512]", k);
+    RAILS_REQUIRE(c0 >= 0 && c0 + k <= U->cap && oc0 >= 0 && oc0 < Out->cap, "rails_panel_rowpair: window [%d,%d) / column %d outside capacities %d / %d", c0, c0 + k, oc0,
+                  U->cap, Out->cap);
+    RAILS_REQUIRE(n >= 0 && n <= Out->m, "rails_panel_rowpair: %lld pairs for an output panel of %lld rows", (long long)n, (long long)Out->m);
+    RAILS_REQUIRE((ia && ib) || n <= U->m, "rails_panel_rowpair: a null index array is the identity, and %lld pairs exceed the %lld rows of U", (long long)n, (long long)U->m);
+    RAILS_REQUIRE(k == 0 || (S_host && lds >= k), "rails_panel_rowpair: bad small matrix (leading dimension %d < %d)", lds, k);
+    if (U->d == Out->d) RAILS_REQUIRE(oc0 < c0 || oc0 >= c0 + k, "rails_panel_rowpair: the output column lies inside the input window");
+    c->last_rowquad_nslices = 0;
+    if (n == 0 || U->m == 0) return RAILS_OK;
+    for (const int32_t *idx : {ia, ib})
+        for (int64_t i = 0; idx && i < n; ++i)
+            RAILS_REQUIRE(idx[i] >= 0 && idx[i] < U->m, "rails_panel_rowpair: index %d at %lld outside [0, %lld)", idx[i], (long long)i, (long long)U->m);
+    if (k == 0) {
+        RAILS_LAUNCH(k_zero_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, Out->d + oc0, Out->ld, n);
+        RAILS_HIP_CHECK(hipGetLastError());
+        return RAILS_OK;
     }
-    RAILS_HIP_CHECK(hipGetLastError());
+    PairRows rw{nullptr, nullptr, n, ia ? 1 : 0, ib ? 1 : 0};
+    RAILS_TRY(stage_small(c, k, S_host, lds, ia, ib, n, &rw.ia, &rw.ib)); // [S | ia | ib] in one upload
+    const int32_t *readable = reinterpret_cast<const int32_t *>(c->small);  // an identity side reads (and ignores) S's first word
+    if (!ia) rw.ia = readable;
+    if (!ib) rw.ib = readable;
+    RAILS_TRY(rowform_slices(c, U, c0, k, rw, Out->d + oc0, Out->ld));
     c->n_rowquad++;
     return RAILS_OK;
 }
@@ -247,6 +280,50 @@ extern "C" int rails_panel_move_rows(rails_ctx *c, const rails_panel *X, int xc0
     RAILS_TRY(rails_pinned_end_write(c));
     const int64_t work = n * nc;
     RAILS_LAUNCH(k_move_rows, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, c->stream, X->d + xc0, X->ld, (const int32_t *)c->small, scatter ? 1 : 0, Y->d + yc0, Y->ld, n, nc);
+    RAILS_HIP_CHECK(hipGetLastError());
+    return RAILS_OK;
+}
+
+// host[0..n) summed over the ranks of the partition, with the context's all-reduce (the one rails_gram uses); one rank without a hook or a
+// communicator: nothing happens, nothing is queued.  Synchronises otherwise.
+extern "C" int rails_allreduce_host(rails_ctx *c, double *host, int64_t n)
+{
+    if (c) hipSetDevice(c->device);
+    RAILS_REQUIRE(c && n >= 0 && (n == 0 || host), "rails_allreduce_host: null argument");
+    if (n == 0 || (c->nranks <= 1 && !c->allreduce && !c->rccl)) return RAILS_OK;
+    const size_t bytes = (size_t)n * sizeof(double);
+    RAILS_TRY(rails_small_reserve(c, bytes));
+    RAILS_TRY(rails_pinned_begin_write(c, bytes));
+    memcpy(c->pinned, host, bytes);
+    RAILS_HIP_CHECK(hipMemcpyAsync(c->small, c->pinned, bytes, hipMemcpyHostToDevice, c->stream));
+    RAILS_TRY(rails_pinned_end_write(c));
+    RAILS_TRY(rails_allreduce_dev(c, c->small, (size_t)n));
+    RAILS_HIP_CHECK(hipMemcpyAsync(c->pinned, c->small, bytes, hipMemcpyDeviceToHost, c->stream));
+    RAILS_HIP_CHECK(rails_stream_sync(c));
+    memcpy(host, c->pinned, bytes);
+    return RAILS_OK;
+}
+
+// Covariances to correlations: Out[i, oc0 + j] /= sqrt(Var[i, vc]) sqrt(rv[j]) for j < q, 0 where either variance is not > 0, exactly 1 where
+// i == rows[j] (the unknown with itself) and its variance is > 0.  rv and rows on the host (q <= 64 entries each).  Asynchronous.
+extern "C" int rails_panel_corr_scale(rails_ctx *c, rails_panel *Out, int oc0, int q, const rails_panel *Var, int vc, const double *rv_host, const int32_t *rows_host)
+{
+    if (c) hipSetDevice(c->device);
+    RAILS_REQUIRE(c && Out && Var && (q == 0 || (rv_host && rows_host)), "rails_panel_corr_scale: null argument");
+    RAILS_REQUIRE(q >= 0 && q <= 64 && oc0 >= 0 && oc0 + q <= Out->cap && vc >= 0 && vc < Var->cap, "rails_panel_corr_scale: bad windows");
+    RAILS_REQUIRE(Out->m == Var->m, "rails_panel_corr_scale: row mismatch %lld vs %lld", (long long)Out->m, (long long)Var->m);
+    if (Out->d == Var->d) RAILS_REQUIRE(vc < oc0 || vc >= oc0 + q, "rails_panel_corr_scale: the variance column lies inside the scaled window");
+    if (q == 0 || Out->m == 0) return RAILS_OK;
+    const size_t nd = (size_t)q + ((size_t)q * sizeof(int32_t) + 7) / 8; // doubles: rv, then rows
+    RAILS_TRY(rails_small_reserve(c, nd * sizeof(double)));
+    RAILS_TRY(rails_pinned_begin_write(c, nd * sizeof(double)));
+    memcpy(c->pinned, rv_host, (size_t)q * sizeof(double));
+    memcpy(c->pinned + q, rows_host, (size_t)q * sizeof(int32_t));
+    RAILS_HIP_CHECK(hipMemcpyAsync(c->small, c->pinned, nd * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    RAILS_TRY(rails_pinned_end_write(c));
+    const int64_t work = Out->m * q;
+    RAILS_LAUNCH(k_corr_scale, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, c->stream, Out->d + oc0, Out->ld, Out->m, q, Var->d + vc, Var->ld, c->small,
+                 reinterpret_cast<const int32_t *>(c->small + q));
     RAILS_HIP_CHECK(hipGetLastError());
     return RAILS_OK;
 }

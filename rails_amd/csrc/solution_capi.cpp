@@ -203,3 +203,83 @@ try {
     rails_set_error("rails_solution_block: out of host memory");
     return RAILS_ENOMEM;
 }
+
+extern "C" int rails_solution_pairs(rails_solution *s, const int32_t *ia, const int32_t *ib, int64_t n, rails_panel *out, int c0)
+{
+    SOL_REQUIRE(s && out, "rails_solution_pairs: null argument");
+    return rails_panel_rowpair(s->ctx, s->U, s->c0, s->k, s->S.data(), s->k, ia, ib, n, out, c0);
+}
+
+// One-point maps.  Whatever only this rank can see to be wrong (an index outside its rows) is not refused before the collective -- the other
+// ranks would wait in it -- but poisons the owner count of that reference unknown, so that every rank refuses after it.
+extern "C" int rails_solution_maps(rails_solution *s, const int32_t *rows, int q, int correlation, rails_panel *Out, int oc0, int var_col)
+try {
+    SOL_REQUIRE(s && Out && (q == 0 || rows), "rails_solution_maps: null argument");
+    SOL_REQUIRE(q >= 0 && q <= 64, "rails_solution_maps: q = %d outside [0, 64]", q);
+    SOL_REQUIRE(oc0 >= 0 && oc0 + q <= rails_panel_capacity(Out), "rails_solution_maps: columns [%d,%d) outside capacity %d", oc0, oc0 + q, rails_panel_capacity(Out));
+    SOL_REQUIRE(var_col < 0 || (var_col < rails_panel_capacity(Out) && (var_col < oc0 || var_col >= oc0 + q)),
+                "rails_solution_maps: the variance column %d lies inside the maps [%d,%d) or outside capacity %d", var_col, oc0, oc0 + q, rails_panel_capacity(Out));
+    SOL_REQUIRE(rails_panel_rows(Out) == s->m, "rails_solution_maps: the solution has %lld rows, Out %lld", (long long)s->m, (long long)rails_panel_rows(Out));
+    SOL_REQUIRE(Out != s->U && (s->m == 0 || rails_panel_device_ptr(Out) != rails_panel_device_ptr(s->U)), "rails_solution_maps: Out is the solution's own panel");
+    const int k = s->k;
+    // 1. the rows this rank owns, gathered and brought to the host
+    std::vector<int32_t> idx, slot;
+    std::vector<double> buf((size_t)k * q + q, 0.0); // G (k x q), then the owner counts
+    double *G = buf.data(), *count = buf.data() + (size_t)k * q;
+    for (int j = 0; j < q; ++j) {
+        if (rows[j] >= 0 && rows[j] < s->m) {
+            idx.push_back(rows[j]);
+            slot.push_back(j);
+            count[j] = 1.0;
+        } else if (rows[j] != -1)
+            count[j] = 2.0; // refused by every rank below
+    }
+    const int nown = (int)idx.size();
+    PanelGuard R;
+    if (nown > 0) {
+        SOL_TRY(rails_panel_create(s->ctx, nown, k, &R.p));
+        SOL_TRY(rails_panel_move_rows(s->ctx, s->U, s->c0, k, idx.data(), nown, 0, R.p, 0));
+        std::vector<double> Uh((size_t)nown * k), SU((size_t)k * nown);
+        SOL_TRY(rails_panel_download(s->ctx, R.p, 0, k, Uh.data(), nown)); // synchronises
+        // 2. G = S U[r,:]'
+        rails_dgemm('N', 'T', k, nown, k, 1.0, s->S.data(), k, Uh.data(), nown, 0.0, SU.data(), k);
+        for (int t = 0; t < nown; ++t) memcpy(G + (size_t)slot[t] * k, &SU[(size_t)t * k], sizeof(double) * k);
+    }
+    // 3. summed over the ranks; the counts say whether every reference unknown has exactly one owner
+    SOL_TRY(rails_allreduce_host(s->ctx, buf.data(), (int64_t)buf.size()));
+    for (int j = 0; j < q; ++j)
+        SOL_REQUIRE(count[j] == 1.0, "rails_solution_maps: reference unknown %d has %s", j, count[j] == 0.0 ? "no owner (row -1 on every rank)" : "several owners or an index outside the local rows");
+    // 4. Out = U G
+    if (q > 0 && s->m > 0) SOL_TRY(rails_panel_gemm(s->ctx, 1.0, s->U, s->c0, k, G, k, q, 0.0, Out, oc0));
+    if (!correlation && var_col < 0) return rails_ctx_sync(s->ctx); // the gathered rows go away here
+    // 5. diag(X), in the caller's column or a temporary one
+    PanelGuard V;
+    const rails_panel *var = Out;
+    int vc = var_col;
+    if (var_col >= 0)
+        SOL_TRY(rails_solution_variance(s, Out, var_col));
+    else if (s->m > 0) {
+        SOL_TRY(rails_panel_create(s->ctx, s->m, 1, &V.p));
+        SOL_TRY(rails_solution_variance(s, V.p, 0));
+        var = V.p;
+        vc = 0;
+    }
+    if (correlation && q > 0) {
+        // 6. the reference variances from their owners' variance column, summed like G
+        std::vector<double> rv(q, 0.0);
+        if (nown > 0) {
+            PanelGuard Rv;
+            std::vector<double> got(nown);
+            SOL_TRY(rails_panel_create(s->ctx, nown, 1, &Rv.p));
+            SOL_TRY(rails_panel_move_rows(s->ctx, var, vc, 1, idx.data(), nown, 0, Rv.p, 0));
+            SOL_TRY(rails_panel_download(s->ctx, Rv.p, 0, 1, got.data(), nown));
+            for (int t = 0; t < nown; ++t) rv[slot[t]] = got[t];
+        }
+        SOL_TRY(rails_allreduce_host(s->ctx, rv.data(), q));
+        if (s->m > 0) SOL_TRY(rails_panel_corr_scale(s->ctx, Out, oc0, q, var, vc, rv.data(), rows));
+    }
+    return rails_ctx_sync(s->ctx); // the temporaries go away here
+} catch (std::bad_alloc const &) {
+    rails_set_error("rails_solution_maps: out of host memory");
+    return RAILS_ENOMEM;
+}

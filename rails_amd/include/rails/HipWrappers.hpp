@@ -484,6 +484,38 @@ public:
         return out;
     }
 
+    // this[ia[i], :] * S * this[ib[i], :]' for i < n as an n x 1 multivector: the same kernel on gathered rows (rails_panel_rowpair;
+    // rails::Solution::covariance picks it up).  Local row indices; an EMPTY vector is the identity (then the other one's length <= rows).
+    HipMultiVectorWrapper rowpair(HostDenseMatrix const &S, std::vector<int32_t> const &ia, std::vector<int32_t> const &ib) const
+    {
+        const int64_t n = (int64_t)(ia.empty() ? ib.size() : ia.size());
+        HipMultiVectorWrapper out(n, 1, ctx_);
+        if (replicated_ || !panel_ || S.M() != n_ || S.N() != n_ || S.transposed() || (!ia.empty() && !ib.empty() && ia.size() != ib.size())) {
+            std::cerr << "rails_amd: rowpair() needs a distributed multivector, an untransposed " << n_ << " x " << n_ << " matrix and index vectors of one length" << std::endl;
+            return out;
+        }
+        hip_ok(rails_panel_rowpair(ctx_, panel_->p, c0_, n_, (double *)S, S.raw_ld(), ia.empty() ? nullptr : ia.data(), ib.empty() ? nullptr : ib.data(), n,
+                                   out.panel_->p, 0),
+               "rails_panel_rowpair");
+        return out;
+    }
+
+    // (this * S * this')[:, rows[j]] for j < q <= 64 as an m x q multivector, or the correlations (rails_solution_maps on a borrowed solution
+    // object: S is symmetrised; rows[j] = -1 on the ranks that do not own reference unknown j).  rails::Solution::maps picks it up.
+    HipMultiVectorWrapper maps(HostDenseMatrix const &S, std::vector<int32_t> const &rows, bool correlation) const
+    {
+        HipMultiVectorWrapper out(*this, (int)rows.size());
+        if (replicated_ || !panel_ || S.M() != n_ || S.N() != n_ || S.transposed()) {
+            std::cerr << "rails_amd: maps() needs a distributed multivector and an untransposed " << n_ << " x " << n_ << " matrix" << std::endl;
+            return out;
+        }
+        rails_solution *sol = nullptr;
+        if (!hip_ok(rails_solution_create(ctx_, panel_->p, c0_, n_, (double *)S, S.raw_ld(), 0, &sol), "rails_solution_create")) return out;
+        hip_ok(rails_solution_maps(sol, rows.data(), (int)rows.size(), correlation ? 1 : 0, out.panel_->p, 0, -1), "rails_solution_maps");
+        rails_solution_destroy(sol);
+        return out;
+    }
+
     // host round trips (tests, I/O)
     void from_host(const double *data, int64_t ld)
     {

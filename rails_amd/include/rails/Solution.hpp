@@ -11,6 +11,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <numeric>
 #include <type_traits>
 #include <utility>
@@ -28,11 +29,72 @@ template <class MultiVector, class DenseMatrix>
 struct has_rowquad<MultiVector, DenseMatrix, decltype(std::declval<MultiVector const &>().rowquad(std::declval<DenseMatrix const &>()), void())> : std::true_type {
 };
 
+// Whether a MultiVector offers `rowpair(S, ia, ib)` -- the n x 1 multivector of U(ia[i],:) S U(ib[i],:)', the same kernel on gathered rows
+// (HipMultiVectorWrapper: rails_panel_rowpair) -- and with it `maps(S, rows, correlation)`, the one-point maps (rails_solution_maps).
+template <class MultiVector, class DenseMatrix, class = void>
+struct has_rowpair : std::false_type {
+};
+template <class MultiVector, class DenseMatrix>
+struct has_rowpair<MultiVector, DenseMatrix,
+                   decltype(std::declval<MultiVector const &>().rowpair(std::declval<DenseMatrix const &>(), std::declval<std::vector<int32_t> const &>(),
+                                                                        std::declval<std::vector<int32_t> const &>()),
+                            void())> : std::true_type {
+};
+
 template <class MultiVector, class DenseMatrix>
 class Solution
 {
     MultiVector U_;
     DenseMatrix S_;
+
+    MultiVector covariance_(std::vector<int32_t> const &ia, std::vector<int32_t> const &ib, std::true_type) const { return U_.rowpair(S_, ia, ib); }
+    // through element access (host back ends; MultiVector(rows, columns) makes the n x 1 result): t = S U(b,:)', then U(a,:) t
+    MultiVector covariance_(std::vector<int32_t> const &ia, std::vector<int32_t> const &ib, std::false_type) const
+    {
+        const int k = U_.N(), n = (int)(ia.empty() ? ib.size() : ia.size());
+        MultiVector out(n, 1);
+        std::vector<double> t(k);
+        for (int i = 0; i < n; ++i) {
+            const int a = ia.empty() ? i : ia[i], b = ib.empty() ? i : ib[i];
+            for (int j = 0; j < k; ++j) {
+                t[j] = 0.0;
+                for (int l = 0; l < k; ++l) t[j] += S_(j, l) * U_(b, l);
+            }
+            double x = 0.0;
+            for (int j = 0; j < k; ++j) x += U_(a, j) * t[j];
+            out(i, 0) = x;
+        }
+        return out;
+    }
+
+    MultiVector maps_(std::vector<int32_t> const &rows, bool correlation, std::true_type) const { return U_.maps(S_, rows, correlation); }
+    // the composition of rails_solution_maps through the contract: G = S U(r,:)' by element access, the maps U G as one product, then the
+    // scaling with the variances (one rank: every rows[j] is a row of U)
+    MultiVector maps_(std::vector<int32_t> const &rows, bool correlation, std::false_type) const
+    {
+        const int k = U_.N(), m = U_.M(), q = (int)rows.size();
+        DenseMatrix G(k, q);
+        for (int j = 0; j < q; ++j)
+            for (int l = 0; l < k; ++l) {
+                double g = 0.0;
+                for (int t = 0; t < k; ++t) g += S_(l, t) * U_(rows[j], t);
+                G(l, j) = g;
+            }
+        MultiVector out = U_ * G;
+        if (!correlation) return out;
+        MultiVector var = variance();
+        for (int j = 0; j < q; ++j) {
+            const double vj = var(rows[j], 0);
+            for (int i = 0; i < m; ++i) {
+                const double vi = var(i, 0);
+                if (!(vi > 0.0) || !(vj > 0.0))
+                    out(i, j) = 0.0;
+                else
+                    out(i, j) = (i == rows[j]) ? 1.0 : out(i, j) / (std::sqrt(vi) * std::sqrt(vj));
+            }
+        }
+        return out;
+    }
 
     MultiVector variance_(std::true_type) const { return U_.rowquad(S_); }
     // through the contract: column l of P = U S is one product with a k x 1 matrix; it is multiplied into U's column l entry by entry, which
@@ -89,6 +151,20 @@ public:
 
     // diag(X) as an m x 1 multivector
     MultiVector variance() const { return variance_(has_rowquad<MultiVector, DenseMatrix>()); }
+
+    // X(ia[i], ib[i]) for every pair as an n x 1 multivector (local row indices; an empty vector is the identity): the covariance of pairs
+    // of unknowns -- two variables of one grid cell, a point and its neighbour along a section
+    MultiVector covariance(std::vector<int32_t> const &ia, std::vector<int32_t> const &ib) const
+    {
+        return covariance_(ia, ib, has_rowpair<MultiVector, DenseMatrix>());
+    }
+
+    // One-point maps as an m x q multivector: column j is X(:, rows[j]), or with `correlation` X(i, r_j) / sqrt(X(i,i) X(r_j,r_j)) -- 0 where a
+    // variance is not > 0, exactly 1 at the reference unknown itself
+    MultiVector maps(std::vector<int32_t> const &rows, bool correlation = false) const
+    {
+        return maps_(rows, correlation, has_rowpair<MultiVector, DenseMatrix>());
+    }
 
     // The `want` eigenpairs of largest modulus (want <= 0: all), those with |lambda| <= tol max|lambda| dropped: Q = orthonormal basis of U,
     // R = Q'U, the small symmetric eigenproblem of R S R', vectors = Q Z.  A dependent column of U leaves a column in Q that U has no part

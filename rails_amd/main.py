@@ -1,7 +1,8 @@
 """Command-line driver: solve A X M' + M X A' + B B' = 0 for X = V T V' with matrices from MatrixMarket files.
 
     python -m rails_amd.main [params.xml] [--dir DIR] [--A A.mtx] [--B B.mtx] [--M M.mtx] [--V V.mtx] [--T T.mtx]
-                               [--eigs K] [--variance FILE] [--sparse-B] [--warm-start V.mtx | --start-space S.mtx] [--restart-upon-start]
+                               [--eigs K] [--variance FILE] [--pairs FILE [--pairs-out FILE]]
+                               [--maps R1,R2,... [--correlation] [--maps-out FILE.mtx]] [--sparse-B] [--warm-start V.mtx | --start-space S.mtx] [--restart-upon-start]
                                [--inverse {lu,cg,bicgstab,iterative}] [--inverse-tol T] [--inverse-poly K] [--inverse-amg]
     python -m torch.distributed.run --nproc-per-node N -m rails_amd.main ... [--backend {nccl,gloo}] [--one-device]
                                                                                   (one rank per GPU, rows partitioned)
@@ -36,7 +37,8 @@ rank on device 0: a rehearsal of the multi-process path on a machine with one GP
 `--eigs K` and `--variance FILE` are the second half of the reference's driver (src/main.cpp:140-170) on the solution object
 (rails_amd.Solution): the K eigenvalues of largest modulus of the covariance X, each next to its share of the trace, written to
 `eigenvalues.mtx` / `eigenvectors.mtx`, and the pointwise variance diag(X).  After a Schur reduction both refer to the solution lifted to
-all unknowns (SchurOperator.lift), in the original row order.
+all unknowns (SchurOperator.lift), in the original row order.  `--pairs FILE` (lines `i j`, 1-based) writes the covariances X[i, j] and
+`--maps R1,R2,...` the covariance (`--correlation`: correlation) of every unknown with the reference unknowns, on the same object.
 """
 import argparse
 import os
@@ -49,6 +51,72 @@ import numpy as np
 def _log(rank, *a):
     if rank == 0:
         print(*a, flush=True)
+
+
+def _read_indices(text, what, m_all):
+    """1-based integers -> 0-based int64 array, every one inside [0, m_all)"""
+    try:
+        idx = np.array([int(t) for t in text], dtype=np.int64) - 1
+    except ValueError:
+        raise SystemExit("%s: not an integer in %r" % (what, text[:4]))
+    if idx.size and (idx.min() < 0 or idx.max() >= m_all):
+        raise SystemExit("%s: indices are 1-based and at most %d, got %d" % (what, m_all, int(idx[(idx < 0) | (idx >= m_all)][0]) + 1))
+    return idx
+
+
+def read_pairs(file, m_all):
+    """--pairs FILE: lines `i j`, 1-based (lines starting with % or # are comments) -> two 0-based int64 arrays"""
+    lines = [ln.split() for ln in open(file) if ln.strip() and not ln.lstrip().startswith(("%", "#"))]
+    if any(len(t) != 2 for t in lines):
+        raise SystemExit("--pairs: every line of %s holds two integers" % file)
+    return _read_indices([t[0] for t in lines], "--pairs", m_all), _read_indices([t[1] for t in lines], "--pairs", m_all)
+
+
+def read_refs(text, m_all):
+    """--maps R1,R2,...: 1-based reference unknowns -> 0-based int64 array of 1 to 64 entries"""
+    ref = _read_indices([t for t in text.split(",") if t.strip()], "--maps", m_all)
+    if not 1 <= ref.size <= 64:
+        raise SystemExit("--maps: between 1 and 64 reference unknowns, got %d" % ref.size)
+    return ref
+
+
+def _write_pairs(args, pairs, sol, path, rank, world, r0, dist):
+    """--pairs: X[i, j] for every pair, through Solution.covariance (one pass on the device)"""
+    from rails_amd import mmio
+
+    ia, ib = pairs
+    if world == 1:
+        cov = sol.covariance(ia.astype(np.int32), ib.astype(np.int32)) if ia.size else np.zeros(0)
+    else:  # every rank does the pairs it holds both unknowns of; a pair nobody holds whole is an error
+        mine = (ia >= r0) & (ia < r0 + sol.m) & (ib >= r0) & (ib < r0 + sol.m)
+        part = np.zeros(ia.size)
+        if mine.any():
+            part[mine] = sol.covariance((ia[mine] - r0).astype(np.int32), (ib[mine] - r0).astype(np.int32))
+        parts = [None] * world
+        dist.all_gather_object(parts, (mine, part))
+        held = sum(p[0].astype(int) for p in parts)
+        if np.any(held != 1):
+            raise SystemExit("--pairs: pair %d has its two unknowns on different ranks (not supported)" % (int(np.flatnonzero(held != 1)[0]) + 1))
+        cov = sum(p[1] for p in parts)
+    if rank == 0:
+        mmio.write_array(path(args.pairs_out), cov.reshape(-1, 1), comment="rails_amd: X[i, j] for the pairs of %s, X = V T V'" % args.pairs)
+        print("wrote %s (%d x 1)" % (path(args.pairs_out), cov.size), flush=True)
+
+
+def _write_maps(args, ref, sol, path, rank, world, r0, dist):
+    """--maps: the covariance (--correlation: correlation) of every unknown with the reference unknowns, through Solution.maps"""
+    from rails_amd import mmio
+
+    local = np.where((ref >= r0) & (ref < r0 + sol.m), ref - r0, -1).astype(np.int32)
+    out = sol.maps(local, correlation=args.correlation)
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, out)
+        out = np.vstack(parts)
+    if rank == 0:
+        what = "correlation" if args.correlation else "covariance"
+        mmio.write_array(path(args.maps_out), out, comment="rails_amd: the %s of every unknown with unknowns %s of X = V T V'" % (what, args.maps))
+        print("wrote %s (%d x %d, %s)" % (path(args.maps_out), out.shape[0], out.shape[1], what), flush=True)
 
 
 def main(argv=None):
@@ -72,6 +140,13 @@ def main(argv=None):
     ap.add_argument("--eigs", type=int, default=0, metavar="K", help="print the K leading eigenvalues of X and their share of the trace "
                                                                    "(src/main.cpp:162-168); writes eigenvalues.mtx and eigenvectors.mtx")
     ap.add_argument("--variance", default=None, metavar="FILE", help="write diag(X), the pointwise variance, to FILE (MatrixMarket array)")
+    ap.add_argument("--pairs", default=None, metavar="FILE", help="two integer columns, 1-based as MatrixMarket: the pairs (i, j) of unknowns whose covariance "
+                    "X[i, j] is wanted (after a Schur reduction: indices of the original row order); on several ranks both unknowns of a pair must be on one rank")
+    ap.add_argument("--pairs-out", default="pairs.mtx", metavar="FILE", help="where the covariances of --pairs go (MatrixMarket array, n x 1)")
+    ap.add_argument("--maps", default=None, metavar="R1,R2,...", help="one-point maps: the covariance of every unknown with each of these (1-based, at most 64) "
+                    "reference unknowns")
+    ap.add_argument("--correlation", action="store_true", help="the maps of --maps as correlations X[i, r] / sqrt(X[i, i] X[r, r])")
+    ap.add_argument("--maps-out", default="maps.mtx", metavar="FILE.mtx", help="where the maps go (MatrixMarket array, m x q)")
     ap.add_argument("--direct", action="store_true", help="direct back end (device panels for V, AV) instead of the default coordinate-space back end")
     ap.add_argument("--projected-lanczos", action="store_true", help="direct back end with the coefficient-space residual Lanczos (M = I only)")
     ap.add_argument("--sparse-B", action="store_true", help="keep B sparse (B.mtx in coordinate format): a device CSR operator instead of a dense panel; one rank")
@@ -139,6 +214,9 @@ def main(argv=None):
         B = mmio.read_dense(path(args.B))
     if B.shape[0] != m:
         raise SystemExit("B has %d rows, A has %d" % (B.shape[0], m))
+    # the unknowns --pairs and --maps name are those of A as given (after a Schur reduction: of the lifted solution), checked before the solve
+    pairs = read_pairs(path(args.pairs), m) if args.pairs else None
+    refs = read_refs(args.maps, m) if args.maps else None
     Mcsr = None
     if not args.no_mass and os.path.exists(path(args.M)):
         mm, mn, mrp, mcol, mval = mmio.read_csr(path(args.M))
@@ -320,11 +398,15 @@ def main(argv=None):
         mmio.write_array(path(args.V), V, comment=note)
         mmio.write_array(path(args.T), T, comment=note)
         print("wrote %s (%d x %d) and %s (%d x %d)" % (path(args.V), V.shape[0], V.shape[1], path(args.T), T.shape[0], T.shape[1]), flush=True)
-    if args.eigs > 0 or args.variance:
+    if args.eigs > 0 or args.variance or args.pairs or args.maps:
         sol = solver.solution()
         if schur is not None:
             sol, small = schur.lift(sol), sol
             small.close()
+        if args.pairs:
+            _write_pairs(args, pairs, sol, path, rank, world, r0, dist)
+        if args.maps:
+            _write_maps(args, refs, sol, path, rank, world, r0, dist)
         if args.variance:
             var = sol.variance()
             if world > 1:

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import check
-from .wrappers import HipMultiVectorWrapper, _f, _p
+from .wrappers import HipMultiVectorWrapper, _f, _p, index_array, index_ptr
 
 _i32p = C.POINTER(C.c_int32)
 
@@ -92,6 +92,40 @@ class Solution:
         check(self.lib.rails_solution_block(self.h, rows.ctypes.data_as(_i32p), rows.size, cols.ctypes.data_as(_i32p), cols.size, _p(out), max(1, rows.size)),
               "rails_solution_block")
         return out
+
+    def covariance(self, ia, ib=None, fetch=True):
+        """X[ia[i], ib[i]] for every pair: local row indices as numpy integer arrays of one length; one of the two may be None = the
+        identity (pair i is (ia[i], i), or (i, ib[i])).  One pass over the gathered rows on the device (rails_panel_rowpair), nothing
+        of U comes to the host.  fetch=False: the n x 1 device multivector"""
+        ia, ib = index_array(ia, self.m, "ia"), index_array(ib, self.m, "ib")
+        if ia is None and ib is None:
+            raise ValueError("covariance: give ia, ib or both (variance() is the case of neither)")
+        if ia is not None and ib is not None and ia.size != ib.size:
+            raise ValueError("covariance: %d indices in ia, %d in ib" % (ia.size, ib.size))
+        n = (ia if ia is not None else ib).size
+        if (ia is None or ib is None) and n > self.m:
+            raise ValueError("covariance: a missing index array is the identity, and %d pairs exceed the %d rows" % (n, self.m))
+        out = HipMultiVectorWrapper(self.ctx, n, 1)
+        check(self.lib.rails_solution_pairs(self.h, index_ptr(ia), index_ptr(ib), n, out.panel.h, 0), "rails_solution_pairs")
+        return out.to_host()[:, 0] if fetch else out
+
+    def maps(self, rows, correlation=False, fetch=True):
+        """One-point maps: column j is X[:, rows[j]] (or the correlation of every unknown with unknown rows[j]; 0 where a variance is not
+        positive, 1 at the unknown itself).  rows: up to 64 LOCAL row indices; on a row partition -1 on every rank but the owner.
+        fetch=False: the m x q device multivector"""
+        rows = index_array(rows, self.m, "rows", lowest=-1)
+        if rows is None or rows.size > 64:
+            raise ValueError("maps: between 0 and 64 reference unknowns, got %s" % (None if rows is None else rows.size))
+        out = HipMultiVectorWrapper(self.ctx, self.m, rows.size)
+        check(self.lib.rails_solution_maps(self.h, index_ptr(rows), rows.size, 1 if correlation else 0, out.panel.h, 0, -1), "rails_solution_maps")
+        return out.to_host() if fetch else out
+
+    def std(self, fetch=True):
+        """sqrt(diag(X)), the pointwise standard deviation; 0 where the computed variance is not > 0 (the rule of the correlation maps).
+        The root is taken on the host; fetch=False uploads it into a new m x 1 device multivector"""
+        v = self.variance()
+        s = np.sqrt(np.where(v > 0.0, v, 0.0))
+        return s if fetch else HipMultiVectorWrapper(self.ctx, data=s.reshape(-1, 1))
 
     def close(self):
         if self.h:

@@ -31,6 +31,31 @@ def _p(a):
     return a.ctypes.data_as(_dp)
 
 
+def index_array(a, limit, name, lowest=0):
+    """a -> contiguous int32 array of row indices in [lowest, limit), or None for None; anything else raises with a clear message before
+    the C call: a non-integer dtype (no silent truncation of 2.7), more than one dimension, an index outside the range"""
+    if a is None:
+        return None
+    a = np.asarray(a)
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        if a.size:
+            raise TypeError("%s: row indices must be integers, got dtype %s" % (name, a.dtype))
+        a = a.astype(np.int32)
+    if a.ndim > 1:
+        raise ValueError("%s: row indices must be one-dimensional, got shape %s" % (name, a.shape))
+    a = a.ravel()
+    if a.size:
+        lo, hi = int(a.min()), int(a.max())
+        if lo < lowest or hi >= limit:
+            bad = int(np.flatnonzero((a < lowest) | (a >= limit))[0])
+            raise IndexError("%s: index %d at position %d outside [%d, %d)" % (name, int(a[bad]), bad, lowest, limit))
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def index_ptr(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
 class Context:
     """Device context: device ordinal, stream, RNG seed, row partition, all-reduce hook."""
 
@@ -339,6 +364,36 @@ class HipMultiVectorWrapper:
         out = np.zeros(max(self.n, 1))
         check(self.ctx.lib.rails_panel_colnorms2(self.ctx.h, self.panel.h, self.c0, self.n, _p(out)), "rails_panel_colnorms2")
         return out[:self.n]
+
+    def rowquad(self, S):
+        """the m x 1 multivector of U[i,:] S U[i,:]' (rails_panel_rowquad): one pass over the window, S a host matrix taken as given"""
+        S = _f(S)
+        if S.shape != (self.n, self.n):
+            raise ValueError("rowquad: S is %d x %d, the multivector has %d columns" % (S.shape[0], S.shape[1], self.n))
+        out = HipMultiVectorWrapper(self.ctx, self.M(), 1)
+        check(self.ctx.lib.rails_panel_rowquad(self.ctx.h, self.panel.h, self.c0, self.n, _p(S), max(1, self.n), out.panel.h, 0), "rails_panel_rowquad")
+        return out
+
+    def rowpair(self, S, ia, ib=None, out=None):
+        """the n x 1 multivector of U[ia[i],:] S U[ib[i],:]' (rails_panel_rowpair): one pass over the gathered rows.  ia, ib: integer
+        arrays of local row indices, either may be None = the identity.  out: a multivector of at least n rows whose first column
+        receives the result (its other rows and columns stay); None: a new n x 1 one"""
+        S = _f(S)
+        if S.shape != (self.n, self.n):
+            raise ValueError("rowpair: S is %d x %d, the multivector has %d columns" % (S.shape[0], S.shape[1], self.n))
+        ia, ib = index_array(ia, self.M(), "ia"), index_array(ib, self.M(), "ib")
+        if ia is not None and ib is not None and ia.size != ib.size:
+            raise ValueError("rowpair: %d indices in ia, %d in ib" % (ia.size, ib.size))
+        n = self.M() if (ia is None and ib is None) else (ia if ia is not None else ib).size
+        if (ia is None or ib is None) and n > self.M():
+            raise ValueError("rowpair: a missing index array is the identity, and %d pairs exceed the %d rows" % (n, self.M()))
+        if out is None:
+            out = HipMultiVectorWrapper(self.ctx, n, 1)
+        elif out.M() < n or out.n < 1:
+            raise ValueError("rowpair: the output has %d rows and %d columns, %d pairs need a column of %d rows" % (out.M(), out.n, n, n))
+        check(self.ctx.lib.rails_panel_rowpair(self.ctx.h, self.panel.h, self.c0, self.n, _p(S), max(1, self.n), index_ptr(ia), index_ptr(ib), n,
+                                               out.panel.h, out.c0), "rails_panel_rowpair")
+        return out
 
     def orthogonalize_range(self, N=None, tol=0.0):
         """The columns past the watermark, which need be neither orthonormal nor independent, replaced by an orthonormal basis of their
