@@ -23,9 +23,9 @@ typedef struct rails_solver rails_solver;
 int rails_solver_create(rails_ctx *ctx, rails_csr *A, rails_csr *M, const double *B_host, int64_t ldb, int p,
                         int64_t m_global, rails_solver **out);
 /* The same with B a sparse right-hand side (rails_sprhs_create; the caller keeps S alive): B takes the operator form of the reference's
- * B adaptor (src/MatrixOrMultiVectorWrapper.hpp; src/main.cpp:67,98).  Single GPU.  Such a solver always runs the direct back end -- the
- * coordinate-space back end needs B inside its basis -- so rails_solver_backend_stats is "{}" and the options "subspace" and
- * "projected_lanczos" are accepted and ignored.  The projection methods that start from B (1.2, 2.2) are refused (*code = -2), as for
+ * B adaptor (src/MatrixOrMultiVectorWrapper.hpp; src/main.cpp:67,98).  Single GPU.  Such a solver always runs the direct back end
+ * (rails_amd/csrc/solve_choice.h), so rails_solver_backend_stats is "{}" and the options "subspace" and "projected_lanczos" are accepted
+ * and ignored.  The projection methods that start from B (1.2, 2.2) are refused (*code = -2), as for
  * any operator B. */
 int rails_solver_create_sparse(rails_ctx *ctx, rails_csr *A, rails_csr *M, rails_sprhs *S, int64_t m_global, rails_solver **out);
 int rails_solver_destroy(rails_solver *s);
@@ -44,7 +44,8 @@ int rails_solver_apply_parameters(rails_solver *s, int *code);
  * generalized projected equation by Cholesky reduction), "verbose", "max_trips", "projected_lanczos" (M = I only: carry the
  * residual Lanczos recurrence in coefficient space, see rails/HipSolverOps.hpp), "subspace" (default 1: run the solver template on the
  * coordinate-space back end of rails/SubspaceWrappers.hpp -- all multivectors as coordinates in one orthonormal device basis;
- * 0: the direct back end of rails/HipWrappers.hpp) */
+ * 0: the direct back end of rails/HipWrappers.hpp; which solves the coordinate-space back end takes, and why the others go to the direct
+ * one, is the one rule of rails_amd/csrc/solve_choice.h) */
 int rails_solver_set_option(rails_solver *s, const char *name, double value);
 /* opts.Ainv of matlab/RAILSsolver.m:18-22: the operator the projection methods other than 1 apply as A^-1 ("Projection method" =
  * 1.1, 1.2, 1.3: expand with A^-1 r instead of r; 2.1, 2.2, 2.3: with [r, A^-1 r]; the decimal picks the start space -- .1 A^-1 V0
@@ -74,8 +75,7 @@ int rails_solver_set_V(rails_solver *s, const double *V_host, int64_t ldv, int k
  * device.  They need not be orthonormal or independent: the solve orthonormalises them (rails_orthogonalize_range), drops every column
  * of which less than 1e-8 survives and projects the nullspace out.  The next solve is a warm start whatever "Restart from solution"
  * says; one solve consumes the space, as rails_solver_set_V is consumed.  The solve is refused (*code = -2, V and T unchanged) when no
- * column survives.  Both back ends; with a nullspace set as well the solve runs on the direct back end (as a sparse B always does),
- * whose orthonormalisation projects the nullspace out column block by column block.  (On the direct back end such a solve applies the
+ * column survives.  Both back ends (with a nullspace set as well: the direct one, rails_amd/csrc/solve_choice.h).  (On the direct back end such a solve applies the
  * parameters set so far, as rails_solver_apply_parameters does.)  A panel with another row count, or k < 1: RAILS_EINVAL. */
 int rails_solver_set_start_space(rails_solver *s, const rails_panel *P, int c0, int k);
 /* columns the last solve kept of its start space; 1 after a cold start */
@@ -88,7 +88,8 @@ int rails_solver_solve(rails_solver *s, int *code, int *k);
 int rails_solver_get_V(rails_solver *s, double *V_host, int64_t ldv); /* local rows x k */
 int rails_solver_get_T(rails_solver *s, double *T_host, int ldt);     /* k x k */
 int rails_solver_trips(rails_solver *s);
-/* ||B||_2^2 as the last solve computed it, the scale of its stopping test (src/LyapunovSolver.hpp:134); 0 before the first solve */
+/* ||B||_2^2 as the last solve computed it on either back end, the scale of its stopping test (src/LyapunovSolver.hpp:134); 0 before the
+ * first solve */
 int rails_solver_scale(rails_solver *s, double *scale);
 int rails_solver_history(rails_solver *s, double *res, int cap);      /* Lanczos estimates per trip; returns count */
 

@@ -13,6 +13,7 @@
 #include "rails/SubspaceSolverOps.hpp"
 #include "rails_solution.h"
 #include "rails_solver.h"
+#include "solve_choice.h"
 
 void rails_set_error(const char *fmt, ...);
 
@@ -35,6 +36,23 @@ public:
     void set(std::string const &name, double val) { params_[name] = val; }
 };
 
+// What a solve leaves behind for the accessors, whichever back end ran it.
+struct Outcome {
+    int code = 0, trips = 0;
+    std::vector<double> history;
+    std::map<std::string, double> profile;
+    double scale = 0.0; // ||B||_2^2
+    int null_rank = 0, start_rank = 0;
+    std::string stats = "{}"; // counters of the coordinate-space back end
+    rails::SolveBackend backend = rails::DirectBackend;
+};
+
+template <class SolverT>
+Outcome outcome_of(SolverT const &solver, int code, rails::SolveBackend backend, std::string const &stats = "{}")
+{
+    return {code, solver.trips(), solver.residual_history(), solver.profile(), solver.scale(), solver.nullspace_rank(), solver.start_rank(), stats, backend};
+}
+
 } // namespace
 
 struct rails_solver {
@@ -52,23 +70,30 @@ struct rails_solver {
     rails::HipOperatorWrapper Ainv; // rails_solver_set_inverse (the caller owns the handle)
     bool has_inv = false;
     rails::HipMultiVectorWrapper N; // rails_solver_set_nullspace (null_q columns; 0: none)
-    int null_q = 0, null_rank = 0;
+    int null_q = 0;
     bool mass = false;
     bool ortho_m = false; // V kept M-orthonormal (matlab/RAILSsolver.m opts.ortho = 'M'); needs mass
     rails_trip_fn trip_fn = nullptr;
     void *trip_user = nullptr;
-    // coordinate-space back end (rails/SubspaceWrappers.hpp): used by solve() when asked for and applicable
-    bool subspace = true, verbose = true, projected = false; // default: coordinate-space back end where applicable (M = I, cold start)
+    // the option "subspace": the coordinate-space back end (rails/SubspaceWrappers.hpp) where solve_choice.h lets it run
+    bool subspace = true, verbose = true, projected = false;
     int max_trips = 0;
     bool have_V0 = false;
     rails::HipMultiVectorWrapper start; // rails_solver_set_start_space: the raw start space of the next solve (a device copy)
     bool have_start = false;
-    int start_rank = 0;
-    bool last_was_subspace = false;
-    int sub_trips = 0;
-    std::vector<double> sub_hist;
-    std::map<std::string, double> sub_profile;
-    std::string sub_stats;
+    Outcome last; // of the last solve that ran, on either back end
+
+    // the options and the trip callback, applied to a solver of either back end
+    template <class SolverT>
+    void configure(SolverT &to)
+    {
+        to.use_mass_matrix(mass);
+        to.use_mass_orthogonalisation(ortho_m);
+        to.set_verbose(verbose);
+        to.set_max_trips(max_trips);
+        to.set_projected_lanczos(projected);
+        to.set_trip_callback(trip_fn ? std::function<void(int)>([this](int trip) { trip_fn(trip_user, trip); }) : std::function<void(int)>());
+    }
 };
 
 extern "C" int rails_solver_create(rails_ctx *ctx, rails_csr *A, rails_csr *M, const double *B_host, int64_t ldb, int p, int64_t m_global,
@@ -140,7 +165,6 @@ try {
     }
     s->solver = new rails::HipSolver(s->A, s->Bop, s->M);
     s->V = rails::HipMultiVectorWrapper(m, 1, ctx);
-    s->subspace = false;
     *out = s;
     return RAILS_OK;
 } catch (std::bad_alloc const &) {
@@ -184,29 +208,25 @@ extern "C" int rails_solver_set_option(rails_solver *s, const char *name, double
             return RAILS_EINVAL;
         }
         s->mass = value != 0.0;
-        s->solver->use_mass_matrix(s->mass);
     } else if (n == "mass_orthogonalisation" || n == "ortho_m") {
         if (value != 0.0 && !s->mass) {
             rails_set_error("rails_solver_set_option: mass_orthogonalisation needs the option mass (set it first)");
             return RAILS_EINVAL;
         }
         s->ortho_m = value != 0.0;
-        s->solver->use_mass_orthogonalisation(s->ortho_m);
-    } else if (n == "verbose") {
+    } else if (n == "verbose")
         s->verbose = value != 0.0;
-        s->solver->set_verbose(s->verbose);
-    } else if (n == "max_trips") {
+    else if (n == "max_trips")
         s->max_trips = (int)value;
-        s->solver->set_max_trips(s->max_trips);
-    } else if (n == "projected_lanczos") {
+    else if (n == "projected_lanczos")
         s->projected = value != 0;
-        s->solver->set_projected_lanczos(s->projected);
-    } else if (n == "subspace")
-        s->subspace = value != 0 && !s->sprhs; // a sparse B always runs the direct back end (the option is accepted and ignored)
+    else if (n == "subspace")
+        s->subspace = value != 0;
     else {
         rails_set_error("rails_solver_set_option: unknown option '%s'", name);
         return RAILS_EINVAL;
     }
+    s->configure(*s->solver);
     return RAILS_OK;
 }
 
@@ -233,7 +253,7 @@ extern "C" int rails_solver_set_nullspace(rails_solver *s, const double *N_host,
         return RAILS_EINVAL;
     }
     s->null_q = q;
-    s->null_rank = 0;
+    s->last.null_rank = 0;
     if (q == 0) {
         s->N = rails::HipMultiVectorWrapper();
         s->solver->clear_nullspace();
@@ -246,17 +266,14 @@ extern "C" int rails_solver_set_nullspace(rails_solver *s, const double *N_host,
     return RAILS_OK;
 }
 
-extern "C" int rails_solver_nullspace_rank(rails_solver *s) { return s ? s->null_rank : -1; }
+extern "C" int rails_solver_nullspace_rank(rails_solver *s) { return s ? s->last.null_rank : -1; }
 
 extern "C" int rails_solver_set_trip_callback(rails_solver *s, rails_trip_fn fn, void *user)
 {
     if (!s) return RAILS_EINVAL;
     s->trip_fn = fn;
     s->trip_user = user;
-    if (fn)
-        s->solver->set_trip_callback([s](int trip) { s->trip_fn(s->trip_user, trip); });
-    else
-        s->solver->set_trip_callback(std::function<void(int)>());
+    s->configure(*s->solver);
     return RAILS_OK;
 }
 
@@ -301,18 +318,16 @@ extern "C" int rails_solver_set_start_space(rails_solver *s, const rails_panel *
     return RAILS_OK;
 }
 
-extern "C" int rails_solver_start_rank(rails_solver *s) { return s ? s->start_rank : -1; }
+extern "C" int rails_solver_start_rank(rails_solver *s) { return s ? s->last.start_rank : -1; }
 
 // the same solve on the coordinate-space back end: B and every later vector are expressed in one orthonormal device basis
 static int solve_in_coordinates(rails_solver *s)
 {
-    const int p = s->B.N();
-    const int restart = s->params.get("Restart size", -1);
-    const int expand = s->params.get("Expand size", 3);
     rails::HipSolver::Projection proj;
     const bool pair = rails::HipSolver::parse_projection(s->params.get("Projection method", 1.0), proj) && proj.pair; // 2.x: twice per trip
-    const int kmax = std::max(restart > 0 ? restart : 100, 1) + (pair ? 2 : 1) * expand + 100 + (s->have_start ? s->start.N() : 0);
-    auto basis = std::make_shared<rails::SubspaceBasis>(s->ctx, s->m_local, s->m_global, 2 * kmax + p + 128);
+    const int restart = s->params.get("Restart size", -1);
+    const int rows = rails::trip::coordinate_basis_rows(restart, s->params.get("Expand size", 3), pair, s->have_start ? s->start.N() : 0, s->B.N());
+    auto basis = std::make_shared<rails::SubspaceBasis>(s->ctx, s->m_local, s->m_global, rows);
     if (restart > 0 || s->params.get("Restart iterations", 20) > 0) basis->preallocate_compress_panel(); // restarts will re-base the basis
     rails::SubspaceMultiVector Bc = rails::SubspaceMultiVector::Absorb(basis, s->B);
     rails::SubspaceOperator Ac(s->A, basis);
@@ -324,11 +339,7 @@ static int solve_in_coordinates(rails_solver *s)
     if (s->have_start) params.set("Restart from solution", 1.0); // a start space makes a warm start whatever the parameter says
     int prc = solver.set_parameters(params);
     if (prc != 0) return prc + 100;
-    solver.set_verbose(s->verbose);
-    solver.set_max_trips(s->max_trips);
-    solver.use_mass_matrix(s->mass);
-    solver.use_mass_orthogonalisation(s->ortho_m);
-    if (s->trip_fn) solver.set_trip_callback([s](int trip) { s->trip_fn(s->trip_user, trip); });
+    s->configure(solver);
     solver.set_failure_check([basis]() { return basis->failed; }); // a latched failure of the basis ends the run at the next trip
     rails::SubspaceMultiVector Vc(basis, 1);
     if (s->have_V0) { // warm start: the caller's (orthonormal) V expressed in the basis (src/LyapunovSolver.hpp:116-123)
@@ -350,21 +361,18 @@ static int solve_in_coordinates(rails_solver *s)
         Vc.set_orthogonalized(Vc.N());
     }
     int rc = solver.solve(Vc, s->T);
-    s->null_rank = solver.nullspace_rank();
-    s->start_rank = solver.start_rank();
-    if (rc == -2) return rc; // refused before the first trip: V and T stay as they were
-    s->V = Vc.materialise();
-    s->V.set_orthogonalized(s->V.N());
-    s->sub_trips = solver.trips();
-    s->sub_hist = solver.residual_history();
-    s->sub_profile = solver.profile();
+    if (rc != -2) { // (refused before the first trip: V and T stay as they were)
+        s->V = Vc.materialise();
+        s->V.set_orthogonalized(s->V.N());
+    }
+    rails::SubspaceBasis const &b = *basis;
     char buf[1536];
     snprintf(buf, sizeof(buf), "{\"dim\": %d, \"absorb\": %ld, \"absorb_columns\": %ld, \"one_by_one\": %ld, \"dropped\": %ld, \"compress\": %ld, \"materialise\": %ld, \"prefetched_random\": %ld, \"second_rounds\": %ld, \"delicate_blocks\": %ld, \"reprojected_blocks\": %ld, \"overlapped_blocks\": %ld, \"scratch_blocks\": %ld, \"replaced_columns\": %ld, \"verified\": %d, \"verify_representation\": %.3e, \"verify_orthonormality\": %.3e, \"seconds\": {\"materialise\": %.4f, \"absorb\": %.4f, \"compress_qr\": %.4f, \"compress_rotate\": %.4f, "
              "\"compress_coefficients\": %.4f}}",
-             basis->dim, basis->n_absorb, basis->n_absorb_cols, basis->n_single, basis->n_dropped, basis->n_compress, basis->n_materialise, basis->n_prefetched, basis->n_second_round, basis->n_delicate, basis->n_reprojected, basis->n_overlapped, basis->n_scratch_blocks, basis->n_replaced, basis->verify ? 1 : 0, basis->verify_repr, basis->verify_orth,
-             basis->t_materialise, basis->t_absorb, basis->t_qr, basis->t_rotate, basis->t_recoef);
-    s->sub_stats = buf;
-    if (basis->failed) {
+             b.dim, b.n_absorb, b.n_absorb_cols, b.n_single, b.n_dropped, b.n_compress, b.n_materialise, b.n_prefetched, b.n_second_round, b.n_delicate, b.n_reprojected, b.n_overlapped, b.n_scratch_blocks, b.n_replaced, b.verify ? 1 : 0, b.verify_repr, b.verify_orth,
+             b.t_materialise, b.t_absorb, b.t_qr, b.t_rotate, b.t_recoef);
+    s->last = outcome_of(solver, rc, rails::CoordinateBackend, buf);
+    if (rc != -2 && basis->failed) {
         rails_set_error("coordinate-space back end: a device operation failed (%s)", rails_last_error());
         return -1000;
     }
@@ -375,10 +383,7 @@ extern "C" int rails_solver_solve(rails_solver *s, int *code, int *k)
 {
     if (!s) return RAILS_EINVAL;
     const bool restart_from_solution = s->params.get("Restart from solution", 0.0) != 0.0;
-    // a warm start needs the caller's V; "Restart from solution" without one is the direct back end's business (it starts from
-    // the single column the solver object holds, like the reference)
-    // (a raw start space together with a nullspace: the direct back end, whose orthonormalisation projects the nullspace out as it goes)
-    s->last_was_subspace = s->subspace && !s->sprhs && (s->have_V0 || s->have_start || !restart_from_solution) && !(s->have_start && s->null_q > 0);
+    const rails::SolveBackend backend = rails::choose_backend(s->subspace, s->sprhs != nullptr, s->have_V0, s->have_start, s->null_q, restart_from_solution);
     { // the projection method: a valid value (rails_solver_apply_parameters reports it) with the inverse it needs
         rails::HipSolver::Projection proj;
         const double method = s->params.get("Projection method", 1.0);
@@ -394,7 +399,7 @@ extern "C" int rails_solver_solve(rails_solver *s, int *code, int *k)
     rails::clear_sticky_error();
     int rc;
     try { // the solver templates allocate (std::vector, make_shared): nothing may unwind through the C boundary
-        if (s->last_was_subspace) {
+        if (backend == rails::CoordinateBackend) {
             rc = solve_in_coordinates(s);
             if (rc == -1000) return RAILS_EHIP;
         } else if (s->have_start) { // on the start space's own copy: a refused solve leaves V and T as they were
@@ -420,14 +425,10 @@ extern "C" int rails_solver_solve(rails_solver *s, int *code, int *k)
             s->solver->set_raw_start_space(true);
             rails::HipMultiVectorWrapper Vs = s->start;
             rc = s->solver->solve(Vs, s->T);
-            s->null_rank = s->solver->nullspace_rank();
-            s->start_rank = s->solver->start_rank();
             if (rc != -2) s->V = Vs;
-        } else {
+        } else
             rc = s->solver->solve(s->V, s->T);
-            s->null_rank = s->solver->nullspace_rank();
-            s->start_rank = s->solver->start_rank();
-        }
+        if (backend == rails::DirectBackend) s->last = outcome_of(*s->solver, rc, backend);
     } catch (std::bad_alloc const &) {
         rails_set_error("rails_solver_solve: out of host memory");
         return RAILS_ENOMEM;
@@ -467,21 +468,21 @@ extern "C" int rails_solver_get_T(rails_solver *s, double *T_host, int ldt)
     return RAILS_OK;
 }
 
-extern "C" int rails_solver_trips(rails_solver *s) { return s ? (s->last_was_subspace ? s->sub_trips : s->solver->trips()) : -1; }
+extern "C" int rails_solver_trips(rails_solver *s) { return s ? s->last.trips : -1; }
 
 extern "C" int rails_solver_scale(rails_solver *s, double *scale)
 {
     if (!s || !scale) return RAILS_EINVAL;
-    *scale = s->last_was_subspace ? 0.0 : s->solver->scale();
+    *scale = s->last.scale;
     return RAILS_OK;
 }
 
-extern "C" const char *rails_solver_backend_stats(rails_solver *s) { return (s && s->last_was_subspace) ? s->sub_stats.c_str() : "{}"; }
+extern "C" const char *rails_solver_backend_stats(rails_solver *s) { return s ? s->last.stats.c_str() : "{}"; }
 
 extern "C" int rails_solver_history(rails_solver *s, double *res, int cap)
 {
     if (!s) return -1;
-    auto const &h = s->last_was_subspace ? s->sub_hist : s->solver->residual_history();
+    auto const &h = s->last.history;
     int n = (int)h.size();
     for (int i = 0; i < n && i < cap; ++i) res[i] = h[i];
     return n;
@@ -492,7 +493,7 @@ extern "C" int rails_solver_profile(rails_solver *s, char *buf, int cap)
     if (!s || !buf || cap < 2) return RAILS_EINVAL;
     std::string out = "{";
     bool first = true;
-    for (auto const &kv : (s->last_was_subspace ? s->sub_profile : s->solver->profile())) {
+    for (auto const &kv : s->last.profile) {
         char tmp[256];
         snprintf(tmp, sizeof(tmp), "%s\"%s\": %.6f", first ? "" : ", ", kv.first.c_str(), kv.second);
         out += tmp;
@@ -504,23 +505,28 @@ extern "C" int rails_solver_profile(rails_solver *s, char *buf, int cap)
     return RAILS_OK;
 }
 
+// S (order n, symmetric) <- P'P for P = [blk[0] ... blk[nb - 1]], block a at row and column off[a]
+static std::vector<double> gram_of_blocks(rails::HipMultiVectorWrapper const *const *blk, const int *off, int nb, int n)
+{
+    std::vector<double> S((size_t)n * n, 0.0);
+    for (int a = 0; a < nb; ++a)
+        for (int b = a; b < nb; ++b) {
+            rails::HostDenseMatrix C = blk[a]->dot(*blk[b]);
+            for (int j = 0; j < C.N(); ++j)
+                for (int i = 0; i < C.M(); ++i) S[(off[a] + i) + (size_t)(off[b] + j) * n] = S[(off[b] + j) + (size_t)(off[a] + i) * n] = C(i, j);
+        }
+    return S;
+}
+
 // The same with a sparse B: P = [AV MV], K = [[0 T],[T 0]], Z = B'P;  ||R||_F^2 = tr((P'P K)^2) + 2 tr(K Z'Z) + ||B'B||_F^2
 static int sparse_relative_residual(rails_solver *s, rails::HipMultiVectorWrapper const &AV, rails::HipMultiVectorWrapper const &MV, double *rel)
 {
     const int k = AV.N(), n = 2 * k;
     const rails::HipOperatorWrapper Bt = s->Bop.transpose();
     rails::HipMultiVectorWrapper ZA = Bt * AV, ZM = Bt * MV; // p x k each
-    std::vector<double> S((size_t)n * n, 0.0), W((size_t)n * n, 0.0);
     rails::HipMultiVectorWrapper const *blk[2] = {&AV, &MV}, *zbl[2] = {&ZA, &ZM};
-    for (int a = 0; a < 2; ++a)
-        for (int b = a; b < 2; ++b) {
-            rails::HostDenseMatrix C = blk[a]->dot(*blk[b]), D = zbl[a]->dot(*zbl[b]);
-            for (int j = 0; j < k; ++j)
-                for (int i = 0; i < k; ++i) {
-                    S[(a * k + i) + (size_t)(b * k + j) * n] = S[(b * k + j) + (size_t)(a * k + i) * n] = C(i, j);
-                    W[(a * k + i) + (size_t)(b * k + j) * n] = W[(b * k + j) + (size_t)(a * k + i) * n] = D(i, j);
-                }
-        }
+    const int off[2] = {0, k};
+    const std::vector<double> S = gram_of_blocks(blk, off, 2, n), W = gram_of_blocks(zbl, off, 2, n);
     // SK = S K: column block 0 of S K is S[:, MV] T, column block 1 is S[:, AV] T
     std::vector<double> SK((size_t)n * n, 0.0);
     for (int i = 0; i < n; ++i)
@@ -557,18 +563,9 @@ extern "C" int rails_solver_relative_residual(rails_solver *s, double *rel)
     rails::HipMultiVectorWrapper MV = s->mass ? (s->M * s->V) : s->V.view();
     if (s->sprhs) return sparse_relative_residual(s, AV, MV, rel);
     int n = 2 * k + p;
-    std::vector<double> S((size_t)n * n, 0.0);
     rails::HipMultiVectorWrapper const *blk[3] = {&AV, &MV, &s->B};
-    int off[3] = {0, k, 2 * k};
-    for (int a = 0; a < 3; ++a)
-        for (int b = a; b < 3; ++b) {
-            rails::HostDenseMatrix C = blk[a]->dot(*blk[b]);
-            for (int j = 0; j < C.N(); ++j)
-                for (int i = 0; i < C.M(); ++i) {
-                    S[(off[a] + i) + (size_t)(off[b] + j) * n] = C(i, j);
-                    S[(off[b] + j) + (size_t)(off[a] + i) * n] = C(i, j);
-                }
-        }
+    const int off[3] = {0, k, 2 * k};
+    const std::vector<double> S = gram_of_blocks(blk, off, 3, n);
     // GS = G * S
     std::vector<double> GS((size_t)n * n, 0.0);
     for (int j = 0; j < n; ++j) {

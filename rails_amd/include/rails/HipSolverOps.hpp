@@ -26,9 +26,7 @@ namespace rails
 {
 
 template <>
-struct SolverOps<HipOperatorWrapper, HipMultiVectorWrapper, HostDenseMatrix> {
-    typedef Solver<HipOperatorWrapper, HipMultiVectorWrapper, HostDenseMatrix> SolverT;
-
+struct SolverOps<HipOperatorWrapper, HipMultiVectorWrapper, HostDenseMatrix> : GenericSolverOps<HipOperatorWrapper, HipMultiVectorWrapper, HostDenseMatrix> {
     // Gram blocks of the projected form, maintained incrementally over the trips of one solve
     struct State {
         std::vector<double> SAA, SAB, SBB; // AV'AV (ld = cap), AV'B (ld = cap), B'B (p x p)
@@ -155,41 +153,26 @@ struct SolverOps<HipOperatorWrapper, HipMultiVectorWrapper, HostDenseMatrix> {
         return f;
     }
 
-    static int lanczos_fused(SolverT &solver, HipMultiVectorWrapper const &AV, HipMultiVectorWrapper const &MV, HostDenseMatrix const &T,
+    // the fused kernel, with B the solver's panel or, where `S` is given, a sparse right-hand side (rails_sprhs: any number of columns)
+    static int lanczos_fused(SolverT &solver, rails_sprhs *S, HipMultiVectorWrapper const &AV, HipMultiVectorWrapper const &MV, HostDenseMatrix const &T,
                              int max_iter, Lanczos &out)
     {
-        HipMultiVectorWrapper const &B = solver.B().panel();
         HostDenseMatrix H(max_iter + 1, max_iter + 1);
         HostDenseMatrix Tc = T.copy(); // contiguous copy, also drops a transpose flag
-        int steps = 0;
-        if (!hip_ok(rails_resid_lanczos(out.ctx, AV.panel(), AV.offset(), MV.panel(), MV.offset(), AV.N(), (double *)Tc, Tc.LDA(), B.panel(),
-                                        B.offset(), B.N(), max_iter, (double *)H, H.LDA(), &steps),
-                    "rails_resid_lanczos"))
-            return -1;
+        int steps = 0, rc;
+        if (S)
+            rc = rails_resid_lanczos_sparse(out.ctx, AV.panel(), AV.offset(), MV.panel(), MV.offset(), AV.N(), (double *)Tc, Tc.LDA(), S, max_iter, (double *)H,
+                                            H.LDA(), &steps);
+        else {
+            HipMultiVectorWrapper const &B = solver.B().panel();
+            rc = rails_resid_lanczos(out.ctx, AV.panel(), AV.offset(), MV.panel(), MV.offset(), AV.N(), (double *)Tc, Tc.LDA(), B.panel(), B.offset(), B.N(),
+                                     max_iter, (double *)H, H.LDA(), &steps);
+        }
+        if (!hip_ok(rc, S ? "rails_resid_lanczos_sparse" : "rails_resid_lanczos")) return -1;
         H.resize(steps, steps);
         out.v = HostDenseMatrix(steps, steps);
         out.eigenvalues = HostDenseMatrix(max_iter, 1);
         H.eigs(out.v, out.eigenvalues); // :441
-        out.steps = steps;
-        out.mode = 1;
-        return 0;
-    }
-
-    // the same with B a sparse right-hand side (rails_sprhs): any number of columns
-    static int lanczos_fused_sparse(rails_sprhs *S, HipMultiVectorWrapper const &AV, HipMultiVectorWrapper const &MV, HostDenseMatrix const &T,
-                                    int max_iter, Lanczos &out)
-    {
-        HostDenseMatrix H(max_iter + 1, max_iter + 1);
-        HostDenseMatrix Tc = T.copy();
-        int steps = 0;
-        if (!hip_ok(rails_resid_lanczos_sparse(out.ctx, AV.panel(), AV.offset(), MV.panel(), MV.offset(), AV.N(), (double *)Tc, Tc.LDA(), S, max_iter,
-                                               (double *)H, H.LDA(), &steps),
-                    "rails_resid_lanczos_sparse"))
-            return -1;
-        H.resize(steps, steps);
-        out.v = HostDenseMatrix(steps, steps);
-        out.eigenvalues = HostDenseMatrix(max_iter, 1);
-        H.eigs(out.v, out.eigenvalues);
         out.steps = steps;
         out.mode = 1;
         return 0;
@@ -421,13 +404,11 @@ struct SolverOps<HipOperatorWrapper, HipMultiVectorWrapper, HostDenseMatrix> {
                         (solver.B().panel().offset() & 1) == 0;
         if (solver.B().given_as_operator() && solver.B().op().sprhs() && AV.N() <= 512 && ((AV.offset() | MV.offset()) & 1) == 0) {
             st.fused_trips++;
-            return lanczos_fused_sparse(solver.B().op().sprhs(), AV, MV, T, max_iter, out);
+            return lanczos_fused(solver, solver.B().op().sprhs(), AV, MV, T, max_iter, out);
         }
         if (!can_fuse) {
-            HostDenseMatrix H(max_iter + 1, max_iter + 1);
-            out.eigenvalues = HostDenseMatrix(max_iter, 1);
             out.mode = 0;
-            return solver.resid_lanczos(AV, MV, T, H, out.eigenvectors, out.eigenvalues, max_iter);
+            return lanczos_by_members(solver, AV, MV, T, max_iter, out);
         }
         if (solver.projected_lanczos() && !solver.mass_matrix_in_use() && !st.below_noise_floor) {
             uint64_t seed = 0, stream = 0;
@@ -441,7 +422,7 @@ struct SolverOps<HipOperatorWrapper, HipMultiVectorWrapper, HostDenseMatrix> {
             rails_ctx_set_seed(out.ctx, seed, stream); // the fused form repeats the draw of the start vector
         }
         st.fused_trips++;
-        return lanczos_fused(solver, AV, MV, T, max_iter, out);
+        return lanczos_fused(solver, nullptr, AV, MV, T, max_iter, out);
     }
 
     // V <- V * X in place (row-local panel GEMM), then shrink to X.N() columns

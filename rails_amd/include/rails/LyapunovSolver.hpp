@@ -4,8 +4,10 @@
 // (src/LyapunovSolver.hpp:27-36,76-87) and return codes (0 converged / -1 stopped without converging / 1 trips used up,
 // :239-240,345; set_parameters 0 / 1, :89-97) -- and every DECISION is the reference's, cited where it is taken:
 // convergence (:223), when to stop (:224-241), when to shrink the space (:245-247), how many vectors to add (:306-307),
-// which (:336-339).  The organisation is this library's own: a solve is a Run object that owns the search space (V, A V, M V,
-// B'V), the reduced matrices (V'AV, V'BB'V, V'MV) and the settings, and advances by trips of four steps --
+// which (:336-339).  What a trip decides without computing -- how it ends, how much an expansion adds, which eigenvalues a selection
+// picks -- is rails/TripRule.hpp: pure functions, checked alone on the host.  The organisation is this library's own: a solve is a Run
+// object that owns the search space (V, A V, M V, B'V), the reduced matrices (V'AV, V'BB'V, V'MV) and the settings, and advances by
+// trips of four steps --
 //
 //     border    A (and M) applied to the columns added last; the reduced matrices get their new border
 //     reduce    the projected Lyapunov equation, on the host (rails_sb03md)
@@ -24,7 +26,6 @@
 #include <cctype>
 #include <chrono>
 #include <cmath>
-#include <cstdlib>
 #include <cstdio>
 #include <cstdlib>
 #include <functional>
@@ -36,6 +37,7 @@
 #include <utility>
 #include <vector>
 
+#include "rails/TripRule.hpp"
 #include "rails_hip.h"
 
 namespace rails
@@ -181,16 +183,21 @@ private:
     Both b_;
 };
 
-// Positions of the `count` entries of largest modulus, in the order the reference's selection produces them
-// (src/StlTools.hpp:12-30: std::sort by decreasing |value|; Ritz values come in +- pairs, so ties are common and the order
-// among them is whatever that sort yields -- an index sort with the same comparison makes the same moves).
+// a column of values as a plain array, for the selections of rails/TripRule.hpp
+template <class DenseMatrix>
+std::vector<double> plain_values(DenseMatrix const &values)
+{
+    std::vector<double> plain(values.M());
+    for (int i = 0; i < values.M(); ++i) plain[i] = values(i);
+    return plain;
+}
+
+// Positions of the `count` entries of largest modulus, in the order the reference's selection produces them (trip::largest_moduli).
 template <class DenseMatrix>
 int find_largest_eigenvalues(DenseMatrix const &values, std::vector<int> &positions, int count)
 {
-    std::vector<int> order(values.M());
-    std::iota(order.begin(), order.end(), 0);
-    std::sort(order.begin(), order.end(), [&values](int a, int b) { return std::abs(values(a)) > std::abs(values(b)); });
-    positions.insert(positions.end(), order.begin(), order.begin() + count);
+    const std::vector<double> plain = plain_values(values);
+    trip::largest_moduli(plain.data(), (int)plain.size(), count, positions);
     return 0;
 }
 
@@ -226,12 +233,36 @@ public:
     ~ScopedTimer() { *slot_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - start_).count(); }
 };
 
+// RAILS_SOLVER_TRIP_TRACE=x: after every trip that took more than x ms, its time per section on stderr.  lap() at the start of every trip.
+class TripTrace
+{
+    std::map<std::string, double> before_;
+    std::chrono::steady_clock::time_point start_ = std::chrono::steady_clock::now();
+
+public:
+    void lap(int trip, std::map<std::string, double> const &sections)
+    {
+        static const double trace_ms = getenv("RAILS_SOLVER_TRIP_TRACE") ? atof(getenv("RAILS_SOLVER_TRIP_TRACE")) : 0.0;
+        if (!(trace_ms > 0.0)) return;
+        const double ms = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - start_).count();
+        if (trip > 0 && ms > trace_ms) {
+            std::cerr << "[rails trip " << trip << "] " << ms << " ms:";
+            for (auto const &kv : sections) std::cerr << " " << kv.first << " " << 1e3 * (kv.second - before_[kv.first]);
+            std::cerr << std::endl;
+        }
+        before_ = sections;
+        start_ = std::chrono::steady_clock::now();
+    }
+};
+
 template <class Matrix, class MultiVector, class DenseMatrix>
 class Solver;
 
 // ---- customisation points; the generic versions go through the backend contract member by member -----------------------
+// SolverOps<...> is what the solver calls; it derives from GenericSolverOps, and a back end's specialisation does too and redefines
+// the members it replaces.
 template <class Matrix, class MultiVector, class DenseMatrix>
-struct SolverOps {
+struct GenericSolverOps {
     typedef Solver<Matrix, MultiVector, DenseMatrix> SolverT;
 
     // result of one residual estimate: Ritz values and a way to append selected Ritz vectors to V
@@ -256,13 +287,20 @@ struct SolverOps {
     struct State {
     };
 
-    // VAV and BV (the reduced operator and B'V) are passed along for backends that can use them
-    static int lanczos(SolverT &solver, State &, MultiVector const &AV, MultiVector const &MV, DenseMatrix const &T, DenseMatrix const &,
-                       MultiVector const &, int max_iter, Lanczos &out)
+    // the residual estimate by Solver::resid_lanczos, into any result that has `eigenvalues` and `eigenvectors`
+    template <class Result>
+    static int lanczos_by_members(SolverT &solver, MultiVector const &AV, MultiVector const &MV, DenseMatrix const &T, int max_iter, Result &out)
     {
         DenseMatrix H(max_iter + 1, max_iter + 1);
         out.eigenvalues = DenseMatrix(max_iter, 1);
         return solver.resid_lanczos(AV, MV, T, H, out.eigenvectors, out.eigenvalues, max_iter);
+    }
+
+    // VAV and BV (the reduced operator and B'V) are passed along for backends that can use them
+    static int lanczos(SolverT &solver, State &, MultiVector const &AV, MultiVector const &MV, DenseMatrix const &T, DenseMatrix const &,
+                       MultiVector const &, int max_iter, Lanczos &out)
+    {
+        return lanczos_by_members(solver, AV, MV, T, max_iter, out);
     }
 
     // after V <- V X and AV <- AV X (:265-291)
@@ -279,50 +317,20 @@ struct SolverOps {
 };
 
 template <class Matrix, class MultiVector, class DenseMatrix>
+struct SolverOps : GenericSolverOps<Matrix, MultiVector, DenseMatrix> {
+};
+
+template <class Matrix, class MultiVector, class DenseMatrix>
 class Solver
 {
 public:
     typedef SolverOps<Matrix, MultiVector, DenseMatrix> Ops;
     typedef BOperand<Matrix, MultiVector> BType;
 
-    // What a solve is asked to do; names and defaults of the reference's parameters (src/LyapunovSolver.hpp:27-36).
-    struct Settings {
-        int trip_limit = 1000;            // "Maximum iterations"
-        double tolerance = 1e-3;          // "Tolerance": on the residual estimate relative to ||B||^2
-        int expand_by = 3;                // "Expand size": residual directions added per trip
-        int lanczos_steps = 10;           // "Lanczos iterations"
-        int shrink_at = -1;               // "Restart size": space dimension that triggers a shrink (<= 0: never by size)
-        int shrink_to = -1;               // "Reduced size": dimension kept (<= 0: whatever passes keep_above)
-        int shrink_every = 20;            // "Restart iterations": trips between shrinks (<= 0: never by count)
-        double keep_above = 1e-3 * 1e-3;  // "Restart tolerance": |eigenvalue of T| a kept direction must exceed (absolute, :471)
-        bool shrink_on_convergence = true; // "Minimize solution space"
-        bool warm_start = false;          // "Restart from solution": V holds an orthonormal basis to continue from
-        bool shrink_at_start = false;     // "Restart upon start": shrink right after the first projected solve (opts.restart_upon_start)
-        double projection_method = 1.0;   // "Projection method": opts.projection_method of matlab/RAILSsolver.m:7-16 (see projection())
-    };
-
-    // The projection method, opts.projection_method of matlab/RAILSsolver.m:7-16,288-314,520-530: `pair` = the 2.x methods (every
-    // expansion adds [W, A^-1 W]; else 1.x adds A^-1 W), `start` = the decimal: 1 start from [V0, A^-1 V0] (2.1) or A^-1 V0 (1.1), 2 from
-    // [B, A^-1 B] or A^-1 B, 3 from V0 as method 1 does.  Method 1 (`start` 0) adds the Ritz vectors W themselves and never uses A^-1.
-    struct Projection {
-        bool pair = false;
-        int start = 0;
-        bool uses_inverse() const { return start != 0; }
-    };
-    // the method named by `value`, false if there is none (1, 1.1, 1.2, 1.3, 2.1, 2.2, 2.3)
-    static bool parse_projection(double value, Projection &out)
-    {
-        for (int family = 1; family <= 2; ++family)
-            for (int decimal = 0; decimal <= 3; ++decimal) {
-                if (family == 2 && decimal == 0) continue;
-                if (std::abs(value - (family + 0.1 * decimal)) < 1.5e-8) { // sqrt(eps), the reference's comparison (:293-304)
-                    out.pair = family == 2;
-                    out.start = decimal;
-                    return true;
-                }
-            }
-        return false;
-    }
+    // what a solve is asked to do, the projection method and its parser: rails/TripRule.hpp
+    typedef trip::Settings Settings;
+    typedef trip::Projection Projection;
+    static bool parse_projection(double value, Projection &out) { return trip::parse_projection(value, out); }
     Projection projection() const
     {
         Projection p;
@@ -400,7 +408,7 @@ public:
     // opts.space of matlab/RAILSsolver.m:25-28,160-204,310-314: with "Restart from solution" the caller's V is ANY start space -- a previous
     // solution's V, [V_prev, B], the union of two earlier solutions -- neither orthonormal nor independent.  The solve orthonormalises it
     // from column 0 with the nullspace projected out and drops every column of which less than 1e-8 survives (orthogonalize_range above;
-    // m_orthogonalize under mass_orthogonalisation()); it is refused (-2, V and T unchanged) when no column survives.
+    // gram_schmidt in M's inner product under mass_orthogonalisation()); it is refused (-2, V and T unchanged) when no column survives.
     void set_raw_start_space(bool on) { raw_start_ = on; }
     bool raw_start_space() const { return raw_start_; }
     // columns the last solve kept of its start space (1 after a cold start)
@@ -556,56 +564,64 @@ public:
         DenseMatrix vectors = T.copy(), values(k, 1);
         int info = 0;
         rails_dsyev('V', 'U', k, vectors, vectors.LDA(), values, &info);
-        const int wanted = num > 0 ? num : k;
-        std::vector<int> leading;
-        find_largest_eigenvalues(values, leading, wanted);
+        std::vector<int> columns;
+        const int kept = trip::restart_columns(plain_values(values).data(), k, num, tol, columns);
         // a column per candidate, filled where the eigenvalue passes; the count of passes is the width that remains (:468-478)
-        X = DenseMatrix(k, wanted);
-        int kept = 0;
-        for (int c = 0; c < wanted; ++c) {
-            if (!(std::abs(values(leading[c], 0)) > tol)) continue;
-            for (int r = 0; r < k; ++r) X(r, c) = vectors(r, leading[c]);
-            ++kept;
-        }
+        X = DenseMatrix(k, (int)columns.size());
+        for (int c = 0; c < (int)columns.size(); ++c)
+            for (int r = 0; r < k && columns[c] >= 0; ++r) X(r, c) = vectors(r, columns[c]);
         X.resize(k, kept);
         return 0;
     }
 
 private:
-    // `nullspace = Morth(opts.nullspace, [])` (matlab/RAILSsolver.m:221-222) into null_basis_: modified Gram-Schmidt, twice per column, in
-    // the inner product of V (M's under mass_orthogonalisation()); a column of which less than 1e-8 survives is dropped, as m_orthogonalize
-    // drops one.  Returns the rank kept, or -2 (with a message) when the solve has to be refused.
+    // Modified Gram-Schmidt on X's columns from `first` on, in the M inner product (`in_M`) or the Euclidean one (matlab/RAILSsolver.m:583-597,
+    // Morth): every column is scaled to unit length, projected against all columns before it (twice: the reference's single sweep leaves a
+    // component of relative size eps * cond, and V'MV = I is what makes the projected equation the standard one), normalised in the inner
+    // product, and DROPPED when less than 1e-8 of it is left (:592-594; a column of norm zero, or not finite, is dropped too) -- the later
+    // columns move up and X ends with fewer columns than it came with.  With N (orthonormal in the same inner product) every pass
+    // projects it out first, with the same M v: `v -= n_i (n_i' M v)` (:600-616).  Returns the columns kept from `first` on.
+    int gram_schmidt(MultiVector &X, int first, bool in_M, MultiVector const *N)
+    {
+        int n = X.N(), j = first;
+        while (j < n) {
+            MultiVector v = X.view(j);
+            const double n0 = v.norm();
+            double nrm = 0.0;
+            if (n0 > 0.0 && std::isfinite(n0)) {
+                v /= n0;
+                for (int pass = 0; pass < 2 && (N || j > 0); ++pass) {
+                    MultiVector const Mv = in_M ? MultiVector(op_M_ * v) : MultiVector(v);
+                    if (N) v -= *N * N->dot(Mv);
+                    if (j > 0) {
+                        MultiVector const before = X.view(0, j - 1);
+                        v -= before * before.dot(Mv);
+                    }
+                }
+                MultiVector const Mv = in_M ? MultiVector(op_M_ * v) : MultiVector(v);
+                nrm = std::sqrt(std::abs(v.dot(Mv)(0, 0))); // (a definite M of either sign: the MOC data's mass entries are negative)
+            }
+            if (!(nrm >= 1e-8)) { // nothing new in this column: the later ones move up
+                for (int l = j + 1; l < n; ++l) X.view(l - 1) = X.view(l);
+                X.resize(--n);
+                continue;
+            }
+            v /= nrm;
+            ++j;
+        }
+        return n - first;
+    }
+
+    // `nullspace = Morth(opts.nullspace, [])` (matlab/RAILSsolver.m:221-222) into null_basis_: gram_schmidt in the inner product of V (M's
+    // under mass_orthogonalisation()).  Returns the rank kept, or -2 (with a message) when the solve has to be refused.
     int prepare_nullspace(int n)
     {
         if (nullspace_.M() != n) {
             std::cerr << "rails::Solver: the nullspace has " << nullspace_.M() << " rows, A has " << n << std::endl;
             return -2;
         }
-        const bool in_M = mass_orthogonalisation();
         MultiVector Q(nullspace_);
-        int q = Q.N(), j = 0;
-        while (j < q) {
-            MultiVector v = Q.view(j);
-            const double n0 = v.norm();
-            double nrm = 0.0;
-            if (n0 > 0.0 && std::isfinite(n0)) {
-                v /= n0;
-                for (int pass = 0; pass < 2 && j > 0; ++pass) {
-                    MultiVector const before = Q.view(0, j - 1);
-                    MultiVector const Mv = in_M ? MultiVector(op_M_ * v) : MultiVector(v);
-                    v -= before * before.dot(Mv);
-                }
-                MultiVector const Mv = in_M ? MultiVector(op_M_ * v) : MultiVector(v);
-                nrm = std::sqrt(std::abs(v.dot(Mv)(0, 0)));
-            }
-            if (!(nrm >= 1e-8)) {
-                for (int l = j + 1; l < q; ++l) Q.view(l - 1) = Q.view(l);
-                Q.resize(--q);
-                continue;
-            }
-            v /= nrm;
-            ++j;
-        }
+        const int q = gram_schmidt(Q, 0, mass_orthogonalisation(), nullptr);
         if (q == 0) {
             std::cerr << "rails::Solver: the nullspace has no independent column" << std::endl;
             return -2;
@@ -642,22 +658,10 @@ private:
 
         int go()
         {
-            if (!open()) return -2;
-            // RAILS_SOLVER_TRIP_TRACE=x: after every trip that took more than x ms, its time per section on stderr
-            static const double trace_ms = getenv("RAILS_SOLVER_TRIP_TRACE") ? atof(getenv("RAILS_SOLVER_TRIP_TRACE")) : 0.0;
-            std::map<std::string, double> before;
-            auto trip_start = std::chrono::steady_clock::now();
+            if (!open()) return trip::Refused;
+            TripTrace trace;
             for (trip_ = 0; trip_ < opt_.trip_limit; ++trip_) {
-                if (trace_ms > 0.0) {
-                    const double ms = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - trip_start).count();
-                    if (trip_ > 0 && ms > trace_ms) {
-                        std::cerr << "[rails trip " << trip_ << "] " << ms << " ms:";
-                        for (auto const &kv : s_.sections_) std::cerr << " " << kv.first << " " << 1e3 * (kv.second - before[kv.first]);
-                        std::cerr << std::endl;
-                    }
-                    before = s_.sections_;
-                    trip_start = std::chrono::steady_clock::now();
-                }
+                trace.lap(trip_, s_.sections_);
                 s_.notify();
                 const int width_before = V_.N();
                 if (fresh_.N()) border();
@@ -665,31 +669,27 @@ private:
                 typename Ops::Lanczos ritz;
                 const double estimate = estimate_residual(ritz);
                 const bool converged = std::abs(estimate) < opt_.tolerance * scale_; // :223
-
-                // Stop?  Convergence ends the run unless the space is to be minimised first: then the first convergence only
-                // triggers a shrink and the second one ends it.  Running out of trips or of dimensions ends it either way (:224-241).
-                if (converged || trip_ + 1 >= opt_.trip_limit || V_.N() >= n_) {
-                    if (converged && opt_.shrink_on_convergence && !converged_once_)
-                        converged_once_ = true;
-                    else
-                        return finish(converged, estimate);
-                }
-                if (s_.broken_ && s_.broken_()) { // extension: the back end has latched a failure -- no point in running on (the caller reports it)
+                const trip::Verdict end = trip::verdict(opt_, trip_, V_.N(), n_, last_shrink_, converged, converged_once_, s_.trips_, s_.trip_budget_,
+                                                        [this]() { return s_.broken_ && s_.broken_(); });
+                converged_once_ = end.converged_once;
+                switch (end.action) {
+                case trip::Finish:
+                    finish(converged, estimate);
+                    return end.code;
+                case trip::Failed:
+                case trip::OutOfBudget:
                     s_.notify();
-                    return -1;
+                    return end.code;
+                case trip::Shrink:
+                    shrink(end.reason);
+                    break;
+                case trip::Expand:
+                    expand(ritz, width_before);
+                    break;
                 }
-                if (s_.trip_budget_ > 0 && s_.trips_ >= s_.trip_budget_) { // extension: bounded run
-                    s_.notify();
-                    return 2;
-                }
-                if (shrink_due(converged)) {
-                    shrink(converged);
-                    continue;
-                }
-                expand(ritz, width_before);
             }
             s_.notify();
-            return 1;
+            return trip::TripsUsedUp;
         }
 
     private:
@@ -702,23 +702,15 @@ private:
             s_.estimates_.clear();
             s_.start_rank_ = 0;
             if (opt_.warm_start && s_.raw_start_ && !orthonormalise_start_space()) return false;
-            capacity_ = std::max(V_.N(), std::min(opt_.shrink_at > 0 ? opt_.shrink_at : 100, n_));
+            capacity_ = trip::opening_capacity(opt_, V_.N(), n_);
             if (!opt_.warm_start) {
                 V_.resize(capacity_);
                 V_.resize(1);
                 V_.random();
-                if (s_.mass_orthogonalisation())
-                    m_orthogonalize(0);
-                else
-                    orthogonalize(0);
+                orthonormalise(0);
             } else {
                 if (V_.N() != capacity_) reserve_columns(V_, capacity_);
-                if (deflating() && !s_.raw_start_) { // the caller's V loses its part along the nullspace like any start space (matlab/RAILSsolver.m:311-313)
-                    if (s_.mass_orthogonalisation())
-                        m_orthogonalize(0);
-                    else
-                        orthogonalize(0);
-                }
+                if (deflating() && !s_.raw_start_) orthonormalise(0); // the caller's V loses its part along the nullspace like any start space (matlab/RAILSsolver.m:311-313)
             }
             const Projection proj = s_.projection();
             if (proj.uses_inverse() && proj.start != 3) open_with_inverse(proj);
@@ -745,7 +737,7 @@ private:
             MultiVector const saved(V_);
             int kept = 0;
             if (s_.mass_orthogonalisation())
-                kept = m_orthogonalize(0);
+                kept = orthonormalise(0);
             else
                 kept = orthogonalize_range(V_, deflating() ? &s_.null_basis_ : (MultiVector const *)nullptr, 1e-8, has_range_orthogonalize<MultiVector>());
             if (kept < 1) {
@@ -772,21 +764,23 @@ private:
             V_.resize(0);
             if (proj.pair) V_.push_back(V0);
             V_.push_back(inv);
-            if (s_.mass_orthogonalisation())
-                m_orthogonalize(0);
-            else
-                orthogonalize(0);
+            orthonormalise(0);
         }
 
         bool deflating() const { return s_.null_rank_ > 0; }
 
-        // V's columns from `first` on (the ones past the watermark), orthonormalised; with a nullspace, against it as well (:556-579)
-        void orthogonalize(int first)
+        // V's columns from `first` on (the ones past the watermark), orthonormalised; with a nullspace, against it as well (:556-579).  Under
+        // mass_orthogonalisation() in the M inner product (gram_schmidt), where dependent columns are dropped.  Returns the columns kept.
+        int orthonormalise(int first)
         {
-            if (deflating())
-                orthogonalize_deflated(V_, s_.null_basis_, first, has_deflated_orthogonalize<MultiVector>());
+            MultiVector const *N = deflating() ? &s_.null_basis_ : nullptr;
+            if (s_.mass_orthogonalisation()) return s_.gram_schmidt(V_, first, true, N);
+            const int added = V_.N() - first;
+            if (N)
+                orthogonalize_deflated(V_, *N, first, has_deflated_orthogonalize<MultiVector>());
             else
                 V_.orthogonalize();
+            return added;
         }
 
         // capacity change that keeps the columns in use (resize up, then back: the contract's resize preserves data, src/StlWrapper.cpp:225-263)
@@ -801,6 +795,19 @@ private:
             const int in_use = S.M();
             S.resize(order, order);
             S.resize(in_use, in_use);
+        }
+
+        // RAILS_DEBUG_DUMP_PROJECTED=file (diagnostics): the projected matrices of every trip appended to it, as text
+        static void dump_projected(DenseMatrix const &a, DenseMatrix const &b)
+        {
+            const char *dump = getenv("RAILS_DEBUG_DUMP_PROJECTED");
+            FILE *f = dump ? fopen(dump, "a") : nullptr;
+            if (!f) return;
+            const int k = a.M();
+            fprintf(f, "%d\n", k);
+            for (int j = 0; j < k; ++j)
+                for (int i = 0; i < k; ++i) fprintf(f, "%.17g %.17g\n", (double)a(i, j), (double)b(i, j));
+            fclose(f);
         }
 
         // block (r0.., c0..) of S <- G
@@ -851,15 +858,7 @@ private:
         void reduce()
         {
             ScopedTimer t(&s_.sections_, "dense_solve");
-            if (const char *dump = getenv("RAILS_DEBUG_DUMP_PROJECTED")) { // diagnostics: the projected matrices of this trip, as text
-                if (FILE *f = fopen(dump, "a")) {
-                    const int k = a_.M();
-                    fprintf(f, "%d\n", k);
-                    for (int j = 0; j < k; ++j)
-                        for (int i = 0; i < k; ++i) fprintf(f, "%.17g %.17g\n", (double)a_(i, j), (double)b_(i, j));
-                    fclose(f);
-                }
-            }
+            dump_projected(a_, b_);
             if (s_.mass_ && !s_.ortho_m_)
                 s_.generalized_dense_solve(a_, b_, m_, T_);
             else
@@ -882,32 +881,21 @@ private:
             return estimate;
         }
 
-        int finish(bool converged, double estimate)
+        void finish(bool converged, double estimate)
         {
             if (s_.verbose_)
                 std::cout << "rails::Solver: " << (converged ? "converged" : "stopped without converging") << " after " << trip_ + 1
                           << " trips, residual estimate " << estimate / scale_ << " of ||B||^2, " << V_.N() << " basis vectors" << std::endl;
             s_.notify();
-            return converged ? 0 : -1;
-        }
-
-        // by size, by trips since the last shrink, or on (first) convergence (:245-247)
-        bool shrink_due(bool converged) const
-        {
-            // opts.restart_upon_start (matlab/RAILSsolver.m:53-57,455): the first trip of a start space of more than one column ends in a
-            // shrink.  (A single column -- every cold start -- has nothing to give up, and a shrink would only cost it a trip.)
-            const bool at_start = opt_.shrink_at_start && trip_ == 0 && V_.N() > 1;
-            return at_start || (opt_.shrink_at > 0 && V_.N() >= opt_.shrink_at) || (opt_.shrink_every > 0 && trip_ - last_shrink_ >= opt_.shrink_every) || converged;
         }
 
         // V <- V X with X the dominant eigenvectors of T; everything expressed in V follows (:263-298, matlab/RAILSsolver.m:499-504).
         // The next trip multiplies nothing (no fresh columns, :284) and V is not re-orthogonalised (X has orthonormal columns, :270).
-        void shrink(bool converged)
+        void shrink(trip::ShrinkReason reason)
         {
             if (s_.verbose_)
-                std::cout << "rails::Solver: shrinking the space ("
-                          << (converged ? "converged" : (opt_.shrink_at > 0 && V_.N() >= opt_.shrink_at ? "size limit" : "trip count")) << "), asking for "
-                          << (opt_.shrink_to > 0 ? opt_.shrink_to : V_.N()) << " of " << V_.N() << " vectors" << std::endl;
+                std::cout << "rails::Solver: shrinking the space (" << trip::text(reason) << "), asking for " << (opt_.shrink_to > 0 ? opt_.shrink_to : V_.N())
+                          << " of " << V_.N() << " vectors" << std::endl;
             ScopedTimer t(&s_.sections_, "Restart");
             DenseMatrix X;
             s_.compute_restart_vectors(X, T_, std::min(opt_.shrink_to, V_.N()), opt_.keep_above);
@@ -933,25 +921,15 @@ private:
             last_shrink_ = trip_;
         }
 
-        // The Ritz vectors of the `add` largest |Ritz values| join V: add = min(expand_by, Ritz values available, room up to shrink_at
-        // or n) (:306-307); capacity grows by 100 columns at a time (:311-332); only the new columns are orthogonalised (:340) and
-        // they are the fresh ones of the next trip (:342).
-        // Methods other than 1 replace W by A^-1 W (1.x) or add [W, A^-1 W] (2.x: then at most half the room goes to Ritz vectors; with
-        // one column of room left only W joins) (matlab/RAILSsolver.m:520-530).
+        // The Ritz vectors of the `add` largest |Ritz values| join V, as they are, replaced by A^-1 W or paired with it, in the room
+        // that trip::plan_expansion works out; only the new columns are orthogonalised (:340) and they are the fresh ones of the next
+        // trip (:342).
         void expand(typename Ops::Lanczos const &ritz, int width_before)
         {
-            const Projection proj = s_.projection();
-            const int room = (opt_.shrink_at > 0 ? opt_.shrink_at : n_) - V_.N();
-            int add = std::min(std::min(opt_.expand_by, ritz.eigenvalues.M()), room);
-            bool pair = proj.uses_inverse() && proj.pair;
-            const bool replace = proj.uses_inverse() && !proj.pair;
-            if (pair && room >= 2)
-                add = std::min(add, room / 2);
-            else
-                pair = false;
-            const int grow = pair ? 2 * add : add;
-            if (V_.N() + grow > capacity_) {
-                capacity_ += std::max(100, V_.N() + grow - capacity_);
+            const trip::Expansion plan = trip::plan_expansion(opt_, s_.projection(), V_.N(), n_, ritz.eigenvalues.M(), capacity_);
+            const int add = plan.add;
+            if (plan.capacity != capacity_) {
+                capacity_ = plan.capacity;
                 reserve_columns(V_, capacity_);
                 reserve_columns(AV_, capacity_);
                 reserve_order(a_, capacity_);
@@ -968,67 +946,21 @@ private:
                 ScopedTimer t(&s_.sections_, "Expand");
                 ritz.append_to(V_, leading, add);
             }
-            if ((pair || replace) && add > 0) {
+            if ((plan.pair || plan.replace) && add > 0) {
                 MultiVector inv;
                 {
                     ScopedTimer t(&s_.sections_, "Apply Ainv");
                     inv = s_.op_Ainv_ * V_.view(width_before, width_before + add - 1);
                 }
-                if (replace) V_.resize(width_before);
+                if (plan.replace) V_.resize(width_before);
                 V_.push_back(inv);
             }
-            int kept = proj.uses_inverse() ? V_.N() - width_before : add;
+            int kept = 0;
             {
                 ScopedTimer t(&s_.sections_, "Orthogonalize");
-                if (s_.mass_orthogonalisation())
-                    kept = m_orthogonalize(width_before);
-                else
-                    orthogonalize(width_before);
+                kept = orthonormalise(width_before);
             }
             fresh_ = V_.view(width_before, width_before + kept - 1);
-        }
-
-        // Modified Gram-Schmidt in the M inner product on the columns from `first` on (matlab/RAILSsolver.m:583-597, Morth with M): every
-        // new column is normalised, M-projected against all columns before it (twice: the reference's single sweep leaves a component
-        // of relative size eps * cond, and V'MV = I is what makes the projected equation the standard one), M-normalised, and DROPPED
-        // when less than 1e-8 of it is left (:592-594) -- V then grows by fewer columns than asked for.  Returns the columns kept.
-        // With a nullspace (M-orthonormal here) every pass projects it out first, with the same M v: `v -= n_i (n_i' M v)` (:600-616).
-        int m_orthogonalize(int first)
-        {
-            int n = V_.N(), j = first;
-            while (j < n) {
-                MultiVector v = V_.view(j);
-                v /= v.norm();
-                if (deflating()) {
-                    MultiVector const &N = s_.null_basis_;
-                    for (int pass = 0; pass < 2; ++pass) {
-                        MultiVector const Mv = s_.op_M_ * v;
-                        v -= N * N.dot(Mv);
-                        if (j > 0) {
-                            MultiVector const before = V_.view(0, j - 1);
-                            v -= before * before.dot(Mv);
-                        }
-                    }
-                } else if (j > 0) {
-                    MultiVector const before = V_.view(0, j - 1);
-                    for (int pass = 0; pass < 2; ++pass) {
-                        MultiVector const Mv = s_.op_M_ * v;
-                        v -= before * before.dot(Mv);
-                    }
-                }
-                MultiVector const Mv = s_.op_M_ * v;
-                DenseMatrix const vMv = v.dot(Mv);
-                const double energy = std::abs(vMv(0, 0)); // (a definite M of either sign: the MOC data's mass entries are negative)
-                const double nrm = std::sqrt(energy);
-                if (!(nrm >= 1e-8)) { // nothing new in this column: the later ones move up
-                    for (int l = j + 1; l < n; ++l) V_.view(l - 1) = V_.view(l);
-                    V_.resize(--n);
-                    continue;
-                }
-                v /= nrm;
-                ++j;
-            }
-            return n - first;
         }
     };
     friend class Run;

@@ -11,31 +11,7 @@ namespace rails
 
 // the restart products are coefficient GEMMs; afterwards the basis is re-based on what is still alive
 template <>
-struct SolverOps<SubspaceOperator, SubspaceMultiVector, HostDenseMatrix> {
-    typedef Solver<SubspaceOperator, SubspaceMultiVector, HostDenseMatrix> SolverT;
-    struct State {
-    };
-    struct Lanczos {
-        HostDenseMatrix eigenvalues;
-        SubspaceMultiVector eigenvectors;
-        void append_to(SubspaceMultiVector &V, std::vector<int> const &indices, int count) const
-        {
-            for (int i = 0; i < count; i++) V.push_back(eigenvectors.view(indices[i]));
-        }
-    };
-    static SubspaceMultiVector apply_append(SubspaceOperator const &A, SubspaceMultiVector const &W, SubspaceMultiVector &AV)
-    {
-        SubspaceMultiVector AW = A * W;
-        AV.push_back(AW);
-        return AW;
-    }
-    static int lanczos(SolverT &solver, State &, SubspaceMultiVector const &AV, SubspaceMultiVector const &MV, HostDenseMatrix const &T,
-                       HostDenseMatrix const &, SubspaceMultiVector const &, int max_iter, Lanczos &out)
-    {
-        HostDenseMatrix H(max_iter + 1, max_iter + 1);
-        out.eigenvalues = HostDenseMatrix(max_iter, 1);
-        return solver.resid_lanczos(AV, MV, T, H, out.eigenvectors, out.eigenvalues, max_iter);
-    }
+struct SolverOps<SubspaceOperator, SubspaceMultiVector, HostDenseMatrix> : GenericSolverOps<SubspaceOperator, SubspaceMultiVector, HostDenseMatrix> {
     static void multiply_inplace(SubspaceMultiVector &V, HostDenseMatrix const &X)
     {
         V.view(0, X.N() - 1) = V * X;

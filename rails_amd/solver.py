@@ -145,7 +145,7 @@ class Solver:
         return self.lib.rails_solver_trips(self.h)
 
     def scale(self):
-        """||B||_2^2 as the last solve computed it (the scale of the stopping test); 0 when the coordinate-space back end ran"""
+        """||B||_2^2 as the last solve computed it (the scale of the stopping test), on either back end; 0 before the first solve"""
         out = C.c_double(0.0)
         check(self.lib.rails_solver_scale(self.h, C.byref(out)), "rails_solver_scale")
         return out.value

@@ -585,3 +585,70 @@ def test_subspace_backend_rejected_prediction_is_loud_and_ends_the_run():
     trips = int(out.stdout.split("FAILED LOUDLY after")[1].split()[0])
     assert trips <= 6, out.stdout  # the third overlapped block is read back at the fourth or fifth trip: the run ends there
     assert "did not confirm its prediction" in out.stderr
+
+
+def _n20_solver(ctx, B, options=None, params=None):
+    """a solver on the n = 20 tridiagonal problem, bounded to three trips (none of the tests below needs convergence)"""
+    import rails_amd
+    from rails_amd import problems as P
+
+    A, _ = _tridiagonal_problem(20, 2)
+    ctx.set_seed(1, 0)
+    s = rails_amd.Solver(ctx, rails_amd.HipOperatorWrapper(ctx, *P.dense_to_csr(A)), B)
+    assert s.set_parameters(params or {}) == 0
+    for name, value in {"verbose": 0, "max_trips": 3, **(options or {})}.items():
+        s.set_option(name, value)
+    return s
+
+
+def test_scale_is_the_norm_of_B_squared_on_either_back_end(ctx):
+    """rails_solver_scale after a cold solve on the default (coordinate-space) back end: ||B||_2^2, as include/rails_solver.h says and as
+    the direct back end reports for the same B.  (Before the solve's outcome became one record for both back ends it was 0.)"""
+    _, B = _tridiagonal_problem(20, 2)
+    expected = np.linalg.norm(B, 2) ** 2
+    scales = {}
+    for subspace in (1, 0):
+        s = _n20_solver(ctx, B, {"subspace": subspace})
+        assert s.scale() == 0.0  # before the first solve
+        code, V, T = s.solve()
+        assert code in (0, 2) and 1 <= s.trips() <= 3 and bool(s.backend_stats()) == bool(subspace)
+        scales[subspace] = s.scale()
+        s.close()
+    print("scale: coordinate %.17g direct %.17g ||B||^2 %.17g" % (scales[1], scales[0], expected))
+    assert abs(scales[1] - expected) <= 1e-14 * expected
+    assert abs(scales[1] - scales[0]) <= 1e-14 * scales[0]
+
+
+# the rows of rails_amd/csrc/solve_choice.h that the Python API reaches: what the solve is given, and whether the coordinate-space back end takes it
+BACKEND_ROWS = {
+    "default": (dict(), True),
+    "subspace=0": (dict(subspace=0), False),
+    "sparse B": (dict(sparse=True), False),
+    "caller's V": (dict(V0=True), True),
+    "start space": (dict(start=True), True),
+    "start space with a nullspace": (dict(start=True, nullspace=True), False),
+    "Restart from solution without a V": (dict(restart=True), False),
+}
+
+
+@pytest.mark.parametrize("row", list(BACKEND_ROWS))
+def test_which_back_end_takes_a_solve(ctx, row):
+    import scipy.sparse as sp
+
+    given, coordinate = BACKEND_ROWS[row]
+    _, B = _tridiagonal_problem(20, 2)
+    g = np.random.default_rng(6)
+    params = {"Restart from solution": 1} if given.get("restart") or given.get("V0") else {}
+    s = _n20_solver(ctx, sp.csr_matrix(B) if given.get("sparse") else B, {"subspace": given.get("subspace", 1)}, params)
+    if given.get("nullspace"):
+        N = np.zeros((20, 2))
+        N[0, 0] = N[1, 1] = 1.0  # orthogonal to B, which has its one entry in the last row
+        s.set_nullspace(N)
+    if given.get("start"):
+        s.set_start_space(g.uniform(-1, 1, (20, 3)))
+    V0 = np.linalg.qr(g.uniform(-1, 1, (20, 2)))[0] if given.get("V0") else None
+    code, V, T = s.solve(V0=V0)
+    assert code in (0, 2) and 1 <= s.trips() <= 3
+    assert bool(s.backend_stats()) == coordinate
+    assert s.nullspace_rank == (2 if given.get("nullspace") else 0)
+    s.close()
