@@ -346,6 +346,42 @@ int64_t rails_csr_cols(const rails_csr *A);
 /* the sparse right-hand side behind a handle made by rails_csr_create_sprhs, NULL for any other operator */
 rails_sprhs *rails_csr_sprhs(const rails_csr *A);
 
+/* ---- block-CSR operators (rails_amd/csrc/bsr_host.cpp, bsr_choice.h, spmm_bsr.hip) -------------------------------------------------------
+ * A sparse matrix of dense b x b blocks, 2 <= b <= 8 (the Jacobian of a PDE system with b unknowns per cell).  Block rows in CSR form:
+ * browptr (int64, mb + 1), bcol (int32 block-column indices), bval (nnzb * b * b doubles, every block row-major) -- the layout of scipy's
+ * bsr_matrix (indptr, indices, data[nnzb, b, b]).  A gathered row of X serves the b scalar rows of a block row from registers, and an
+ * index costs 4 / b^2 bytes per scalar entry.  The product is bit for bit the row-gather product (rails_csr_set_variant 3) of the
+ * expanded CSR matrix: every Y[i, j] one accumulator from +0, one fused multiply-add per stored entry of scalar row i in stored order,
+ * the zeros inside a block included. */
+
+/* Host only.  *nnzb = the number of b x b blocks that the entries of a CSR matrix (m x n_cols, both multiples of b) touch.  RAILS_EINVAL
+ * with a text for a b outside 2 .. 8, sizes that are no multiples of b, a rowptr that does not start at 0 or decreases and a column
+ * outside [0, n_cols); nothing is read out of range (this holds for the three functions). */
+int rails_bsr_count_host(int64_t m, int64_t n_cols, int b, const int64_t *rowptr, const int32_t *col, int64_t *nnzb);
+/* Host only.  Fills browptr (m / b + 1), bcol and bval (as many blocks as rails_bsr_count_host counts; zeros where a touched block has
+ * no entry).  Block columns ascend within a block row; the CSR columns may come in any order; duplicate entries are added in stored order. */
+int rails_bsr_fill_host(int64_t m, int64_t n_cols, int b, const int64_t *rowptr, const int32_t *col, const double *val, int64_t *browptr,
+                        int32_t *bcol, double *bval);
+/* Host only.  The transposed block matrix (nb block rows, mb block columns): a stable counting sort by block column, as
+ * rails_csr_transpose_host, with every block transposed. */
+int rails_bsr_transpose_host(int64_t mb, int64_t nb, int b, const int64_t *browptr, const int32_t *bcol, const double *bval,
+                             int64_t *t_browptr, int32_t *t_bcol, double *t_bval);
+/* An operator handle over a block-CSR matrix of mb block rows: rails_spmm multiplies by it (both trans values; the transposed copy is
+ * made on the host at the first transposed product), rails_csr_rows is mb * b and rails_csr_nnz nnzb * b * b, rails_csr_prepare and
+ * rails_csr_set_variant are accepted and change nothing.  Square only (nb_ext == mb) and single GPU only: RAILS_EINVAL on a context with
+ * a partition, an all-reduce hook or a communicator, and from rails_csr_set_halo.  rails_iter_create takes the handle as it takes a
+ * callback operator (no Jacobi diagonal unless one is given); "amg" over it is refused, and "poly_degree" without "eig_max" fails the
+ * solve, both with RAILS_EINVAL: they read scalar CSR arrays, which the handle does not keep. */
+int rails_csr_create_bsr(rails_ctx *ctx, int64_t mb, int64_t nb_ext, int b, const int64_t *browptr, const int32_t *bcol, const double *bval,
+                         rails_csr **out);
+/* b of a block-CSR handle, 1 for every other kind of handle */
+int rails_csr_block_size(const rails_csr *A);
+/* info[0 .. cap): nnzb, b, blocks of the longest block row, bytes on the device (the transposed copy included once it exists), then of the
+ * last launch (zeros before the first): b, lanes per block row, threads per workgroup, block rows per lane group, whether every
+ * workgroup's run of blocks fits the LDS buffer, grid: 10 values, the first min(cap, 10) are written.  RAILS_EINVAL for another kind of
+ * handle. */
+int rails_csr_bsr_stats(const rails_csr *A, int64_t *info, int cap);
+
 typedef struct rails_sweep_plan rails_sweep_plan;
 int rails_sweep_plan_create(int64_t m, int64_t ncols, const int64_t *rowptr, const int32_t *col, const double *val,
                             const int *params, rails_sweep_plan **out);

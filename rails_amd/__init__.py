@@ -11,5 +11,5 @@ from .solution import Solution  # noqa: F401
 from .solver import Solver  # noqa: F401
 from .sparse_rhs import SparseRHS, resid_lanczos_sparse  # noqa: F401
 from .splu import SparseLU  # noqa: F401
-from .wrappers import (Context, HipMultiVectorWrapper, HipOperatorWrapper, lanczos_vectors,  # noqa: F401
+from .wrappers import (Context, HipMultiVectorWrapper, HipOperatorWrapper, csr_to_bsr, lanczos_vectors,  # noqa: F401
                        resid_lanczos)

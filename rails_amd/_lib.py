@@ -104,6 +104,12 @@ SIGNATURES = {
     "rails_iter_destroy": (None, [_vp]),
     "rails_csr_transpose_host": (C.c_int, [C.c_int64, C.c_int64, _i64p, _i32p, _dp, _i64p, _i32p, _dp]),
     "rails_csr_gram_norm2_host": (C.c_int, [C.c_int64, C.c_int64, _i64p, _i32p, _dp, _i64p, _i32p, _dp, _dp]),
+    "rails_bsr_count_host": (C.c_int, [C.c_int64, C.c_int64, C.c_int, _i64p, _i32p, _i64p]),
+    "rails_bsr_fill_host": (C.c_int, [C.c_int64, C.c_int64, C.c_int, _i64p, _i32p, _dp, _i64p, _i32p, _dp]),
+    "rails_bsr_transpose_host": (C.c_int, [C.c_int64, C.c_int64, C.c_int, _i64p, _i32p, _dp, _i64p, _i32p, _dp]),
+    "rails_csr_create_bsr": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int, _i64p, _i32p, _dp, C.POINTER(_vp)]),
+    "rails_csr_block_size": (C.c_int, [_vp]),
+    "rails_csr_bsr_stats": (C.c_int, [_vp, _i64p, C.c_int]),
     "rails_sprhs_create": (C.c_int, [_vp, C.c_int64, C.c_int, _i64p, _i32p, _dp, C.POINTER(_vp)]),
     "rails_sprhs_destroy": (None, [_vp]),
     "rails_sprhs_rows": (C.c_int64, [_vp]),

@@ -182,6 +182,7 @@ int amg_check(const rails_iter *it, const char *who)
     RAILS_REQUIRE(it->poly_degree == 0, "%s: \"amg\" together with poly_degree %d: one preconditioner at a time", who, it->poly_degree);
     RAILS_REQUIRE(A->kind != rails_csr::CALLBACK, "%s: \"amg\" needs the entries of the matrix: the operator is a callback", who);
     RAILS_REQUIRE(A->kind != rails_csr::LU && A->kind != rails_csr::ITER, "%s: \"amg\" needs the entries of the matrix: the operator is an LU or an iterative solve", who);
+    RAILS_REQUIRE(A->kind != rails_csr::BSR, "%s: \"amg\" needs the entries of the matrix as scalar CSR arrays: the operator is block-CSR (keep a CSR handle for the preconditioner)", who);
     RAILS_REQUIRE(!it->reduces && A->n_ghost == 0 && A->n_send == 0,
                   "%s: \"amg\" on a context that reduces (more than one rank, an all-reduce hook or a communicator): the multigrid preconditioner is single GPU", who);
     RAILS_REQUIRE(it->m < ((int64_t)1 << 24), "%s: \"amg\" on %lld rows: the multigrid preconditioner takes fewer than 2^24", who, (long long)it->m);
@@ -509,6 +510,8 @@ int plan_call(Run &run, const char *who)
     if (run.K == 0) return RAILS_OK;
     Sweep &s = run.sw[0];
     const double hi = poly_hi(it);
+    RAILS_REQUIRE((hi > 0.0 && rails_iter_finite(hi)) || run.it->A->kind != rails_csr::BSR,
+                  "%s: poly_degree %d needs an upper bound on the spectrum: a block-CSR operator keeps no scalar CSR arrays to take one from, set \"eig_max\"", who, run.K);
     RAILS_REQUIRE(hi > 0.0 && rails_iter_finite(hi),
                   "%s: poly_degree %d needs an upper bound on the spectrum: the operator keeps no CSR arrays on the host to take one from, set \"eig_max\"", who, run.K);
     RAILS_REQUIRE(rails_cheb_coef(hi / it->poly_ratio, hi, run.K, &s.theta, s.a, s.b), "%s: no polynomial of degree %d on [%g, %g]", who, run.K, hi / it->poly_ratio, hi);

@@ -142,6 +142,7 @@ struct rails_panel {
 struct rails_planes_plan; // spmm_planes.hip: coefficient records of a structured-grid stencil
 struct rails_sweep_cache; // spmm_sweep.hip: device copies of the sweep kernel's schedules, one per column-chunk count
 struct rails_tile_cache;  // spmm_tiled.hip: device copy of the LDS-staged kernels' tile plan (tile_plan.h) and what they last launched
+struct rails_bsr;         // spmm_bsr.hip: a block-CSR matrix on the device, with its host copy and its lazily built transposed copy
 
 struct rails_csr {
     rails_ctx *ctx = nullptr;
@@ -178,13 +179,15 @@ struct rails_csr {
     // What rails_spmm does with the operator: multiplies by the stored matrix, or hands the panels to a delegate -- the action given to
     // rails_csr_create_callback (apply_fn with `delegate` as its user pointer), a sparse LU (rails_csr_create_lu, splu.hip: rails_lu_solve),
     // a sparse right-hand side (rails_csr_create_sprhs, sprhs.hip: rails_sprhs_apply) or an iterative solve (rails_csr_create_iter,
-    // itsolve.hip: rails_iter_solve).  The caller owns the delegate object.
-    enum Kind { STORED, CALLBACK, LU, SPRHS, ITER } kind = STORED;
+    // itsolve.hip: rails_iter_solve).  The caller owns the delegate object -- except a block-CSR matrix (rails_csr_create_bsr, spmm_bsr.hip:
+    // rails_bsr_apply), which the handle owns and which keeps rowptr / col / val and their host copies empty.
+    enum Kind { STORED, CALLBACK, LU, SPRHS, ITER, BSR } kind = STORED;
     void *delegate = nullptr;
     rails_apply_fn apply_fn = nullptr;
     rails_lu *lu() const { return kind == LU ? static_cast<rails_lu *>(delegate) : nullptr; }
     rails_sprhs *sprhs() const { return kind == SPRHS ? static_cast<rails_sprhs *>(delegate) : nullptr; }
     rails_iter *iter() const { return kind == ITER ? static_cast<rails_iter *>(delegate) : nullptr; }
+    rails_bsr *bsr() const { return kind == BSR ? static_cast<rails_bsr *>(delegate) : nullptr; }
 };
 
 // Sparse right-hand side B (m x p) and its transpose, both as rectangular CSR operators on the device (sprhs.hip), and the host-made plan
@@ -295,6 +298,9 @@ bool planes_last_interior(const rails_csr *A);
 int rails_spmm_tiled(rails_ctx *c, rails_csr *A, const double *X, int ldx, const double *Xg, int ldg, double *Y, int ldy, int nc, bool vec2,
                      int x_room, bool *done);
 void rails_tiled_release(rails_csr *A);
+// spmm_bsr.hip: the product of a block-CSR handle (windows checked, nc >= 1), and the release of its matrix with the handle
+int rails_bsr_apply(rails_ctx *c, rails_csr *A, int trans, const rails_panel *X, int xc0, int nc, rails_panel *Y, int yc0);
+void rails_bsr_release(rails_csr *A);
 // dense_gram.hip: partial Gram into device memory (no host copy / all-reduce): C_dev (a x b col-major, ldc = a)
 int rails_gram_dev(rails_ctx *ctx, const double *X, int ldx, const double *Y, int ldy, int64_t m, int a, int b,
                    double *C_dev);

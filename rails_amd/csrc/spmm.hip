@@ -562,6 +562,7 @@ extern "C" int rails_csr_destroy(rails_csr *A)
     rails_sweep_release(A);
     rails_planes_release(A);
     rails_tiled_release(A);
+    rails_bsr_release(A);
     if (A->rowptr) hipFree(A->rowptr);
     if (A->col) hipFree(A->col);
     if (A->val) hipFree(A->val);
@@ -616,7 +617,7 @@ extern "C" int rails_csr_set_halo(rails_csr *A, int64_t n_send, const int64_t *s
                                   void *user)
 {
     RAILS_REQUIRE(A, "null operator");
-    static const char *const single_gpu_only[] = {nullptr, nullptr, "an LU solve operator", "a sparse right-hand side", "an iterative solve operator"}; // by rails_csr::Kind
+    static const char *const single_gpu_only[] = {nullptr, nullptr, "an LU solve operator", "a sparse right-hand side", "an iterative solve operator", "a block-CSR operator"}; // by rails_csr::Kind
     RAILS_REQUIRE(!single_gpu_only[A->kind], "rails_csr_set_halo: %s is single GPU only", single_gpu_only[A->kind]);
     RAILS_REQUIRE(n_send >= 0 && n_ghost >= 0 && A->m + n_ghost == A->ncols_ext,
                   "rails_csr_set_halo: m_local %lld + ghosts %lld != extended columns %lld", (long long)A->m, (long long)n_ghost,
@@ -738,6 +739,7 @@ int apply_delegate(rails_ctx *c, rails_csr *A, int trans, const rails_panel *X, 
     case rails_csr::SPRHS: return rails_sprhs_apply(c, A->sprhs(), trans, X, xc0, nc, Y, yc0);
     case rails_csr::LU: return rails_lu_solve(c, A->lu(), trans, X, xc0, nc, Y, yc0);
     case rails_csr::ITER: return rails_iter_solve(c, A->iter(), trans, X, xc0, nc, Y, yc0);
+    case rails_csr::BSR: return rails_bsr_apply(c, A, trans, X, xc0, nc, Y, yc0);
     default: break;
     }
     int rc = A->apply_fn(A->delegate, trans ? 1 : 0, X, xc0, nc, Y, yc0);

@@ -3,7 +3,7 @@
     python -m rails_amd.main [params.xml] [--dir DIR] [--A A.mtx] [--B B.mtx] [--M M.mtx] [--V V.mtx] [--T T.mtx]
                                [--eigs K] [--variance FILE] [--pairs FILE [--pairs-out FILE]]
                                [--maps R1,R2,... [--correlation] [--maps-out FILE.mtx]] [--sparse-B] [--warm-start V.mtx | --start-space S.mtx] [--restart-upon-start]
-                               [--inverse {lu,cg,bicgstab,iterative}] [--inverse-tol T] [--inverse-poly K] [--inverse-amg]
+                               [--inverse {lu,cg,bicgstab,iterative}] [--inverse-tol T] [--inverse-poly K] [--inverse-amg] [--block-size b]
     python -m torch.distributed.run --nproc-per-node N -m rails_amd.main ... [--backend {nccl,gloo}] [--one-device]
                                                                                   (one rank per GPU, rows partitioned)
 
@@ -30,6 +30,12 @@ Schur-complement problem keeps the inverse of its Schur operator.  On more than 
 does not partition by rows): name one of the iterative inverses there.  Each rank then builds its inverse from its own row block, the
 inner products of the iteration are all-reduced, and `iterative` decides symmetry on the whole matrix, which every rank has read.  No run
 on more than one GPU has been made yet; what an inner iteration costs on a real partition is unmeasured.
+
+`--block-size b` (2 .. 8) keeps A, and M when given, as block-CSR operators of dense b x b blocks (rails_amd.HipOperatorWrapper.from_bsr;
+the matrix of a PDE system with b unknowns per cell): the files are read as before and converted on the host, zeros filling the touched
+blocks, and the driver prints the blocks, the fill ratio (stored entries over the file's) and the bytes on the device.  The number of rows
+must be a multiple of b, and the run has one rank (a block-CSR operator is single GPU).  The inverse of a "Projection method" above 1 is
+still built from the CSR arrays.
 
 `--backend gloo` runs the collectives through torch.distributed's gloo backend, staged through host memory, and `--one-device` puts every
 rank on device 0: a rehearsal of the multi-process path on a machine with one GPU, as bench.py has it.
@@ -157,12 +163,18 @@ def main(argv=None):
                                                                             "(K products per application; 0: off)")
     ap.add_argument("--inverse-amg", action="store_true", help="precondition a conjugate-gradients inverse with a smoothed-aggregation multigrid V-cycle "
                                                              "(one rank; not together with --inverse-poly)")
+    ap.add_argument("--block-size", type=int, default=0, metavar="b", help="keep A (and M) as block-CSR operators of b x b blocks, 2 .. 8; the rows must be a multiple of b; "
+                                                                          "one rank")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend of a run on several ranks; gloo = rehearsal of the "
                                                                                 "multi-process path (collectives staged through host memory)")
     ap.add_argument("--one-device", action="store_true", help="every rank uses device 0 (rehearsal on a machine with one GPU)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args(argv)
+    if args.block_size and not 2 <= args.block_size <= 8:
+        raise SystemExit("--block-size %d: blocks of 2 .. 8" % args.block_size)
+    if args.block_size and int(os.environ.get("WORLD_SIZE", "1")) > 1:  # refused before the ranks meet
+        raise SystemExit("--block-size on %s ranks: a block-CSR operator is single GPU" % os.environ["WORLD_SIZE"])
 
     import torch
 
@@ -239,8 +251,17 @@ def main(argv=None):
     r0, r1 = int(starts[rank]), int(starts[rank + 1])
     ctx.set_partition(rank, world, r0, m)
 
-    def operator(csr):
+    def operator(csr, name="A"):
         rp, cg, vv = csr
+        if args.block_size:
+            b, rows = args.block_size, len(rp) - 1
+            if rows % b:
+                raise SystemExit("--block-size %d: %s has %d rows, no multiple of %d" % (b, name, rows, b))
+            op = rails_amd.HipOperatorWrapper.from_bsr(ctx, *rails_amd.csr_to_bsr(rows, rows, b, rp, cg, vv))
+            st = op.bsr_stats()
+            _log(rank, "  %s as block-CSR: %d blocks of %d x %d, fill ratio %.3f (%d stored entries for %d), %d bytes on the device" % (
+                name, st["nnzb"], b, b, st["nnzb"] * b * b / max(1, len(vv)), st["nnzb"] * b * b, len(vv), st["device_bytes"]))
+            return op
         if world == 1:
             return rails_amd.HipOperatorWrapper(ctx, rp, cg.astype(np.int32), vv)
         p0, p1 = rp[r0], rp[r1]
@@ -288,7 +309,7 @@ def main(argv=None):
         raise SystemExit("--nullspace: N has %d rows, the equation solved has %d%s" % (Nsp.shape[0], m, " (the rows of the Schur complement)" if schur is not None else ""))
     _log(rank, "Creating solver")
     A = schur.op if schur is not None else operator((rowptr, col, val))
-    Mop = operator(Mcsr) if Mcsr else None
+    Mop = operator(Mcsr, "M") if Mcsr else None
     if world > 1:
         ctx.set_allreduce(partition.make_allreduce(on_device=True, host_staged=staged))
     solver = rails_amd.Solver(ctx, A, B if args.sparse_B else B[r0:r1], M=Mop, m_global=m)

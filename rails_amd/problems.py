@@ -65,6 +65,53 @@ def stencil27(nx, ny, nz, random_values=False, seed=0):
     return _csr_from_offsets(m, cols, vals)
 
 
+def block_stencil7(nx, ny, nz, b, seed=0):
+    """7-point grid stencil of dense random b x b blocks: the synthetic stand-in for the Jacobian of a PDE system with b unknowns per cell.
+    Entries U(-1, 1); the diagonal of every diagonal block is shifted to -(sum of the row's other |entries| + 1), so the matrix is strictly
+    diagonally dominant, hence stable.  Returns ((indptr, indices, data[nnzb, b, b]), (rowptr, col, val)): the block-CSR arrays as scipy's
+    bsr_matrix keeps them and the same matrix entry by entry as CSR, block columns ascending."""
+    mb = nx * ny * nz
+    idx = np.arange(mb, dtype=np.int64)
+    x = idx % nx
+    y = (idx // nx) % ny
+    z = idx // (nx * ny)
+    bcols = np.full((mb, 7), -1, dtype=np.int64)
+    # sorted by block column: z-1, y-1, x-1, centre, x+1, y+1, z+1
+    specs = [(z > 0, -nx * ny), (y > 0, -nx), (x > 0, -1), (None, 0), (x < nx - 1, 1), (y < ny - 1, nx), (z < nz - 1, nx * ny)]
+    for s, (cond, off) in enumerate(specs):
+        if cond is None:
+            bcols[:, s] = idx
+        else:
+            bcols[cond, s] = idx[cond] + off
+    mask = bcols >= 0
+    indptr = np.zeros(mb + 1, dtype=np.int64)
+    np.cumsum(mask.sum(1), out=indptr[1:])
+    indices = bcols[mask].astype(np.int32)
+    g = np.random.default_rng(seed)
+    data = g.uniform(-1.0, 1.0, (indices.size, b, b))
+    brow = np.repeat(idx, mask.sum(1))
+    centre = np.flatnonzero(indices == brow)
+    d = np.arange(b)
+    data[centre[:, None], d, d] = 0.0
+    rowsum = np.zeros((mb, b))
+    np.add.at(rowsum, brow, np.abs(data).sum(2))
+    data[centre[:, None], d, d] = -(rowsum + 1.0)
+    # entry by entry: scalar row i * b + r holds row r of each block of block row i
+    counts = np.diff(indptr)
+    rowptr = np.zeros(mb * b + 1, dtype=np.int64)
+    np.cumsum(np.repeat(counts, b) * b, out=rowptr[1:])
+    col = np.empty(indices.size * b * b, dtype=np.int32)
+    val = np.empty(indices.size * b * b)
+    # (block q of block row i is the q - indptr[i]'th of that row: its row r goes to rowptr[i * b + r] + (q - indptr[i]) * b)
+    within = np.arange(indices.size) - indptr[brow]
+    for r in range(b):
+        at = rowptr[brow * b + r] + within * b
+        for s in range(b):
+            col[at + s] = indices * b + s
+            val[at + s] = data[:, r, s]
+    return (indptr, indices, data), (rowptr, col, val)
+
+
 def banded_random(m, nnz_row=27, bandwidth=4096, seed=0):
     """nnz_row entries per row incl. the diagonal; off-diagonal columns uniform in |j - i| <= bandwidth
     (reflected at the boundary), values U(0,1); diagonal = -(row sum + 1).  Config C3 (primary)."""

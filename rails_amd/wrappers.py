@@ -414,6 +414,26 @@ class HipMultiVectorWrapper:
         return kept.value, idx[:kept.value].copy()
 
 
+def csr_to_bsr(m, n_cols, b, rowptr, col, val):
+    """The b x b blocking of an m x n_cols CSR matrix on the host (rails_bsr_count_host, rails_bsr_fill_host): (indptr, indices,
+    data[nnzb, b, b]) as scipy's bsr_matrix keeps them, zeros where a touched block has no entry.  No device is touched."""
+    lib = _lib.load()
+    rowptr = np.ascontiguousarray(rowptr, dtype=np.int64)
+    col = np.ascontiguousarray(col, dtype=np.int32)
+    val = np.ascontiguousarray(val, dtype=np.float64)
+    if rowptr.size != m + 1 or col.size != val.size or (rowptr.size and col.size < rowptr[-1]):
+        raise ValueError("csr_to_bsr: %d row pointers for %d rows, %d columns and %d values" % (rowptr.size, m, col.size, val.size))
+    i64, i32 = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+    nnzb = C.c_int64(0)
+    check(lib.rails_bsr_count_host(m, n_cols, b, rowptr.ctypes.data_as(i64), col.ctypes.data_as(i32), C.byref(nnzb)), "rails_bsr_count_host")
+    indptr = np.zeros(m // b + 1, dtype=np.int64)
+    indices = np.zeros(nnzb.value, dtype=np.int32)
+    data = np.zeros((nnzb.value, b, b))
+    check(lib.rails_bsr_fill_host(m, n_cols, b, rowptr.ctypes.data_as(i64), col.ctypes.data_as(i32), _p(val), indptr.ctypes.data_as(i64), indices.ctypes.data_as(i32),
+                                  _p(data)), "rails_bsr_fill_host")
+    return indptr, indices, data
+
+
 class HipOperatorWrapper:
     """Device CSR operator: the Matrix role (`A * X`, `A.transpose() * X`)."""
 
@@ -466,6 +486,49 @@ class HipOperatorWrapper:
         op._apply_cb = cb  # keep the trampoline alive as long as the operator
         op.h._keep = cb
         return op
+
+    @classmethod
+    def from_bsr(cls, ctx, indptr, indices, data):
+        """A block-CSR operator (include/rails_hip.h: rails_csr_create_bsr) from the arrays of a scipy.sparse.bsr_matrix: indptr
+        (mb + 1), indices (block columns), data (nnzb, b, b) with 2 <= b <= 8.  Square, single GPU."""
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(indices, dtype=np.int32)
+        data = np.ascontiguousarray(data, dtype=np.float64)
+        if data.ndim != 3 or data.shape[1] != data.shape[2] or data.shape[0] != indices.size:
+            raise ValueError("from_bsr: data must have shape (nnzb, b, b) with one block per index, got %s for %d indices" % (data.shape, indices.size))
+        mb = indptr.size - 1
+        h = C.c_void_p()
+        check(ctx.lib.rails_csr_create_bsr(ctx.h, mb, mb, int(data.shape[1]), indptr.ctypes.data_as(C.POINTER(C.c_int64)), indices.ctypes.data_as(C.POINTER(C.c_int32)),
+                                           _p(data), C.byref(h)), "rails_csr_create_bsr")
+        return cls(ctx, None, None, None, _handle=_Handle(ctx, h))
+
+    @classmethod
+    def from_scipy(cls, ctx, A, block_size=None):
+        """An operator from a scipy.sparse matrix.  A bsr_matrix with square blocks goes in as it is (block_size, when given, must be its
+        own); anything else becomes a CSR operator, or with block_size=b a block-CSR operator through the host conversion
+        (rails_bsr_fill_host: zero fill inside the touched blocks)."""
+        if getattr(A, "format", None) == "bsr":
+            if A.blocksize[0] != A.blocksize[1] or A.shape[0] != A.shape[1]:
+                raise ValueError("from_scipy: a block-CSR operator is square with square blocks, got %s with blocks %s" % (A.shape, A.blocksize))
+            if block_size is not None and int(block_size) != A.blocksize[0]:
+                raise ValueError("from_scipy: block_size %d given for a bsr_matrix with blocks of %d" % (block_size, A.blocksize[0]))
+            return cls.from_bsr(ctx, A.indptr, A.indices, A.data)
+        A = A.tocsr()
+        if block_size is None:
+            return cls(ctx, A.indptr, A.indices, A.data, ncols_ext=A.shape[1])
+        return cls.from_bsr(ctx, *csr_to_bsr(A.shape[0], A.shape[1], int(block_size), A.indptr, A.indices, A.data))
+
+    @property
+    def block_size(self):
+        """b of a block-CSR operator, 1 for every other kind"""
+        return self.ctx.lib.rails_csr_block_size(self.h.h)
+
+    def bsr_stats(self):
+        """A block-CSR operator's sizes and the template parameters of its last launch (rails_csr_bsr_stats)."""
+        out = (C.c_int64 * 10)()
+        check(self.ctx.lib.rails_csr_bsr_stats(self.h.h, out, 10), "rails_csr_bsr_stats")
+        return {"nnzb": out[0], "b": out[1], "max_block_row": out[2], "device_bytes": out[3], "B": out[4], "LPR": out[5], "threads": out[6], "rpg": out[7],
+                "all_staged": bool(out[8]), "grid": out[9]}
 
     def M(self):
         return self.ctx.lib.rails_csr_rows(self.h.h)
