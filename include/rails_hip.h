@@ -244,7 +244,7 @@ int rails_csr_create_lu(rails_ctx *ctx, rails_lu *lu, rails_csr **out);
  * finite on any rank gives RAILS_EINVAL on every rank.  On a context that does not reduce nothing of this runs.
  * Settings (rails_iter_set): "tolerance" 1e-10, "max_iterations" 1000, "jacobi" 1, "check_every" 8, "strict" 0, and those of the polynomial
  * preconditioner below: "poly_degree" 0, "poly_ratio" 10, "eig_max" 0, "poly_fused" 1; those of the multigrid preconditioner: "amg" 0,
- * "amg_degree" 1, "amg_ratio" 4, "amg_theta" 0.08, "amg_coarse" 256.
+ * "amg_degree" 1, "amg_ratio" 4, "amg_theta" 0.08, "amg_coarse" 256; block Jacobi: "block_jacobi" 0.
  * Chebyshev polynomial preconditioner (CG only; rails_amd/csrc/cheb_coef.h): with "poly_degree" K in 1 .. 64 the
  * solve preconditions with z = p_K(G A) G r, K products with A in a row without an inner product, a scalar kernel or a read-back between
  * them; G is the Jacobi diagonal's inverse when Jacobi is in effect and otherwise +-I, the sign of the operator's diagonal.  The
@@ -269,6 +269,19 @@ int rails_csr_create_lu(rails_ctx *ctx, rails_lu *lu, rails_csr **out);
  * operator (a sparse right-hand side or a rectangular handle is refused by rails_iter_create already); a context that reduces; 2^24 rows or more; and from the set-up a matrix with unsorted
  * or repeated columns in a row, a zero, missing or non-finite diagonal entry, one that is not definite, or one that does not coarsen
  * below 1025 rows (there is no huge dense block).
+ * Block-Jacobi preconditioner (both methods, single GPU; rails_amd/csrc/block_jacobi_host.h): for an operator with b
+ * unknowns per cell, G is the inverse of the b x b diagonal blocks instead of the inverse of the diagonal, 2 <= b <= 8 and b divides m.
+ * rails_iter_block_jacobi installs the blocks -- given on the host, or taken from a block-CSR handle's host copy or from the CSR arrays
+ * a stored handle keeps on the host -- inverts them on the host in long double (Gauss-Jordan with partial pivoting, rounded once) and
+ * sets "block_jacobi" to 1; rails_iter_set(it, "block_jacobi", 0 | 1) toggles it.  With "block_jacobi" 1 the preconditioner in effect
+ * is block Jacobi; otherwise "jacobi" decides, as before.  The passes that apply G walk block rows, z_i = sum_j G[i][j] r_j with one
+ * fused multiply-add per j, j ascending; a transposed BiCGStab solve applies the transposed inverse blocks.  "block_jacobi" 0, the
+ * default, is the solve without any of this: the same kernels, bits and launch counts.  RAILS_EINVAL, before any device work: b outside
+ * 2 .. 8 or not dividing m; a block with a zero or non-finite pivot or a non-finite inverse (the message names the block); no blocks
+ * given on a callback, LU or iterative-solve operator, or on a stored handle without host arrays; b different from a block-CSR
+ * handle's block size; a context that reduces; "block_jacobi" 1 without blocks; and "block_jacobi" 1 together with a "poly_degree"
+ * above 0 or "amg" 1, in whichever order they are set (one preconditioner at a time).  Not available: block Jacobi as the G of the
+ * Chebyshev polynomial, and on a row partition.
  * Outcomes: a zero right-hand-side column gives x = 0 after 0 iterations; a column that stops at max_iterations or breaks down (a
  * vanishing denominator; CG: p'Ap of the wrong sign, the operator is not definite) keeps its last iterate and is flagged, and the call
  * still returns RAILS_OK unless "strict" is set (RAILS_ENOCONV); a right-hand side that is not finite gives RAILS_EINVAL. */
@@ -295,6 +308,16 @@ int rails_iter_amg_setup(rails_ctx *ctx, rails_iter *it);
  * and upload time in microseconds and, in hi[n + 1], the operator complexity.  Any pointer may be NULL.  Returns n (0: no hierarchy has
  * been built) or a negative code; at most cap entries are written.  rails_iter_stats keeps its 19 entries. */
 int rails_iter_amg_info(const rails_iter *it, int64_t *rows, int64_t *nnz, double *hi, int cap);
+/* Installs the block-Jacobi preconditioner and sets "block_jacobi" to 1.  blocks_host != NULL: the m / b diagonal blocks themselves, each
+ * row-major b x b (the library inverts them, as it does diag_host), on any square operator.  blocks_host == NULL on a block-CSR handle: the
+ * blocks of its host copy, b 0 or the handle's block size, a diagonal block stored more than once in a block row summed in stored order;
+ * on a stored CSR handle with host arrays: the entries of row i whose column lies in i's block range, absent entries 0, duplicates added
+ * in stored order.  blocks_host == NULL and b == 0 on anything but a block-CSR handle clears the blocks and turns the setting off.
+ * Synchronises. */
+int rails_iter_block_jacobi(rails_ctx *ctx, rails_iter *it, int b, const double *blocks_host);
+/* Returns the number of blocks installed (0: none) and their size in *b (may be NULL); copies the first cap_blocks inverse blocks,
+ * row-major, exactly as they were uploaded (inv_blocks_host may be NULL). */
+int64_t rails_iter_block_jacobi_info(const rails_iter *it, int *b, double *inv_blocks_host, int64_t cap_blocks);
 /* Last solve: info[0] most iterations of a column, [1] inner products, [2] launches of the library's own passes, [3] columns that did not
  * converge, [4] of those, broken down, [5] worst relative residual of the recurrence, [6] work-panel columns, [7] products with A;
  * totals since creation: [8] solves, [9] columns, [10] iterations summed over columns, [11] flagged columns, [12] products; the polynomial

@@ -1,7 +1,7 @@
 // iter_kernels.inc -- the device code of the iterative A^-1 operator, included by itsolve.hip inside its anonymous namespace (one translation
 // unit, as with lanczos_pass.inc and dense_gram.inc): the shape every pass shares, the passes of CG and BiCGStab, the Chebyshev sweep
-// (init, unfused pass, the fused step on the shared row gather of csr_row_gather.inc), the multigrid cycle's own kernels and the scalar
-// step.  PassGeom is iter_geom.h's rails_pass_geom; itsolve.hip's head comment says what the passes are.
+// (init, unfused pass, the fused step on the shared row gather of csr_row_gather.inc), the multigrid cycle's own kernels, the scalar
+// step and, at the end, the block forms of the passes that apply the preconditioner when it is block Jacobi.  PassGeom is iter_geom.h's rails_pass_geom; itsolve.hip's head comment says what the passes are.
 typedef double it_v2 __attribute__((ext_vector_type(2)));
 
 enum { STEP_CG_INIT = 0, STEP_CG_ALPHA, STEP_CG_BETA, STEP_BI_INIT, STEP_BI_ALPHA, STEP_BI_OMEGA, STEP_BI_END };
@@ -25,10 +25,12 @@ __device__ __forceinline__ it_v2 axpy_sel(it_v2 a, it_v2 x, it_v2 y)
 
 // The shape every pass shares.  body(row, offset of the pair in a work panel, has1, acc) streams one row of one column pair and adds to
 // acc[0 .. NQ); the partial sums of block b land in partial[(b * NQ + q) * ncw + column].
+template <int NQ>
+__device__ __forceinline__ void iter_pass_sums(const PassGeom &g, double *__restrict__ partial, const it_v2 *acc);
+
 template <int NQ, class Body>
 __device__ __forceinline__ void iter_pass(const PassGeom &g, double *__restrict__ partial, Body body)
 {
-    __shared__ double sh[NQ > 0 ? NQ : 1][256][2];
     const int TX = 1 << g.tx_bits, TY = 256 >> g.tx_bits;
     const int tx = threadIdx.x & (TX - 1), ty = threadIdx.x >> g.tx_bits;
     const int c = 2 * tx;
@@ -43,6 +45,19 @@ __device__ __forceinline__ void iter_pass(const PassGeom &g, double *__restrict_
         for (int64_t r = r_begin + ty; r < r_end; r += TY) body(r, r * g.ld + c, has1, acc);
     }
     if (NQ == 0) return;
+    iter_pass_sums<NQ>(g, partial, acc);
+}
+
+// The end of a pass that sums: the TY row classes' NQ sums per column meet in an LDS tree of fixed shape, and row class 0 writes the
+// block's partial sums.  Shared by the point form above and the block form (iter_pass_block).
+template <int NQ>
+__device__ __forceinline__ void iter_pass_sums(const PassGeom &g, double *__restrict__ partial, const it_v2 *acc)
+{
+    __shared__ double sh[NQ > 0 ? NQ : 1][256][2];
+    const int TX = 1 << g.tx_bits, TY = 256 >> g.tx_bits;
+    const int tx = threadIdx.x & (TX - 1), ty = threadIdx.x >> g.tx_bits;
+    const int c = 2 * tx;
+    const bool has0 = c < g.ncw, has1 = c + 1 < g.ncw;
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
         sh[q][threadIdx.x][0] = acc[q].x;
@@ -411,4 +426,131 @@ __global__ __launch_bounds__(64) void k_iter_compute(int step, const double *__r
                                                      double tol2, int maxit, double sign)
 {
     iter_columns(step, sums, ncw, nq, cols, status, tol2, maxit, sign);
+}
+
+// ---- block Jacobi (DESIGN.md section 18): z = G r with G the inverses of the b x b diagonal blocks, ginv[block][i][j] row-major, in the
+// passes that apply dinv[row] in the point form.  RAILS_BJ_TABLE is the list of block sizes compiled; the launching switches of itsolve.hip
+// expand from it. ----
+#define RAILS_BJ_TABLE(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
+
+struct bj_row {
+    it_v2 r, aux; // the row's entry of the vector G applies to, and what else the pass formed from its loads (k_cg_update_bj: x)
+};
+
+// The block form of iter_pass.  A thread owns a column pair and every TY-th BLOCK row of its block's slab (g.rows_per_slab is a multiple
+// of B, rails_iter_pass_geom_block).  For one block row it calls load(offset) for the B rows -- every load of the pass is in there, and it
+// stores nothing -- then forms z_i = sum_j G[i][j] r_j (TRANS: G[j][i]), one accumulator from +0 and one fma per j, j ascending, and
+// calls emit(offset, has1, row i's loads, z_i, acc) for the stores and the sums.  The trip count of the row loop is the same for every
+// thread of the block and the loads are unconditional (lanczos_pass.inc's rule): a thread past the slab's last block row loads that last
+// block row again and emits nothing.  All lanes of a row class read the inverse block at one address.
+template <int B, int NQ, bool TRANS, class Load, class Emit>
+__device__ __forceinline__ void iter_pass_block(const PassGeom &g, const double *__restrict__ ginv, double *__restrict__ partial, Load load, Emit emit)
+{
+    const int TX = 1 << g.tx_bits, TY = 256 >> g.tx_bits;
+    const int tx = threadIdx.x & (TX - 1), ty = threadIdx.x >> g.tx_bits;
+    const int c = 2 * tx;
+    const bool has0 = c < g.ncw, has1 = c + 1 < g.ncw;
+    const int64_t nb = g.m / B, bps = g.rows_per_slab / B;
+    const int64_t b_begin = (int64_t)blockIdx.x * bps;
+    const int64_t b_end = b_begin + bps < nb ? b_begin + bps : nb;
+    it_v2 acc[NQ > 0 ? NQ : 1];
+#pragma unroll
+    for (int q = 0; q < (NQ > 0 ? NQ : 1); ++q) acc[q] = (it_v2){0.0, 0.0};
+    if (has0) {
+        for (int64_t base = b_begin; base < b_end; base += TY) {
+            const bool live = base + ty < b_end;
+            const int64_t br = live ? base + ty : b_end - 1;
+            const int64_t o = br * B * g.ld + c;
+            const double *__restrict__ gb = ginv + br * (B * B);
+            bj_row in[B];
+#pragma unroll
+            for (int i = 0; i < B; ++i) in[i] = load(o + (int64_t)i * g.ld);
+#pragma unroll
+            for (int i = 0; i < B; ++i) {
+                it_v2 z = (it_v2){0.0, 0.0};
+#pragma unroll
+                for (int j = 0; j < B; ++j) {
+                    const double v = TRANS ? gb[j * B + i] : gb[i * B + j];
+                    z.x = __builtin_fma(v, in[j].r.x, z.x);
+                    z.y = __builtin_fma(v, in[j].r.y, z.y);
+                }
+                if (live) emit(o + (int64_t)i * g.ld, has1, in[i], z, acc);
+            }
+        }
+    }
+    if (NQ == 0) return;
+    iter_pass_sums<NQ>(g, partial, acc);
+}
+
+// k_cg_init<true> with blocks: z = G r, p = z, x = 0; partial sums of r.z and r.r
+template <int B>
+__global__ __launch_bounds__(256) void k_cg_init_bj(PassGeom g, const double *__restrict__ ginv, const double *__restrict__ R, double *__restrict__ Z,
+                                                    double *__restrict__ P, double *__restrict__ Xw, double *__restrict__ partial)
+{
+    iter_pass_block<B, 2, false>(
+        g, ginv, partial, [&](int64_t o) { return bj_row{ld2(R + o), (it_v2){0.0, 0.0}}; },
+        [&](int64_t o, bool has1, const bj_row &in, it_v2 z, it_v2 *acc) {
+            st2(Z + o, z, has1);
+            st2(P + o, z, has1);
+            st2(Xw + o, (it_v2){0.0, 0.0}, has1);
+            acc[0] += in.r * z;
+            acc[1] += in.r * in.r;
+        });
+}
+
+// k_cg_update<true> with blocks: x += alpha p, r -= alpha q, z = G r; partial sums of r.z and r.r
+template <int B>
+__global__ __launch_bounds__(256) void k_cg_update_bj(PassGeom g, const rails_iter_col *__restrict__ cols, const double *__restrict__ ginv,
+                                                      const double *__restrict__ P, const double *__restrict__ Q, double *__restrict__ Xw,
+                                                      double *__restrict__ R, double *__restrict__ Z, double *__restrict__ partial)
+{
+    ITER_COEF(alpha, alpha);
+    iter_pass_block<B, 2, false>(
+        g, ginv, partial, [&](int64_t o) { return bj_row{axpy_sel(-alpha, ld2(Q + o), ld2(R + o)), axpy_sel(alpha, ld2(P + o), ld2(Xw + o))}; },
+        [&](int64_t o, bool has1, const bj_row &in, it_v2 z, it_v2 *acc) {
+            st2(Xw + o, in.aux, has1);
+            st2(R + o, in.r, has1);
+            st2(Z + o, z, has1);
+            acc[0] += in.r * z;
+            acc[1] += in.r * in.r;
+        });
+}
+
+// k_bi_dir<true> with blocks: p = r + beta (p - omega v), p^ = G p (TRANS: G')
+template <int B, bool TRANS>
+__global__ __launch_bounds__(256) void k_bi_dir_bj(PassGeom g, const rails_iter_col *__restrict__ cols, const double *__restrict__ ginv,
+                                                   const double *__restrict__ R, const double *__restrict__ V, double *__restrict__ P,
+                                                   double *__restrict__ PH)
+{
+    ITER_COEF(beta, beta);
+    ITER_COEF(omega, omega);
+    iter_pass_block<B, 0, TRANS>(
+        g, ginv, nullptr, [&](int64_t o) { return bj_row{axpy_sel(beta, axpy_sel(-omega, ld2(V + o), ld2(P + o)), ld2(R + o)), (it_v2){0.0, 0.0}}; },
+        [&](int64_t o, bool has1, const bj_row &in, it_v2 z, it_v2 *) {
+            st2(P + o, in.r, has1);
+            st2(PH + o, z, has1);
+        });
+}
+
+// k_bi_s<true> with blocks: s = r - alpha v (kept in R), s^ = G s (TRANS: G')
+template <int B, bool TRANS>
+__global__ __launch_bounds__(256) void k_bi_s_bj(PassGeom g, const rails_iter_col *__restrict__ cols, const double *__restrict__ ginv,
+                                                 const double *__restrict__ V, double *__restrict__ R, double *__restrict__ SH)
+{
+    ITER_COEF(alpha, alpha);
+    iter_pass_block<B, 0, TRANS>(
+        g, ginv, nullptr, [&](int64_t o) { return bj_row{axpy_sel(-alpha, ld2(V + o), ld2(R + o)), (it_v2){0.0, 0.0}}; },
+        [&](int64_t o, bool has1, const bj_row &in, it_v2 z, it_v2 *) {
+            st2(R + o, in.r, has1);
+            st2(SH + o, z, has1);
+        });
+}
+
+// Z = G R: the preconditioner on its own (rails_iter_precondition with block Jacobi in effect)
+template <int B>
+__global__ __launch_bounds__(256) void k_bj_apply(PassGeom g, const double *__restrict__ ginv, const double *__restrict__ R, double *__restrict__ Z)
+{
+    iter_pass_block<B, 0, false>(
+        g, ginv, nullptr, [&](int64_t o) { return bj_row{ld2(R + o), (it_v2){0.0, 0.0}}; },
+        [&](int64_t o, bool has1, const bj_row &, it_v2 z, it_v2 *) { st2(Z + o, z, has1); });
 }

@@ -5,7 +5,11 @@
 // Chebyshev polynomial in the Jacobi-scaled operator ("poly_degree", cheb_coef.h), whose steps -- a product and its
 // recurrence update -- are one kernel each for a stored CSR operator (k_cheb_step_csr); or, instead, with one V-cycle of smoothed-
 // aggregation multigrid ("amg", amg_host.h for the set-up on the host, Run::vcycle below) that smooths with the
-// same kernels and adds three of its own (k_amg_residual_csr, k_amg_prolong_add, k_amg_coarse_dense).  This file is the host code; the
+// same kernels and adds three of its own (k_amg_residual_csr, k_amg_prolong_add, k_amg_coarse_dense); or, for both methods, with block
+// Jacobi ("block_jacobi", rails_iter_block_jacobi; block_jacobi_host.h for the blocks and their inverses on the host, DESIGN.md section
+// 18): the inverses of the b x b diagonal blocks in place of the diagonal's, in block forms of the passes that apply it (k_cg_init_bj,
+// k_cg_update_bj, k_bi_dir_bj, k_bi_s_bj, k_bj_apply on iter_pass_block), every pass of such a solve on slabs of whole block rows
+// (rails_iter_pass_geom_block).  This file is the host code; the
 // kernels are iter_kernels.inc, the geometry of a pass is iter_geom.h.  Both preconditioners are Chebyshev sweeps (struct Sweep,
 // Run::sweep_start, Run::sweep_step); what a call needs of them -- coefficients, the choice of the fused step, geometry -- is its plan,
 // made before anything is queued (begin_call, plan_call, plan_group), and every refusal is there.
@@ -36,6 +40,7 @@
 #include <vector>
 
 #include "amg_host.h"
+#include "block_jacobi_host.h"
 #include "cheb_coef.h"
 #include "iter_agree.h"
 #include "iter_geom.h"
@@ -110,6 +115,11 @@ struct rails_iter {
     double amg_ratio = 4.0, amg_theta = RAILS_AMG_THETA;
     Amg *hier = nullptr;
     long last_cycles = 0, last_cycle_products = 0, last_cycle_launches = 0; // of the last call: cycles, and the products and launches inside them
+    // block Jacobi ("block_jacobi"): the inverses of the m / bj_b diagonal blocks, row-major, on the device and as
+    // uploaded on the host (rails_iter_block_jacobi_info); the setting is on only while there are blocks
+    int block_jacobi = 0, bj_b = 0;
+    double *bj_dev = nullptr;
+    std::vector<double> bj_host;
     double tot_solves = 0, tot_iterations = 0, tot_flagged = 0, tot_products = 0, tot_columns = 0;
 };
 
@@ -180,6 +190,7 @@ int amg_check(const rails_iter *it, const char *who)
     const rails_csr *A = it->A;
     RAILS_REQUIRE(it->method == RAILS_ITER_CG, "%s: \"amg\" on a BiCGStab object: the multigrid preconditioner is for conjugate gradients (a symmetric definite operator)", who);
     RAILS_REQUIRE(it->poly_degree == 0, "%s: \"amg\" together with poly_degree %d: one preconditioner at a time", who, it->poly_degree);
+    RAILS_REQUIRE(!it->block_jacobi, "%s: \"amg\" together with \"block_jacobi\": one preconditioner at a time", who);
     RAILS_REQUIRE(A->kind != rails_csr::CALLBACK, "%s: \"amg\" needs the entries of the matrix: the operator is a callback", who);
     RAILS_REQUIRE(A->kind != rails_csr::LU && A->kind != rails_csr::ITER, "%s: \"amg\" needs the entries of the matrix: the operator is an LU or an iterative solve", who);
     RAILS_REQUIRE(A->kind != rails_csr::BSR, "%s: \"amg\" needs the entries of the matrix as scalar CSR arrays: the operator is block-CSR (keep a CSR handle for the preconditioner)", who);
@@ -191,7 +202,7 @@ int amg_check(const rails_iter *it, const char *who)
 
 bool uses_panel(const rails_iter *it, int which)
 {
-    const bool jac = it->dinv != nullptr;
+    const bool jac = it->dinv != nullptr || it->bj_dev != nullptr;
     if (which == W_D || which == W_Z2) return it->poly_degree > 0 || it->amg;
     if (which == W_Z && (it->poly_degree > 0 || it->amg)) return true;
     if (it->method == RAILS_ITER_CG) return which == W_X || which == W_R || which == W_P || which == W_Q || (which == W_Z && jac);
@@ -240,6 +251,34 @@ int grow_cols(rails_ctx *c, rails_iter *it, int nc)
     return RAILS_OK;
 }
 
+// The block forms of the passes that apply G, by block size: one switch per kernel, expanded from RAILS_BJ_TABLE (iter_kernels.inc).  A
+// block size outside the table gives a null pointer, which the call refuses before anything is queued (begin_call).
+#define RAILS_BJ_PICK(fn, expr)                                                                                                                   \
+    auto fn(int b, bool trans)->decltype(expr(2))                                                                                                   \
+    {                                                                                                                                             \
+        (void)trans;                                                                                                                              \
+        switch (b) {                                                                                                                              \
+            RAILS_BJ_TABLE(expr##_CASE)                                                                                                           \
+        default: return nullptr;                                                                                                                  \
+        }                                                                                                                                         \
+    }
+#define BJ_CG_INIT(B) (&k_cg_init_bj<B>)
+#define BJ_CG_INIT_CASE(B) case B: return BJ_CG_INIT(B);
+#define BJ_CG_UPDATE(B) (&k_cg_update_bj<B>)
+#define BJ_CG_UPDATE_CASE(B) case B: return BJ_CG_UPDATE(B);
+#define BJ_APPLY(B) (&k_bj_apply<B>)
+#define BJ_APPLY_CASE(B) case B: return BJ_APPLY(B);
+#define BJ_BI_DIR(B) (trans ? &k_bi_dir_bj<B, true> : &k_bi_dir_bj<B, false>)
+#define BJ_BI_DIR_CASE(B) case B: return BJ_BI_DIR(B);
+#define BJ_BI_S(B) (trans ? &k_bi_s_bj<B, true> : &k_bi_s_bj<B, false>)
+#define BJ_BI_S_CASE(B) case B: return BJ_BI_S(B);
+RAILS_BJ_PICK(bj_cg_init, BJ_CG_INIT)
+RAILS_BJ_PICK(bj_cg_update, BJ_CG_UPDATE)
+RAILS_BJ_PICK(bj_apply, BJ_APPLY)
+RAILS_BJ_PICK(bj_bi_dir, BJ_BI_DIR)
+RAILS_BJ_PICK(bj_bi_s, BJ_BI_S)
+#undef RAILS_BJ_PICK
+
 // A Chebyshev sweep on an operator: z = p(G A) G r by d = z = G r / theta, then steps d = a d + b G (r - A z), z += d.  The polynomial
 // preconditioner is one sweep on the object's operator in the object's panels; the multigrid cycle smooths with one per level.  What does
 // not depend on the group is filled in by plan_call, the geometry by plan_group.
@@ -263,7 +302,8 @@ struct Run {
     PassGeom g;
     int64_t nslab;
     rails_iter_col *cols;
-    bool jac;
+    bool jac; // a preconditioner applied inside the passes: the Jacobi diagonal, or (bj) the diagonal blocks
+    int bj = 0; // block Jacobi in effect: the block size (the passes that apply G take their block form, on the block geometry)
     double tol2;
     // the preconditioner beyond Jacobi: the polynomial's degree (0: off) or the multigrid cycle (K is 0 then); sw[0] is the polynomial's
     // sweep, or sw[l] the smoother of level l; the last level's passes run on gc
@@ -419,6 +459,11 @@ struct Run {
     }
     int precondition()
     {
+        if (bj) { // (neither the polynomial nor the cycle is on: rails_iter_set)
+            it->last_poly++;
+            pass(g, nslab, bj_apply(bj, false), (const double *)it->bj_dev, (const double *)d(W_R), d(W_Z));
+            return RAILS_OK;
+        }
         cycle = amg; // (off again however the cycle ends)
         const int rc = amg ? vcycle() : polynomial();
         cycle = false;
@@ -434,7 +479,9 @@ struct Run {
         if (other) {
             RAILS_TRY(precondition());
             RAILS_TRY(pass_sums(k_cg_init_poly, d(W_R), d(W_Z), d(W_P), d(W_X)));
-        } else
+        } else if (bj)
+            RAILS_TRY(pass_sums(bj_cg_init(bj, false), (const double *)it->bj_dev, (const double *)d(W_R), d(W_Z), d(W_P), d(W_X)));
+        else
             RAILS_TRY(pass_sums(jac ? k_cg_init<true> : k_cg_init<false>, it->dinv, d(W_R), jac ? d(W_Z) : nullptr, d(W_P), d(W_X)));
         it->last_dots += 2 * g.ncw;
         return scalars(STEP_CG_INIT, 2);
@@ -452,7 +499,11 @@ struct Run {
                 RAILS_TRY(precondition());
                 RAILS_TRY(dots(2, W_R, W_Z, W_R, W_R));
             } else {
-                RAILS_TRY(pass_sums(jac ? k_cg_update<true> : k_cg_update<false>, cols, it->dinv, d(W_P), d(W_Q), d(W_X), d(W_R), jac ? d(W_Z) : nullptr));
+                if (bj)
+                    RAILS_TRY(pass_sums(bj_cg_update(bj, false), (const rails_iter_col *)cols, (const double *)it->bj_dev, (const double *)d(W_P), (const double *)d(W_Q), d(W_X),
+                                        d(W_R), d(W_Z)));
+                else
+                    RAILS_TRY(pass_sums(jac ? k_cg_update<true> : k_cg_update<false>, cols, it->dinv, d(W_P), d(W_Q), d(W_X), d(W_R), jac ? d(W_Z) : nullptr));
                 it->last_dots += 2 * g.ncw;
             }
             RAILS_TRY(scalars(STEP_CG_BETA, 2));
@@ -460,11 +511,17 @@ struct Run {
             return RAILS_OK;
         }
         const int ph = jac ? W_Z : W_P, sh = jac ? W_SH : W_R;
-        pass(g, nslab, jac ? k_bi_dir<true> : k_bi_dir<false>, cols, it->dinv, d(W_R), d(W_Q), d(W_P), jac ? d(W_Z) : nullptr);
+        if (bj)
+            pass(g, nslab, bj_bi_dir(bj, trans != 0), (const rails_iter_col *)cols, (const double *)it->bj_dev, (const double *)d(W_R), (const double *)d(W_Q), d(W_P), d(W_Z));
+        else
+            pass(g, nslab, jac ? k_bi_dir<true> : k_bi_dir<false>, cols, it->dinv, d(W_R), d(W_Q), d(W_P), jac ? d(W_Z) : nullptr);
         RAILS_TRY(product(ph, W_Q)); // v = A p^
         RAILS_TRY(dots(1, W_RH, W_Q, W_RH, W_Q));
         RAILS_TRY(scalars(STEP_BI_ALPHA, 1));
-        pass(g, nslab, jac ? k_bi_s<true> : k_bi_s<false>, cols, it->dinv, d(W_Q), d(W_R), jac ? d(W_SH) : nullptr);
+        if (bj)
+            pass(g, nslab, bj_bi_s(bj, trans != 0), (const rails_iter_col *)cols, (const double *)it->bj_dev, (const double *)d(W_Q), d(W_R), d(W_SH));
+        else
+            pass(g, nslab, jac ? k_bi_s<true> : k_bi_s<false>, cols, it->dinv, d(W_Q), d(W_R), jac ? d(W_SH) : nullptr);
         RAILS_TRY(product(sh, W_T)); // t = A s^
         RAILS_TRY(dots(2, W_T, W_R, W_T, W_T));
         RAILS_TRY(scalars(STEP_BI_OMEGA, 2));
@@ -537,6 +594,7 @@ void plan_group(Run &run, int w)
     for (int l = 0; l < std::max(1, nl); ++l) run.sw[l].g = rails_iter_pass_geom(run.sw[l].n, w, ld, &run.sw[l].slabs);
     run.g = run.sw[0].g; // (level 0 has the operator's rows)
     run.nslab = run.sw[0].slabs;
+    if (run.bj) run.g = rails_iter_pass_geom_block(it->m, w, ld, run.bj, &run.nslab); // every pass of the group, the point ones too
     if (run.amg) run.gc = rails_iter_pass_geom(it->hier->n_coarse, w, ld, &run.slabs_c);
 }
 
@@ -552,6 +610,7 @@ extern "C" void rails_iter_destroy(rails_iter *it)
     amg_release(it);
     release_work(it);
     hipFree(it->dinv);
+    hipFree(it->bj_dev);
     hipFree(it->cols_dev);
     hipFree(it->status_dev);
     hipFree(it->sums_dev);
@@ -708,6 +767,7 @@ extern "C" int rails_iter_set(rails_iter *it, const char *name, double value)
         RAILS_REQUIRE(value >= 0.0 && value <= RAILS_CHEB_MAX_DEGREE && value == std::floor(value), "rails_iter_set: poly_degree %g is not a whole number in 0 .. %d", value,
                       RAILS_CHEB_MAX_DEGREE);
         RAILS_REQUIRE(value == 0.0 || !it->amg, "rails_iter_set: poly_degree %g together with \"amg\": one preconditioner at a time", value);
+        RAILS_REQUIRE(value == 0.0 || !it->block_jacobi, "rails_iter_set: poly_degree %g together with \"block_jacobi\": one preconditioner at a time", value);
         RAILS_REQUIRE(value == 0.0 || it->method == RAILS_ITER_CG,
                       "rails_iter_set: poly_degree %g on a BiCGStab object: the polynomial preconditioner is for conjugate gradients (a real spectrum)", value);
         it->poly_degree = (int)value;
@@ -719,7 +779,14 @@ extern "C" int rails_iter_set(rails_iter *it, const char *name, double value)
         it->eig_max = value;
     } else if (n == "poly_fused")
         it->poly_fused = value != 0.0;
-    else if (n == "amg") {
+    else if (n == "block_jacobi") {
+        if (value != 0.0) {
+            RAILS_REQUIRE(it->bj_dev, "rails_iter_set: \"block_jacobi\" 1 without blocks: install them first (rails_iter_block_jacobi)");
+            RAILS_REQUIRE(it->poly_degree == 0, "rails_iter_set: \"block_jacobi\" together with poly_degree %d: one preconditioner at a time", it->poly_degree);
+            RAILS_REQUIRE(!it->amg, "rails_iter_set: \"block_jacobi\" together with \"amg\": one preconditioner at a time");
+        }
+        it->block_jacobi = value != 0.0;
+    } else if (n == "amg") {
         if (value != 0.0) RAILS_TRY(amg_check(it, "rails_iter_set"));
         it->amg = value != 0.0;
     } else if (n == "amg_degree") {
@@ -739,10 +806,97 @@ extern "C" int rails_iter_set(rails_iter *it, const char *name, double value)
         it->amg_coarse = (int)value;
     } else {
         rails_set_error("rails_iter_set: no setting named '%s' (tolerance, max_iterations, jacobi, check_every, strict, poly_degree, poly_ratio, eig_max, poly_fused, amg, amg_degree, "
-                        "amg_ratio, amg_theta, amg_coarse)", name);
+                        "amg_ratio, amg_theta, amg_coarse, block_jacobi)", name);
         return RAILS_EINVAL;
     }
     return RAILS_OK;
+}
+
+// Installs (or clears) the block-Jacobi preconditioner: where the diagonal blocks come from and every refusal is rails_bj_plan
+// (block_jacobi_host.h), the extraction and the long-double inverses are host code there too; nothing touches the device before the
+// inverses stand.  Installing sets "block_jacobi" to 1.
+extern "C" int rails_iter_block_jacobi(rails_ctx *c, rails_iter *it, int b, const double *blocks_host)
+{
+    if (c) hipSetDevice(c->device);
+    RAILS_REQUIRE(c && it, "rails_iter_block_jacobi: null argument");
+    RAILS_REQUIRE(c == it->ctx, "rails_iter_block_jacobi: the object belongs to another context");
+    const rails_csr *A = it->A;
+    const int64_t m = it->m;
+    int hb = 0;
+    int64_t hmb = 0;
+    const int64_t *browptr = nullptr;
+    const int32_t *bcol = nullptr;
+    const double *bval = nullptr;
+    const bool host_csr = A->kind == rails_csr::STORED && (int64_t)A->h_rowptr.size() == m + 1 && (int64_t)A->h_val.size() == A->h_rowptr[m] && A->h_col.size() == A->h_val.size();
+    int op = RAILS_BJ_OP_CALLBACK;
+    switch (A->kind) {
+    case rails_csr::STORED: op = host_csr ? RAILS_BJ_OP_CSR : RAILS_BJ_OP_CSR_NO_HOST; break;
+    case rails_csr::BSR:
+        RAILS_REQUIRE(rails_bsr_host_arrays(A, &hb, &hmb, &browptr, &bcol, &bval), "rails_iter_block_jacobi: the block-CSR operator keeps no host copy");
+        op = RAILS_BJ_OP_BSR;
+        break;
+    case rails_csr::LU: op = RAILS_BJ_OP_LU; break;
+    case rails_csr::ITER: op = RAILS_BJ_OP_ITER; break;
+    default: op = RAILS_BJ_OP_CALLBACK; break;
+    }
+    const bool reduces = it->reduces || A->n_ghost > 0 || A->n_send > 0;
+    int source = RAILS_BJ_CLEAR, be = 0;
+    char err[256] = "";
+    if (rails_bj_plan(op, hb, reduces, m, b, blocks_host != nullptr, &source, &be, err, sizeof err)) {
+        rails_set_error("%s", err);
+        return RAILS_EINVAL;
+    }
+    if (source == RAILS_BJ_CLEAR) {
+        RAILS_HIP_CHECK(hipStreamSynchronize(c->stream));
+        hipFree(it->bj_dev);
+        it->bj_dev = nullptr;
+        it->bj_host.clear();
+        it->bj_b = it->block_jacobi = 0;
+        return RAILS_OK;
+    }
+    RAILS_REQUIRE(it->poly_degree == 0, "rails_iter_block_jacobi: together with poly_degree %d: one preconditioner at a time", it->poly_degree);
+    RAILS_REQUIRE(!it->amg, "rails_iter_block_jacobi: together with \"amg\": one preconditioner at a time");
+    const int64_t nb = m / be;
+    const size_t n = (size_t)nb * be * be;
+    std::vector<double> blocks, inv(n);
+    if (source != RAILS_BJ_FROM_ARGUMENT) {
+        blocks.resize(n);
+        if (source == RAILS_BJ_FROM_BSR)
+            rails_bj_from_bsr(nb, be, browptr, bcol, bval, blocks.data());
+        else
+            rails_bj_from_csr(nb, be, A->h_rowptr.data(), A->h_col.data(), A->h_val.data(), blocks.data());
+        blocks_host = blocks.data();
+    }
+    if (rails_bj_invert(nb, be, blocks_host, inv.data(), err, sizeof err)) {
+        rails_set_error("%s", err);
+        return RAILS_EINVAL;
+    }
+    double *dev = nullptr;
+    RAILS_HIP_CHECK(hipStreamSynchronize(c->stream)); // (a solve still queued reads the old blocks)
+    RAILS_HIP_CHECK(hipMalloc((void **)&dev, n * sizeof(double)));
+    const hipError_t e = hipMemcpy(dev, inv.data(), n * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        hipFree(dev);
+        RAILS_HIP_CHECK(e);
+    }
+    hipFree(it->bj_dev);
+    it->bj_dev = dev;
+    it->bj_host.swap(inv);
+    it->bj_b = be;
+    it->block_jacobi = 1;
+    c->n_dev_alloc++;
+    return RAILS_OK;
+}
+
+// the number of blocks (0: none installed) and their size; the first cap_blocks inverses exactly as uploaded
+extern "C" int64_t rails_iter_block_jacobi_info(const rails_iter *it, int *b, double *inv_blocks_host, int64_t cap_blocks)
+{
+    RAILS_REQUIRE(it, "rails_iter_block_jacobi_info: null argument");
+    const int64_t nb = it->bj_b ? it->m / it->bj_b : 0;
+    if (b) *b = it->bj_b;
+    if (inv_blocks_host && cap_blocks > 0 && nb > 0)
+        std::copy(it->bj_host.begin(), it->bj_host.begin() + (size_t)std::min(nb, cap_blocks) * it->bj_b * it->bj_b, inv_blocks_host);
+    return nb;
 }
 
 // Builds (or rebuilds) the multigrid hierarchy from the CSR arrays the operator's handle keeps on the host and uploads it: the level operators, P and R = P' as rectangular operators, the inverse diagonals, the dense inverse.
@@ -875,7 +1029,9 @@ int begin_call(rails_ctx *c, rails_iter *it, const char *who, bool solve, int tr
     run.c = c;
     run.it = it;
     run.trans = trans ? 1 : 0;
-    run.jac = it->jacobi && it->dinv;
+    run.bj = it->block_jacobi && it->bj_dev ? it->bj_b : 0;
+    RAILS_REQUIRE(!run.bj || bj_apply(run.bj, false), "%s: no block-Jacobi kernels for block size %d (RAILS_BJ_TABLE)", who, run.bj);
+    run.jac = run.bj || (it->jacobi && it->dinv);
     run.tol2 = solve ? it->tol * it->tol : 0.0;
     run.cols = nullptr;
     return plan_call(run, who);

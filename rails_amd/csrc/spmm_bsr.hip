@@ -279,6 +279,19 @@ extern "C" int rails_csr_bsr_stats(const rails_csr *A, int64_t *info, int cap)
 }
 
 // the block matrix of a BSR handle goes with the handle (rails_csr_destroy)
+// the host copy a block-CSR handle keeps (block Jacobi of the iterative A^-1 takes its diagonal blocks from it, itsolve.hip)
+bool rails_bsr_host_arrays(const rails_csr *A, int *b, int64_t *mb, const int64_t **browptr, const int32_t **bcol, const double **bval)
+{
+    const rails_bsr *M = A->bsr();
+    if (!M || (int64_t)M->h_browptr.size() != M->mb + 1) return false;
+    *b = M->b;
+    *mb = M->mb;
+    *browptr = M->h_browptr.data();
+    *bcol = M->h_bcol.data();
+    *bval = M->h_bval.data();
+    return true;
+}
+
 void rails_bsr_release(rails_csr *A)
 {
     if (A->kind != rails_csr::BSR) return;

@@ -32,6 +32,10 @@ class IterativeInverse:
     smoothed-aggregation multigrid, whose iteration count does not grow with the grid: Chebyshev smoothing of degree amg_degree (1) on
     [hi / amg_ratio, hi] (4) per level, strength threshold amg_theta (0.08), levels until at most amg_coarse (256) rows are left, which
     are inverted densely.  None: the library's defaults.  The hierarchy is built by the first solve, or by amg_setup().
+    block_jacobi (both methods, one GPU, not together with poly_degree or amg): precondition with the inverses of the b x b diagonal
+    blocks instead of the diagonal's, for a matrix with b unknowns per cell whose coupling inside a cell is the stiff part.  True: the
+    blocks of the operator -- a block-CSR operator's own, or for a CSR operator those of block_size=b; an array of shape (m / b, b, b):
+    these blocks (any operator).  See block_jacobi().
 
     On a row-partitioned context (Context.set_partition with more than one rank) A is the rank's operator wrapper with its halo plan set,
     the all-reduce hook or the communicator is installed before the object is made, and making it, set(), solve() and precondition() are
@@ -39,7 +43,8 @@ class IterativeInverse:
     (ValueError), and so is trans=True (the transposed product of a row block is single GPU)."""
 
     def __init__(self, ctx, A, method="auto", tol=1e-10, maxit=1000, jacobi=True, strict=False, diag=None, check_every=None, poly_degree=0,
-                 poly_ratio=None, eig_max=None, amg=False, amg_degree=None, amg_ratio=None, amg_theta=None, amg_coarse=None):
+                 poly_ratio=None, eig_max=None, amg=False, amg_degree=None, amg_ratio=None, amg_theta=None, amg_coarse=None, block_jacobi=False,
+                 block_size=0):
         self.ctx = ctx
         self._owned = None
         if isinstance(A, HipOperatorWrapper):
@@ -69,6 +74,8 @@ class IterativeInverse:
             raise ValueError("IterativeInverse: no method %r (cg, bicgstab, auto)" % (method,))
         self.method = method
         self.m = self.n = int(self.A.M())
+        if block_jacobi is True and not block_size and self.A.block_size == 1:  # (b = 0 without blocks is the clearing call there)
+            raise ValueError("IterativeInverse: block_jacobi=True on an operator that is not block-CSR needs block_size=b (2 .. 8), or pass the blocks")
         d = None if diag is None else np.ascontiguousarray(diag, dtype=np.float64)
         if d is not None and d.size != self.m:
             raise ValueError("IterativeInverse: the diagonal has %d entries, the operator %d rows" % (d.size, self.m))
@@ -92,6 +99,10 @@ class IterativeInverse:
                 self.set(name, value)
         if amg:
             self.set("amg", 1)
+        if block_jacobi is True:
+            self.block_jacobi(b=block_size)
+        elif block_jacobi is not False and block_jacobi is not None:
+            self.block_jacobi(block_jacobi, b=block_size)
         oh = C.c_void_p()
         check(ctx.lib.rails_csr_create_iter(ctx.h, h, C.byref(oh)), "rails_csr_create_iter")
         self.op = HipOperatorWrapper(ctx, None, None, None, _handle=_Handle(ctx, oh))
@@ -101,7 +112,8 @@ class IterativeInverse:
         """"tolerance", "max_iterations", "jacobi", "check_every", "strict"; the polynomial preconditioner: "poly_degree" (0 .. 64, 0 is
         off; conjugate gradients only), "poly_ratio" (hi / lo of its interval, above 1), "eig_max" (hi; 0: the Gershgorin bound),
         "poly_fused" (0: never the fused step kernel); the multigrid preconditioner: "amg" (1: on), "amg_degree" (0 .. 8), "amg_ratio"
-        (above 1), "amg_theta" (in [0, 1)), "amg_coarse" (1 .. 1024) (rails_iter_set)"""
+        (above 1), "amg_theta" (in [0, 1)), "amg_coarse" (1 .. 1024); "block_jacobi" (1: the installed diagonal blocks precondition, 0: "jacobi"
+        decides again; block_jacobi() installs them) (rails_iter_set)"""
         check(self.ctx.lib.rails_iter_set(self.h, name.encode(), float(value)), "rails_iter_set")
 
     def solve(self, X, Y=None, trans=False):
@@ -114,13 +126,39 @@ class IterativeInverse:
         return Y
 
     def precondition(self, X, Y=None):
-        """Y = p_K(G A) G X, the preconditioner of the solve on its own (K = poly_degree; 0: G X; with amg on: one V-cycle), for a
+        """Y = p_K(G A) G X, the preconditioner of the solve on its own (K = poly_degree; 0: G X, G the inverse diagonal or with block_jacobi
+        on the inverse diagonal blocks; with amg on: one V-cycle), for a
         HipMultiVectorWrapper X of m rows (a new Y when None).  Queues its work and does not synchronise."""
         if Y is None:
             Y = HipMultiVectorWrapper(self.ctx, self.m, X.n)
         assert Y.n == X.n
         check(self.ctx.lib.rails_iter_precondition(self.ctx.h, self.h, X.panel.h, X.c0, X.n, Y.panel.h, Y.c0), "rails_iter_precondition")
         return Y
+
+    def block_jacobi(self, blocks=None, b=0):
+        """installs the block-Jacobi preconditioner and turns it on (rails_iter_block_jacobi).  blocks: the m / b diagonal blocks, shape
+        (m / b, b, b) -- the library inverts them; None: those of the operator, a block-CSR operator's own (b 0 or its block size) or a
+        CSR operator's for the block size b.  None with b = 0 on any other operator clears the blocks.  Returns block_jacobi_info()."""
+        ptr = None
+        if blocks is not None:
+            blocks = np.ascontiguousarray(blocks, dtype=np.float64)
+            if blocks.ndim != 3 or blocks.shape[1] != blocks.shape[2] or (b and b != blocks.shape[1]) or blocks.shape[0] * blocks.shape[1] != self.m:
+                raise ValueError("IterativeInverse.block_jacobi: blocks of shape %s for %d rows and b = %d: (m / b, b, b) is wanted" % (blocks.shape, self.m, b))
+            b = blocks.shape[1]
+            ptr = blocks.ctypes.data_as(_dp)
+        check(self.ctx.lib.rails_iter_block_jacobi(self.ctx.h, self.h, int(b), ptr), "rails_iter_block_jacobi")
+        return self.block_jacobi_info()
+
+    def block_jacobi_info(self):
+        """{"blocks": how many diagonal blocks are installed (0: none), "b": their size, "inverse": their inverses exactly as the kernels
+        read them, shape (blocks, b, b)} (rails_iter_block_jacobi_info)"""
+        b = C.c_int(0)
+        n = self.ctx.lib.rails_iter_block_jacobi_info(self.h, C.byref(b), None, 0)
+        check(min(n, 0), "rails_iter_block_jacobi_info")
+        inv = np.zeros((n, b.value, b.value))
+        if n:
+            self.ctx.lib.rails_iter_block_jacobi_info(self.h, C.byref(b), inv.ctypes.data_as(_dp), n)
+        return {"blocks": int(n), "b": int(b.value), "inverse": inv}
 
     def amg_setup(self):
         """builds (or rebuilds) the multigrid hierarchy now and uploads it (rails_iter_amg_setup); returns amg_info()"""

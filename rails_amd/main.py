@@ -4,6 +4,7 @@
                                [--eigs K] [--variance FILE] [--pairs FILE [--pairs-out FILE]]
                                [--maps R1,R2,... [--correlation] [--maps-out FILE.mtx]] [--sparse-B] [--warm-start V.mtx | --start-space S.mtx] [--restart-upon-start]
                                [--inverse {lu,cg,bicgstab,iterative}] [--inverse-tol T] [--inverse-poly K] [--inverse-amg] [--block-size b]
+                               [--inverse-block-jacobi]
     python -m torch.distributed.run --nproc-per-node N -m rails_amd.main ... [--backend {nccl,gloo}] [--one-device]
                                                                                   (one rank per GPU, rows partitioned)
 
@@ -35,7 +36,13 @@ on more than one GPU has been made yet; what an inner iteration costs on a real 
 the matrix of a PDE system with b unknowns per cell): the files are read as before and converted on the host, zeros filling the touched
 blocks, and the driver prints the blocks, the fill ratio (stored entries over the file's) and the bytes on the device.  The number of rows
 must be a multiple of b, and the run has one rank (a block-CSR operator is single GPU).  The inverse of a "Projection method" above 1 is
-still built from the CSR arrays.
+built from the CSR arrays unless `--inverse-block-jacobi` is given: an iterative inverse (`--inverse cg`, `bicgstab` or `iterative`) then
+iterates on the block-CSR operator itself and preconditions with the inverses of its b x b diagonal blocks
+(rails_amd.IterativeInverse(block_jacobi=True): for a matrix whose coupling inside a cell is the stiff part, where the scalar diagonal
+says little).  The driver prints b, the number of blocks and, after the solve, the iterations the solve's first application of the inverse
+took (the solver reaches the inverse through a callback handle that notes them); it refuses the flag without `--block-size`, together
+with `--inverse-poly` or `--inverse-amg`, with the sparse LU and on more than one rank, and says so when "Projection method" 1 makes it
+moot.
 
 `--backend gloo` runs the collectives through torch.distributed's gloo backend, staged through host memory, and `--one-device` puts every
 rank on device 0: a rehearsal of the multi-process path on a machine with one GPU, as bench.py has it.
@@ -163,6 +170,9 @@ def main(argv=None):
                                                                             "(K products per application; 0: off)")
     ap.add_argument("--inverse-amg", action="store_true", help="precondition a conjugate-gradients inverse with a smoothed-aggregation multigrid V-cycle "
                                                              "(one rank; not together with --inverse-poly)")
+    ap.add_argument("--inverse-block-jacobi", action="store_true", help="build an iterative inverse on the block-CSR operator of --block-size b and precondition it with "
+                                                                      "the inverses of the b x b diagonal blocks (one rank; not together with --inverse-poly or "
+                                                                      "--inverse-amg)")
     ap.add_argument("--block-size", type=int, default=0, metavar="b", help="keep A (and M) as block-CSR operators of b x b blocks, 2 .. 8; the rows must be a multiple of b; "
                                                                           "one rank")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend of a run on several ranks; gloo = rehearsal of the "
@@ -175,6 +185,18 @@ def main(argv=None):
         raise SystemExit("--block-size %d: blocks of 2 .. 8" % args.block_size)
     if args.block_size and int(os.environ.get("WORLD_SIZE", "1")) > 1:  # refused before the ranks meet
         raise SystemExit("--block-size on %s ranks: a block-CSR operator is single GPU" % os.environ["WORLD_SIZE"])
+    if args.inverse_block_jacobi:  # what the arguments alone decide, before anything is read or built
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit("--inverse-block-jacobi on %s ranks: the block-Jacobi preconditioner is single GPU" % os.environ["WORLD_SIZE"])
+        if not args.block_size:
+            raise SystemExit("--inverse-block-jacobi needs --block-size b: the diagonal blocks are those of the block-CSR operator")
+        if args.inverse_poly:
+            raise SystemExit("--inverse-block-jacobi together with --inverse-poly %d: one preconditioner at a time" % args.inverse_poly)
+        if args.inverse_amg:
+            raise SystemExit("--inverse-block-jacobi together with --inverse-amg: one preconditioner at a time")
+        if args.inverse == "lu":
+            raise SystemExit("--inverse-block-jacobi: the block-Jacobi preconditioner is for an iterative inverse (--inverse cg, bicgstab or iterative), and the "
+                             "inverse chosen is a sparse LU")
 
     import torch
 
@@ -336,6 +358,10 @@ def main(argv=None):
         if args.inverse == "lu" or schur is not None:
             raise SystemExit("--inverse-amg: the multigrid preconditioner is for a conjugate-gradients inverse (--inverse cg or iterative), and the inverse chosen is "
                              "a sparse LU")
+    if args.inverse_block_jacobi and method <= 1:
+        _log(rank, "--inverse-block-jacobi has no effect: 'Projection method' %g applies no inverse" % method)
+    if args.inverse_block_jacobi and schur is not None:  # (the other refusals of the flag need the arguments alone: above)
+        raise SystemExit("--inverse-block-jacobi: a Schur-complement problem keeps the sparse LU inverse of its Schur operator")
     if method > 1:
         if world > 1 and args.inverse == "lu":
             raise SystemExit("'Projection method' %g on %d ranks: the sparse LU inverse runs on one rank; use --inverse iterative (or cg, bicgstab), "
@@ -347,9 +373,10 @@ def main(argv=None):
         elif args.inverse == "lu":
             inverse = rails_amd.SparseLU(ctx, (rowptr, col.astype(np.int32), val))
             what = "a sparse LU of A"
-        elif world > 1:
+        elif world > 1 or args.inverse_block_jacobi:
             # the rank's own row block with its halo plan; the all-reduce hook is in place (above).  Symmetry is a property of the whole
-            # matrix, which every rank has read: every rank reaches the same method
+            # matrix, which every rank has read: every rank reaches the same method.  With --inverse-block-jacobi (one rank): the
+            # block-CSR operator itself, whose diagonal blocks precondition
             how = args.inverse
             if how == "iterative":
                 import scipy.sparse as sp
@@ -370,11 +397,28 @@ def main(argv=None):
                 raise SystemExit("--inverse-amg: the multigrid preconditioner is for conjugate gradients, and the inverse chosen is %s" % inverse.method)
             inverse.set("amg", 1)
             amg = inverse.amg_setup()
-        solver.set_inverse(inverse)
+        if isinstance(inverse, rails_amd.IterativeInverse) and args.inverse_block_jacobi:
+            bj = inverse.block_jacobi()
+            bj_first = {}
+
+            def counted(trans, X, Y):
+                # the solve's own applications, through a callback handle that notes what the first of them took
+                inverse.solve(X, Y, trans=trans)
+                if not bj_first:
+                    bj_first.update(columns=X.n, iterations=inverse.stats()["max_iterations_of_a_column"])
+                return 0
+
+            bj_handle = rails_amd.HipOperatorWrapper.from_callback(ctx, m, counted)
+            solver.set_inverse(bj_handle)
+        else:
+            solver.set_inverse(inverse)
         if isinstance(inverse, rails_amd.IterativeInverse):
-            _log(rank, "Projection method %g: A^-1 is an iterative solve on the device, method %s, Jacobi, tolerance %g" % (method, inverse.method, args.inverse_tol))
+            _log(rank, "Projection method %g: A^-1 is an iterative solve on the device, method %s, %s, tolerance %g" % (
+                method, inverse.method, "block Jacobi" if args.inverse_block_jacobi else "Jacobi", args.inverse_tol))
             if args.inverse_poly:
                 _log(rank, "its preconditioner: a Chebyshev polynomial of degree %d in the Jacobi-scaled matrix" % args.inverse_poly)
+            if args.inverse_block_jacobi:
+                _log(rank, "its preconditioner: block Jacobi on the block-CSR operator, b = %d, %d blocks" % (bj["b"], bj["blocks"]))
             if args.inverse_amg:
                 _log(rank, "its preconditioner: a smoothed-aggregation multigrid V-cycle, %d levels of %s rows, operator complexity %.2f, set up in %.3f s" % (
                     amg["levels"], " / ".join(str(r) for r in amg["rows"]), amg["operator_complexity"], amg["host_seconds"] + amg["upload_seconds"]))
@@ -399,6 +443,8 @@ def main(argv=None):
         st = inverse.stats()
         _log(rank, "iterative inverse (%s): %d solves of %d columns, %d inner iterations in all, %d flagged columns" % (
             inverse.method, st["total_solves"], st["total_columns"], st["total_iterations"], st["total_flagged_columns"]))
+        if args.inverse_block_jacobi and bj_first:
+            _log(rank, "its first application (%d columns): %d iterations at most" % (bj_first["columns"], bj_first["iterations"]))
         if args.inverse_poly:  # what the object itself counted in its last solve, not what was asked for
             _log(rank, "its last solve: %d applications of the polynomial, %d products with A, %d of them in fused steps" % (
                 st["poly_applications"], st["products"], st["fused_launches"]))
