@@ -244,7 +244,7 @@ int rails_csr_create_lu(rails_ctx *ctx, rails_lu *lu, rails_csr **out);
  * finite on any rank gives RAILS_EINVAL on every rank.  On a context that does not reduce nothing of this runs.
  * Settings (rails_iter_set): "tolerance" 1e-10, "max_iterations" 1000, "jacobi" 1, "check_every" 8, "strict" 0, and those of the polynomial
  * preconditioner below: "poly_degree" 0, "poly_ratio" 10, "eig_max" 0, "poly_fused" 1; those of the multigrid preconditioner: "amg" 0,
- * "amg_degree" 1, "amg_ratio" 4, "amg_theta" 0.08, "amg_coarse" 256; block Jacobi: "block_jacobi" 0.
+ * "amg_degree" 1, "amg_ratio" 4, "amg_theta" 0.08, "amg_coarse" 256; block Jacobi: "block_jacobi" 0; block multigrid: "block_amg" 0.
  * Chebyshev polynomial preconditioner (CG only; rails_amd/csrc/cheb_coef.h): with "poly_degree" K in 1 .. 64 the
  * solve preconditions with z = p_K(G A) G r, K products with A in a row without an inner product, a scalar kernel or a read-back between
  * them; G is the Jacobi diagonal's inverse when Jacobi is in effect and otherwise +-I, the sign of the operator's diagonal.  The
@@ -282,6 +282,19 @@ int rails_csr_create_lu(rails_ctx *ctx, rails_lu *lu, rails_csr **out);
  * handle's block size; a context that reduces; "block_jacobi" 1 without blocks; and "block_jacobi" 1 together with a "poly_degree"
  * above 0 or "amg" 1, in whichever order they are set (one preconditioner at a time).  Not available: block Jacobi as the G of the
  * Chebyshev polynomial, and on a row partition.
+ * Block multigrid preconditioner (CG only, single GPU, block-CSR handles only; rails_amd/csrc/block_amg_host.h):
+ * with "block_amg" 1 the solve preconditions with one V-cycle of smoothed aggregation on the cells of a block-CSR operator: the cycle of
+ * "amg" with G the inverses of the b x b diagonal blocks of every level matrix (block-CSR on every level, the same b), aggregation by
+ * the Frobenius norms of the blocks, every unknown of a cell going to the same component of its aggregate.  "amg_degree", "amg_ratio",
+ * "amg_theta" and "amg_coarse" keep their meaning, ranges and defaults and serve both multigrids; "poly_fused" 0 keeps this cycle off
+ * its fused kernels too.  rails_iter_block_amg_setup builds the hierarchy; the first solve or rails_iter_precondition with "block_amg"
+ * on calls it when there is none.  "block_amg" 0, the default, is the solve without any of this: the same kernels, bits and launch
+ * counts.  RAILS_EINVAL, before any device work: a BiCGStab object; an operator that is not a block-CSR handle with a host copy;
+ * "block_amg" 1 together with "block_jacobi" 1, "amg" 1 or a "poly_degree" above 0, in whichever order they are set (one
+ * preconditioner at a time); a context that reduces; 2^24 rows or more; and from the set-up a block row without a stored diagonal
+ * block, block columns of a block row that are not strictly increasing, a non-finite entry, a diagonal block whose scalar diagonal has
+ * a zero or entries of both signs (or a sign that differs between blocks), a singular diagonal block (the block is named), a hierarchy
+ * that does not coarsen below 1025 rows, and a last matrix that is not definite.
  * Outcomes: a zero right-hand-side column gives x = 0 after 0 iterations; a column that stops at max_iterations or breaks down (a
  * vanishing denominator; CG: p'Ap of the wrong sign, the operator is not definite) keeps its last iterate and is flagged, and the call
  * still returns RAILS_OK unless "strict" is set (RAILS_ENOCONV); a right-hand side that is not finite gives RAILS_EINVAL. */
@@ -308,6 +321,13 @@ int rails_iter_amg_setup(rails_ctx *ctx, rails_iter *it);
  * and upload time in microseconds and, in hi[n + 1], the operator complexity.  Any pointer may be NULL.  Returns n (0: no hierarchy has
  * been built) or a negative code; at most cap entries are written.  rails_iter_stats keeps its 19 entries. */
 int rails_iter_amg_info(const rails_iter *it, int64_t *rows, int64_t *nnz, double *hi, int cap);
+/* Builds or rebuilds the block hierarchy of "block_amg" from the host copy a block-CSR handle keeps, and uploads it.  With "block_amg" on,
+ * rails_iter_precondition applies one cycle.  Synchronises. */
+int rails_iter_block_amg_setup(rails_ctx *ctx, rails_iter *it);
+/* rails_iter_amg_info on the block hierarchy, with its conventions: per matrix the rows, the scalar entries (blocks times b^2) and the
+ * smoother's bound (max_i sum_j |(G A)_ij|; 0 for the last matrix), then the two trailing entries.  Returns 0 when no block hierarchy has
+ * been built (rails_iter_amg_info returns 0 on a block hierarchy, and this on a scalar one). */
+int rails_iter_block_amg_info(const rails_iter *it, int64_t *rows, int64_t *nnz, double *hi, int cap);
 /* Installs the block-Jacobi preconditioner and sets "block_jacobi" to 1.  blocks_host != NULL: the m / b diagonal blocks themselves, each
  * row-major b x b (the library inverts them, as it does diag_host), on any square operator.  blocks_host == NULL on a block-CSR handle: the
  * blocks of its host copy, b 0 or the handle's block size, a diagonal block stored more than once in a block row summed in stored order;

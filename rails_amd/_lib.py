@@ -98,6 +98,8 @@ SIGNATURES = {
     "rails_iter_precondition": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int]),
     "rails_iter_amg_setup": (C.c_int, [_vp, _vp]),
     "rails_iter_amg_info": (C.c_int, [_vp, _i64p, _i64p, _dp, C.c_int]),
+    "rails_iter_block_amg_setup": (C.c_int, [_vp, _vp]),
+    "rails_iter_block_amg_info": (C.c_int, [_vp, _i64p, _i64p, _dp, C.c_int]),
     "rails_iter_block_jacobi": (C.c_int, [_vp, _vp, C.c_int, _dp]),
     "rails_iter_block_jacobi_info": (C.c_int64, [_vp, _ip, _dp, C.c_int64]),
     "rails_iter_stats": (C.c_int, [_vp, _dp, C.c_int]),

@@ -61,8 +61,10 @@ int take_diagonal(const rails_amg_csr &A, int level, std::vector<double> &diag, 
     return RAILS_OK;
 }
 
+} // namespace
+
 // the three passes; returns the number of aggregates
-int64_t aggregate(const rails_amg_csr &A, const std::vector<double> &diag, double theta_l, std::vector<int32_t> &agg)
+int64_t rails_amg_aggregate(const rails_amg_csr &A, const std::vector<double> &diag, double theta_l, std::vector<int32_t> &agg)
 {
     const int64_t n = A.n_rows;
     auto strong = [&](int64_t i, int64_t q) {
@@ -107,7 +109,7 @@ int64_t aggregate(const rails_amg_csr &A, const std::vector<double> &diag, doubl
 
 // C = A B by Gustavson's row-wise product: row i of C gathers a_ik times row k of B in the stored order of both, so every entry is one
 // sum of fixed order; the columns of a row are then sorted and every structural entry is kept.
-void spgemm(const rails_amg_csr &A, const rails_amg_csr &B, rails_amg_csr &C)
+void rails_amg_spgemm(const rails_amg_csr &A, const rails_amg_csr &B, rails_amg_csr &C)
 {
     C.n_rows = A.n_rows;
     C.n_cols = B.n_cols;
@@ -143,6 +145,8 @@ void spgemm(const rails_amg_csr &A, const rails_amg_csr &B, rails_amg_csr &C)
     }
 }
 
+namespace {
+
 // P = (I - omega D^-1 A) T: entry (i, a) is [a == agg_i] - (omega / d_i) sum over the j of aggregate a of a_ij, the sum in stored order
 void smoothed_prolongation(const rails_amg_csr &A, const std::vector<double> &dinv, const std::vector<int32_t> &agg, int64_t n_agg, double omega,
                            rails_amg_csr &P)
@@ -154,7 +158,7 @@ void smoothed_prolongation(const rails_amg_csr &A, const std::vector<double> &di
     T.col.assign(agg.begin(), agg.end());
     T.val.assign((size_t)A.n_rows, 1.0);
     for (int64_t i = 0; i <= A.n_rows; ++i) T.rowptr[(size_t)i] = i;
-    spgemm(A, T, P); // A T; the diagonal of A is stored, so the pattern of A T holds the pattern of T
+    rails_amg_spgemm(A, T, P); // A T; the diagonal of A is stored, so the pattern of A T holds the pattern of T
     for (int64_t i = 0; i < A.n_rows; ++i) {
         const double s = omega * dinv[(size_t)i];
         for (int64_t q = P.rowptr[i]; q < P.rowptr[i + 1]; ++q) {
@@ -164,8 +168,10 @@ void smoothed_prolongation(const rails_amg_csr &A, const std::vector<double> &di
     }
 }
 
+} // namespace
+
 // the dense inverse of the last matrix through Cholesky of defsign A_L
-int dense_inverse(const rails_amg_csr &A, double defsign, std::vector<double> &inv)
+int rails_amg_dense_inverse(const rails_amg_csr &A, double defsign, std::vector<double> &inv)
 {
     const int n = (int)A.n_rows;
     std::vector<double> M((size_t)n * n, 0.0);
@@ -193,8 +199,6 @@ int dense_inverse(const rails_amg_csr &A, double defsign, std::vector<double> &i
     return RAILS_OK;
 }
 
-} // namespace
-
 int rails_amg_build_host(int64_t n, const int64_t *rowptr, const int32_t *col, const double *val, double theta, int coarse, rails_amg_hierarchy *out)
 {
     if (!out) AMG_FAIL("rails_amg_build_host: null output");
@@ -219,7 +223,7 @@ int rails_amg_build_host(int64_t n, const int64_t *rowptr, const int32_t *col, c
         if ((negative ? -1.0 : 1.0) != out->defsign) AMG_FAIL("rails_amg_build_host: the matrix is not definite (the diagonal changes sign at level %d)", l);
         if (cur.n_rows <= coarse || l + 1 >= RAILS_AMG_MAX_LEVELS) break;
         std::vector<int32_t> agg;
-        const int64_t n_agg = aggregate(cur, diag, theta * std::pow(0.5, l), agg);
+        const int64_t n_agg = rails_amg_aggregate(cur, diag, theta * std::pow(0.5, l), agg);
         if (n_agg * 5 > cur.n_rows * 4) break; // the level would keep more than 0.8 of its rows
         rails_amg_level L;
         L.hi = rails_cheb_gershgorin(cur.n_rows, cur.rowptr.data(), cur.val.data(), dinv.data());
@@ -233,8 +237,8 @@ int rails_amg_build_host(int64_t n, const int64_t *rowptr, const int32_t *col, c
         rc = rails_csr_transpose_host(L.P.n_rows, L.P.n_cols, L.P.rowptr.data(), L.P.col.data(), L.P.val.data(), L.R.rowptr.data(), L.R.col.data(), L.R.val.data());
         if (rc != RAILS_OK) return rc;
         rails_amg_csr RA, next;
-        spgemm(L.R, cur, RA);
-        spgemm(RA, L.P, next);
+        rails_amg_spgemm(L.R, cur, RA);
+        rails_amg_spgemm(RA, L.P, next);
         L.A = std::move(cur);
         L.dinv = std::move(dinv);
         L.agg = std::move(agg);
@@ -244,7 +248,7 @@ int rails_amg_build_host(int64_t n, const int64_t *rowptr, const int32_t *col, c
     if (cur.n_rows > RAILS_AMG_MAX_COARSE)
         AMG_FAIL("rails_amg_build_host: the matrix does not coarsen: %lld rows are left after %d level(s), above the %d a dense coarsest block may have",
                  (long long)cur.n_rows, (int)out->levels.size(), RAILS_AMG_MAX_COARSE);
-    rc = dense_inverse(cur, out->defsign, out->coarse_inv);
+    rc = rails_amg_dense_inverse(cur, out->defsign, out->coarse_inv);
     if (rc != RAILS_OK) return rc;
     out->coarse = std::move(cur);
     return RAILS_OK;

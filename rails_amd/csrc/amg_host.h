@@ -53,4 +53,12 @@ struct rails_amg_hierarchy {
 int rails_amg_build_host(int64_t n, const int64_t *rowptr, const int32_t *col, const double *val, double theta, int coarse,
                          rails_amg_hierarchy *out);
 
+// The pieces the block form of the set-up (block_amg_host.cpp) takes from here, so that each rule is written once:
+// the three aggregation passes on a matrix with its diagonal (returns the number of aggregates),
+int64_t rails_amg_aggregate(const rails_amg_csr &A, const std::vector<double> &diag, double theta_l, std::vector<int32_t> &agg);
+// C = A B by Gustavson's row-wise product, the columns of a row sorted, every structural entry kept,
+void rails_amg_spgemm(const rails_amg_csr &A, const rails_amg_csr &B, rails_amg_csr &C);
+// and the dense inverse (column-major) of the last matrix through the Cholesky factorisation of defsign A.
+int rails_amg_dense_inverse(const rails_amg_csr &A, double defsign, std::vector<double> &inv);
+
 #endif

@@ -1,7 +1,7 @@
 // iter_kernels.inc -- the device code of the iterative A^-1 operator, included by itsolve.hip inside its anonymous namespace (one translation
 // unit, as with lanczos_pass.inc and dense_gram.inc): the shape every pass shares, the passes of CG and BiCGStab, the Chebyshev sweep
 // (init, unfused pass, the fused step on the shared row gather of csr_row_gather.inc), the multigrid cycle's own kernels, the scalar
-// step and, at the end, the block forms of the passes that apply the preconditioner when it is block Jacobi.  PassGeom is iter_geom.h's rails_pass_geom; itsolve.hip's head comment says what the passes are.
+// step, the block forms of the passes that apply the preconditioner when it is block Jacobi and, at the end, the block multigrid cycle's kernels.  PassGeom is iter_geom.h's rails_pass_geom; itsolve.hip's head comment says what the passes are.
 typedef double it_v2 __attribute__((ext_vector_type(2)));
 
 enum { STEP_CG_INIT = 0, STEP_CG_ALPHA, STEP_CG_BETA, STEP_BI_INIT, STEP_BI_ALPHA, STEP_BI_OMEGA, STEP_BI_END };
@@ -553,4 +553,120 @@ __global__ __launch_bounds__(256) void k_bj_apply(PassGeom g, const double *__re
     iter_pass_block<B, 0, false>(
         g, ginv, nullptr, [&](int64_t o) { return bj_row{ld2(R + o), (it_v2){0.0, 0.0}}; },
         [&](int64_t o, bool has1, const bj_row &, it_v2 z, it_v2 *) { st2(Z + o, z, has1); });
+}
+
+// ---- the block multigrid cycle (DESIGN.md section 19): the Chebyshev sweep with G the inverses of the diagonal blocks of a block-CSR
+// level matrix.  The fused step and the residual run on the block-row body k_spmm_bsr runs on (bsr_row_gather.inc): the lanes that own a
+// block row hold all B rows of A z for their two columns, so G (r - A z) is register-local.  Instantiations and launching switches expand
+// from RAILS_BSR_TABLE (bsr_choice.h) and RAILS_BJ_TABLE; which step a level takes is block_amg_choice.h's. ----
+#include "bsr_row_gather.inc"
+
+// The step's epilogue for one block row and one column pair at offset o (row stride ld) of the work panels, from t = (A Zin) of the B
+// rows: u_j = R_j - t_j; then row by row w_i = sum_j G[i][j] u_j (one accumulator from +0, one fma per j, j ascending: iter_pass_block's
+// rule), d_i = fma(a, D_i, b w_i) stored in place, Zout_i = Zin_i + d_i.  gb: the block's inverse, every lane of a group at one address.
+// The fused step and the unfused pass both end here.
+template <int B>
+__device__ __forceinline__ void cheb_block_epilogue(const double *__restrict__ gb, it_v2 (&t)[B], const double *__restrict__ R, double *__restrict__ D,
+                                                    const double *Zin, double *Zout, int64_t o, int64_t ld, double a, double b, bool full)
+{
+#pragma unroll
+    for (int j = 0; j < B; ++j) t[j] = ld2(R + o + j * ld) - t[j];
+#pragma unroll
+    for (int i = 0; i < B; ++i) {
+        it_v2 w = (it_v2){0.0, 0.0};
+#pragma unroll
+        for (int j = 0; j < B; ++j) {
+            const double v = gb[i * B + j];
+            w.x = __builtin_fma(v, t[j].x, w.x);
+            w.y = __builtin_fma(v, t[j].y, w.y);
+        }
+        const it_v2 dold = ld2(D + o + i * ld);
+        it_v2 d;
+        d.x = __builtin_fma(a, dold.x, b * w.x);
+        d.y = __builtin_fma(a, dold.y, b * w.y);
+        st2(D + o + i * ld, d, full);
+        st2(Zout + o + i * ld, ld2(Zin + o + i * ld) + d, full);
+    }
+}
+
+// the accumulators of the shared body as the pair at the lane's own column: the lane of an odd last column holds its column's value in .y
+// (.x for a panel of one column); its second entry is the pad column's, read and never written
+template <int B>
+__device__ __forceinline__ void bsr_own_pair(const bsr_v2 (&acc)[B], bool full, bool one, it_v2 (&t)[B])
+{
+#pragma unroll
+    for (int r = 0; r < B; ++r) {
+        t[r].x = (full || one) ? acc[r].x : acc[r].y;
+        t[r].y = acc[r].y;
+    }
+}
+
+// The fused step on a block-CSR level matrix.  Zin and Zout are different panels (every workgroup reads rows of Zin that others own); all
+// panels are work panels: window at column 0, one row stride, rows 16-byte aligned, a pad column beside an odd width.
+template <int B, int LPR>
+__global__ __launch_bounds__(rails_bsr_threads(B)) void k_cheb_step_bsr(int64_t mb, const int64_t *__restrict__ browptr, const int32_t *__restrict__ bcol,
+                                                                        const double *__restrict__ bval, const double *__restrict__ Zin, int ld, int nc, int rpg,
+                                                                        int64_t blocks_per_xcd, const double *__restrict__ ginv, double a, double b,
+                                                                        const double *__restrict__ R, double *__restrict__ D, double *__restrict__ Zout)
+{
+    bsr_row_gather<B, LPR>(mb, browptr, bcol, bval, Zin, ld, nc, rpg, blocks_per_xcd, [&](int64_t brow, int cb, const bsr_v2 (&acc)[B], bool full, bool one) {
+        it_v2 t[B];
+        bsr_own_pair<B>(acc, full, one, t);
+        cheb_block_epilogue<B>(ginv + brow * (B * B), t, R, D, Zin, Zout, brow * B * (int64_t)ld + cb, ld, a, b, full);
+    });
+}
+
+// Q = R - A Z on the shared body
+template <int B, int LPR>
+__global__ __launch_bounds__(rails_bsr_threads(B)) void k_amg_residual_bsr(int64_t mb, const int64_t *__restrict__ browptr, const int32_t *__restrict__ bcol,
+                                                                           const double *__restrict__ bval, const double *__restrict__ Z, int ld, int nc, int rpg,
+                                                                           int64_t blocks_per_xcd, const double *__restrict__ R, double *__restrict__ Q)
+{
+    bsr_row_gather<B, LPR>(mb, browptr, bcol, bval, Z, ld, nc, rpg, blocks_per_xcd, [&](int64_t brow, int cb, const bsr_v2 (&acc)[B], bool full, bool one) {
+        it_v2 t[B];
+        bsr_own_pair<B>(acc, full, one, t);
+        const int64_t o = brow * B * (int64_t)ld + cb;
+#pragma unroll
+        for (int r = 0; r < B; ++r) st2(Q + o + r * (int64_t)ld, ld2(R + o + r * (int64_t)ld) - t[r], full);
+    });
+}
+
+// d = z = (G r) / theta, the sweep's start with blocks
+template <int B>
+__global__ __launch_bounds__(256) void k_cheb_init_bj(PassGeom g, const double *__restrict__ ginv, double theta, const double *__restrict__ R, double *__restrict__ D,
+                                                      double *__restrict__ Z)
+{
+    iter_pass_block<B, 0, false>(
+        g, ginv, nullptr, [&](int64_t o) { return bj_row{ld2(R + o), (it_v2){0.0, 0.0}}; },
+        [&](int64_t o, bool has1, const bj_row &, it_v2 z, it_v2 *) {
+            const it_v2 d = z / theta;
+            st2(D + o, d, has1);
+            st2(Z + o, d, has1);
+        });
+}
+
+// The unfused step with blocks, after Q = A Z: iter_pass_block's walk over the block rows of a slab (the same trip count for every thread
+// of the block, a thread past the slab's last block row loads that block row again and stores nothing), its loads those of the B rows of
+// Q, then the fused step's own epilogue, in place in Z.
+template <int B>
+__global__ __launch_bounds__(256) void k_cheb_pass_bj(PassGeom g, const double *__restrict__ ginv, double a, double b, const double *__restrict__ Q,
+                                                      const double *__restrict__ R, double *__restrict__ D, double *__restrict__ Z)
+{
+    const int TX = 1 << g.tx_bits, TY = 256 >> g.tx_bits;
+    const int tx = threadIdx.x & (TX - 1), ty = threadIdx.x >> g.tx_bits;
+    const int c = 2 * tx;
+    if (c >= g.ncw) return;
+    const bool has1 = c + 1 < g.ncw;
+    const int64_t nb = g.m / B, bps = g.rows_per_slab / B;
+    const int64_t b_begin = (int64_t)blockIdx.x * bps;
+    const int64_t b_end = b_begin + bps < nb ? b_begin + bps : nb;
+    for (int64_t base = b_begin; base < b_end; base += TY) {
+        const bool live = base + ty < b_end;
+        const int64_t br = live ? base + ty : b_end - 1;
+        const int64_t o = br * B * g.ld + c;
+        it_v2 t[B];
+#pragma unroll
+        for (int i = 0; i < B; ++i) t[i] = ld2(Q + o + (int64_t)i * g.ld);
+        if (live) cheb_block_epilogue<B>(ginv + br * (B * B), t, R, D, Z, Z, o, g.ld, a, b, has1);
+    }
 }

@@ -9,7 +9,10 @@
 // Jacobi ("block_jacobi", rails_iter_block_jacobi; block_jacobi_host.h for the blocks and their inverses on the host, DESIGN.md section
 // 18): the inverses of the b x b diagonal blocks in place of the diagonal's, in block forms of the passes that apply it (k_cg_init_bj,
 // k_cg_update_bj, k_bi_dir_bj, k_bi_s_bj, k_bj_apply on iter_pass_block), every pass of such a solve on slabs of whole block rows
-// (rails_iter_pass_geom_block).  This file is the host code; the
+// (rails_iter_pass_geom_block); or, for conjugate gradients on a block-CSR operator, with one V-cycle of block multigrid ("block_amg",
+// rails_iter_block_amg_setup; block_amg_host.h for the set-up on the host): the same Run::vcycle on block-CSR level
+// matrices with the inverse diagonal blocks as the smoother's G, the step fused with the block-CSR product on bsr_row_gather.inc
+// (k_cheb_step_bsr, k_amg_residual_bsr) or unfused (k_cheb_init_bj, k_cheb_pass_bj), as block_amg_choice.h decides.  This file is the host code; the
 // kernels are iter_kernels.inc, the geometry of a pass is iter_geom.h.  Both preconditioners are Chebyshev sweeps (struct Sweep,
 // Run::sweep_start, Run::sweep_step); what a call needs of them -- coefficients, the choice of the fused step, geometry -- is its plan,
 // made before anything is queued (begin_call, plan_call, plan_group), and every refusal is there.
@@ -40,7 +43,10 @@
 #include <vector>
 
 #include "amg_host.h"
+#include "block_amg_choice.h"
+#include "block_amg_host.h"
 #include "block_jacobi_host.h"
+#include "bsr_choice.h"
 #include "cheb_coef.h"
 #include "iter_agree.h"
 #include "iter_geom.h"
@@ -69,6 +75,7 @@ struct AmgLevel {
     rails_csr *A = nullptr; // level 0: the object's operator (not owned)
     rails_csr *P = nullptr, *R = nullptr;
     double *dinv = nullptr;
+    double *ginv = nullptr; // the block hierarchy: the inverses of the level's diagonal blocks (dinv is null then)
     rails_panel *w[L_COUNT] = {};
 };
 struct Amg {
@@ -77,6 +84,7 @@ struct Amg {
     double *Ainv = nullptr;
     rails_panel *rc = nullptr, *zc = nullptr;
     int cols = 0; // columns of the level panels
+    int b = 0;    // 0: the scalar hierarchy of "amg"; else the block size of the block hierarchy of "block_amg" 
     double host_seconds = 0.0, upload_seconds = 0.0;
 };
 
@@ -114,6 +122,8 @@ struct rails_iter {
     int amg = 0, amg_degree = 1, amg_coarse = RAILS_AMG_COARSE;
     double amg_ratio = 4.0, amg_theta = RAILS_AMG_THETA;
     Amg *hier = nullptr;
+    // the block multigrid preconditioner ("block_amg"): the same cycle on a block hierarchy (hier->b is the block size)
+    int block_amg = 0;
     long last_cycles = 0, last_cycle_products = 0, last_cycle_launches = 0; // of the last call: cycles, and the products and launches inside them
     // block Jacobi ("block_jacobi"): the inverses of the m / bj_b diagonal blocks, row-major, on the device and as
     // uploaded on the host (rails_iter_block_jacobi_info); the setting is on only while there are blocks
@@ -160,6 +170,7 @@ void amg_release(rails_iter *it)
         rails_csr_destroy(L.P);
         rails_csr_destroy(L.R);
         hipFree(L.dinv);
+        hipFree(L.ginv);
     }
     hipFree(H->Ainv);
     delete H;
@@ -191,6 +202,7 @@ int amg_check(const rails_iter *it, const char *who)
     RAILS_REQUIRE(it->method == RAILS_ITER_CG, "%s: \"amg\" on a BiCGStab object: the multigrid preconditioner is for conjugate gradients (a symmetric definite operator)", who);
     RAILS_REQUIRE(it->poly_degree == 0, "%s: \"amg\" together with poly_degree %d: one preconditioner at a time", who, it->poly_degree);
     RAILS_REQUIRE(!it->block_jacobi, "%s: \"amg\" together with \"block_jacobi\": one preconditioner at a time", who);
+    RAILS_REQUIRE(!it->block_amg, "%s: \"amg\" together with \"block_amg\": one preconditioner at a time", who);
     RAILS_REQUIRE(A->kind != rails_csr::CALLBACK, "%s: \"amg\" needs the entries of the matrix: the operator is a callback", who);
     RAILS_REQUIRE(A->kind != rails_csr::LU && A->kind != rails_csr::ITER, "%s: \"amg\" needs the entries of the matrix: the operator is an LU or an iterative solve", who);
     RAILS_REQUIRE(A->kind != rails_csr::BSR, "%s: \"amg\" needs the entries of the matrix as scalar CSR arrays: the operator is block-CSR (keep a CSR handle for the preconditioner)", who);
@@ -200,11 +212,34 @@ int amg_check(const rails_iter *it, const char *who)
     return RAILS_OK;
 }
 
+// What the block multigrid preconditioner refuses before it looks at the entries (block_amg_host.cpp refuses those), by reason; nothing
+// here touches the device.  rails_iter_set is the gate of "block_amg" as it is of "amg"; rails_iter_block_amg_setup checks again.
+int bamg_check(const rails_iter *it, const char *who)
+{
+    const rails_csr *A = it->A;
+    RAILS_REQUIRE(it->method == RAILS_ITER_CG, "%s: \"block_amg\" on a BiCGStab object: the multigrid preconditioner is for conjugate gradients (a symmetric definite operator)", who);
+    RAILS_REQUIRE(it->poly_degree == 0, "%s: \"block_amg\" together with poly_degree %d: one preconditioner at a time", who, it->poly_degree);
+    RAILS_REQUIRE(!it->block_jacobi, "%s: \"block_amg\" together with \"block_jacobi\": one preconditioner at a time", who);
+    RAILS_REQUIRE(!it->amg, "%s: \"block_amg\" together with \"amg\": one preconditioner at a time", who);
+    int b = 0;
+    int64_t mb = 0;
+    const int64_t *browptr = nullptr;
+    const int32_t *bcol = nullptr;
+    const double *bval = nullptr;
+    RAILS_REQUIRE(A->kind == rails_csr::BSR && rails_bsr_host_arrays(A, &b, &mb, &browptr, &bcol, &bval),
+                  "%s: \"block_amg\" needs the blocks of the matrix: the operator is not a block-CSR handle with a host copy (rails_csr_create_bsr)", who);
+    RAILS_REQUIRE(!it->reduces, "%s: \"block_amg\" on a context that reduces (more than one rank, an all-reduce hook or a communicator): the multigrid preconditioner is single GPU", who);
+    RAILS_REQUIRE(rails_bamg_rows_ok(it->m, b), "%s: \"block_amg\" on %lld rows of block size %d: the multigrid cycle's kernels address fewer than 2^24 rows", who,
+                  (long long)it->m, b);
+    return RAILS_OK;
+}
+
 bool uses_panel(const rails_iter *it, int which)
 {
     const bool jac = it->dinv != nullptr || it->bj_dev != nullptr;
-    if (which == W_D || which == W_Z2) return it->poly_degree > 0 || it->amg;
-    if (which == W_Z && (it->poly_degree > 0 || it->amg)) return true;
+    const bool mg = it->amg || it->block_amg;
+    if (which == W_D || which == W_Z2) return it->poly_degree > 0 || mg;
+    if (which == W_Z && (it->poly_degree > 0 || mg)) return true;
     if (it->method == RAILS_ITER_CG) return which == W_X || which == W_R || which == W_P || which == W_Q || (which == W_Z && jac);
     return which == W_X || which == W_R || which == W_P || which == W_Q || which == W_RH || which == W_T || ((which == W_Z || which == W_SH) && jac);
 }
@@ -276,7 +311,13 @@ RAILS_BJ_PICK(bj_cg_init, BJ_CG_INIT)
 RAILS_BJ_PICK(bj_cg_update, BJ_CG_UPDATE)
 RAILS_BJ_PICK(bj_apply, BJ_APPLY)
 RAILS_BJ_PICK(bj_bi_dir, BJ_BI_DIR)
+#define BJ_CHEB_INIT(B) (&k_cheb_init_bj<B>)
+#define BJ_CHEB_INIT_CASE(B) case B: return BJ_CHEB_INIT(B);
+#define BJ_CHEB_PASS(B) (&k_cheb_pass_bj<B>)
+#define BJ_CHEB_PASS_CASE(B) case B: return BJ_CHEB_PASS(B);
 RAILS_BJ_PICK(bj_bi_s, BJ_BI_S)
+RAILS_BJ_PICK(bj_cheb_init, BJ_CHEB_INIT)
+RAILS_BJ_PICK(bj_cheb_pass, BJ_CHEB_PASS)
 #undef RAILS_BJ_PICK
 
 // A Chebyshev sweep on an operator: z = p(G A) G r by d = z = G r / theta, then steps d = a d + b G (r - A z), z += d.  The polynomial
@@ -293,6 +334,15 @@ struct Sweep {
     PassGeom g;
     int64_t slabs = 0;
     int at = 0; // the z panel that holds z now
+    // the block form of G (the block multigrid cycle): the inverses of the diagonal blocks of a block-CSR A, bs > 0 their size; the level
+    // matrix's device arrays and the step the level takes (block_amg_choice.h), filled in by plan_call and plan_group
+    const double *ginv = nullptr;
+    int bs = 0;
+    int64_t mb = 0, max_brow = 0;
+    const int64_t *browptr = nullptr;
+    const int32_t *bcol = nullptr;
+    const double *bval = nullptr;
+    BamgStep step{};
 };
 
 struct Run {
@@ -388,14 +438,58 @@ struct Run {
     void sweep_start(Sweep &s, int steps)
     {
         s.at = rails_cheb_start_panel(s.fused, steps);
-        pass(s.g, s.slabs, k_cheb_init, s.gvec, s.gs, s.theta, s.r->d, s.d->d, s.z[s.at]->d);
+        if (s.bs)
+            pass(s.g, s.slabs, bj_cheb_init(s.bs, false), s.ginv, s.theta, (const double *)s.r->d, s.d->d, s.z[s.at]->d);
+        else
+            pass(s.g, s.slabs, k_cheb_init, s.gvec, s.gs, s.theta, s.r->d, s.d->d, s.z[s.at]->d);
+    }
+    // a kernel on the shared block-row body over a block sweep's matrix, launched as k_spmm_bsr is for the group's width.  One product.
+    int block_step(Sweep &s, const double *zin, double a, double b, double *zout)
+    {
+        const BsrChoice &k = s.step.k;
+#define RAILS_BAMG_CASE(B, LPR)                                                                                                                   \
+    case rails_bsr_inst(B, LPR):                                                                                                                  \
+        launch((k_cheb_step_bsr<B, LPR>), k.grid, k.threads, s.mb, s.browptr, s.bcol, s.bval, zin, g.ld, g.ncw, k.rpg, k.bpx, s.ginv, a, b, (const double *)s.r->d, s.d->d, \
+               zout);                                                                                                                             \
+        break;
+        switch (k.key()) {
+            RAILS_BSR_TABLE(RAILS_BAMG_CASE)
+        default: rails_set_error("rails_iter: k_cheb_step_bsr<%d, %d> is not among the instantiations of bsr_choice.h", k.b, k.lpr); return RAILS_EINVAL;
+        }
+#undef RAILS_BAMG_CASE
+        count_product();
+        return RAILS_OK;
+    }
+    int block_residual(Sweep &s, const double *z)
+    {
+        const BsrChoice &k = s.step.k;
+#define RAILS_BAMG_CASE(B, LPR)                                                                                                                   \
+    case rails_bsr_inst(B, LPR):                                                                                                                  \
+        launch((k_amg_residual_bsr<B, LPR>), k.grid, k.threads, s.mb, s.browptr, s.bcol, s.bval, z, g.ld, g.ncw, k.rpg, k.bpx, (const double *)s.r->d, s.q->d);        \
+        break;
+        switch (k.key()) {
+            RAILS_BSR_TABLE(RAILS_BAMG_CASE)
+        default: rails_set_error("rails_iter: k_amg_residual_bsr<%d, %d> is not among the instantiations of bsr_choice.h", k.b, k.lpr); return RAILS_EINVAL;
+        }
+#undef RAILS_BAMG_CASE
+        count_product();
+        return RAILS_OK;
     }
     int sweep_step(Sweep &s, double a, double b)
     {
         rails_panel *zin = s.z[s.at];
         if (!s.fused) {
             RAILS_TRY(product(s.A, 0, zin, s.q));
-            pass(s.g, s.slabs, k_cheb_pass, s.gvec, s.gs, a, b, s.q->d, s.r->d, s.d->d, zin->d);
+            if (s.bs)
+                pass(s.g, s.slabs, bj_cheb_pass(s.bs, false), s.ginv, a, b, (const double *)s.q->d, (const double *)s.r->d, s.d->d, zin->d);
+            else
+                pass(s.g, s.slabs, k_cheb_pass, s.gvec, s.gs, a, b, s.q->d, s.r->d, s.d->d, zin->d);
+            return RAILS_OK;
+        }
+        if (s.bs) {
+            s.at ^= 1;
+            RAILS_TRY(block_step(s, zin->d, a, b, s.z[s.at]->d));
+            it->last_fused++;
             return RAILS_OK;
         }
         int nce = 0;
@@ -436,7 +530,9 @@ struct Run {
             sweep_start(s, 2 * S + 1); // S steps here, 1 + S on the way up
             for (int k = 0; k < S; ++k) RAILS_TRY(sweep_step(s, s.a[k], s.b[k]));
             rails_panel *z = s.z[s.at];
-            if (s.fused) {
+            if (s.fused && s.bs) {
+                RAILS_TRY(block_residual(s, z->d));
+            } else if (s.fused) {
                 gather(lanes(k_amg_residual_csr<2, 8>, k_amg_residual_csr<4, 16>), s, z->d, (const double *)s.r->d, s.q->d);
             } else {
                 RAILS_TRY(product(s.A, 0, z, s.q));
@@ -547,7 +643,7 @@ int plan_call(Run &run, const char *who)
     rails_csr *A = it->A;
     const int ld = it->w[W_R]->ld;
     run.K = it->poly_degree;
-    run.amg = it->amg != 0;
+    run.amg = it->amg != 0 || it->block_amg != 0; // (either cycle: Run::vcycle on the sweeps made here)
     run.other = run.K > 0 || run.amg;
     run.sw[0] = Sweep{A, it->m, run.jac ? it->dinv : nullptr, it->defsign, it->w[W_R], {it->w[W_Z], it->w[W_Z2]}, it->w[W_D], it->w[W_Q]};
     if (run.amg) {
@@ -560,7 +656,15 @@ int plan_call(Run &run, const char *who)
             s.gs = 1.0;
             RAILS_REQUIRE(rails_cheb_coef(L.hi / it->amg_ratio, L.hi, it->amg_degree, &s.theta, s.a, s.b), "rails_iter: no smoother of degree %d on [%g, %g] (level %d)",
                           it->amg_degree, L.hi / it->amg_ratio, L.hi, (int)l);
-            s.fused = it->poly_fused && rails_cheb_fused_eligible(true, 0, L.n, ld);
+            if (H.b) { // the block hierarchy: G is the level's inverse diagonal blocks; whether the step is fused depends on the group (plan_group)
+                s.gvec = nullptr;
+                s.ginv = L.ginv;
+                s.bs = H.b;
+                RAILS_REQUIRE(rails_bsr_device_arrays(L.A, &s.mb, &s.max_brow, &s.browptr, &s.bcol, &s.bval), "%s: level %d of the block hierarchy is not a block-CSR handle", who, (int)l);
+                RAILS_REQUIRE(bj_cheb_init(s.bs, false), "%s: no block kernels for block size %d (RAILS_BJ_TABLE)", who, s.bs);
+                s.fused = false;
+            } else
+                s.fused = it->poly_fused && rails_cheb_fused_eligible(true, 0, L.n, ld);
         }
         return RAILS_OK;
     }
@@ -591,11 +695,23 @@ void plan_group(Run &run, int w)
     const rails_iter *it = run.it;
     const int ld = it->w[W_R]->ld;
     const int nl = run.amg ? (int)it->hier->lv.size() : 0;
-    for (int l = 0; l < std::max(1, nl); ++l) run.sw[l].g = rails_iter_pass_geom(run.sw[l].n, w, ld, &run.sw[l].slabs);
+    const int hb = run.amg ? it->hier->b : 0; // the block hierarchy: every pass of every level on slabs of whole block rows
+    for (int l = 0; l < std::max(1, nl); ++l) {
+        Sweep &s = run.sw[l];
+        s.g = hb ? rails_iter_pass_geom_block(s.n, w, ld, hb, &s.slabs) : rails_iter_pass_geom(s.n, w, ld, &s.slabs);
+        if (hb && nl) {
+            BsrFacts f;
+            f.b = hb; f.nc = w; f.mb = s.mb; f.max_brow = s.max_brow; f.num_cu = run.c->num_cu;
+            f.ldx = f.ldy = ld;
+            f.y_vec2 = ld % 2 == 0;
+            s.step = rails_bamg_step(f, it->poly_fused != 0);
+            s.fused = s.step.ok && s.step.fused;
+        }
+    }
     run.g = run.sw[0].g; // (level 0 has the operator's rows)
     run.nslab = run.sw[0].slabs;
     if (run.bj) run.g = rails_iter_pass_geom_block(it->m, w, ld, run.bj, &run.nslab); // every pass of the group, the point ones too
-    if (run.amg) run.gc = rails_iter_pass_geom(it->hier->n_coarse, w, ld, &run.slabs_c);
+    if (run.amg) run.gc = hb ? rails_iter_pass_geom_block(it->hier->n_coarse, w, ld, hb, &run.slabs_c) : rails_iter_pass_geom(it->hier->n_coarse, w, ld, &run.slabs_c);
 }
 
 } // namespace
@@ -768,6 +884,7 @@ extern "C" int rails_iter_set(rails_iter *it, const char *name, double value)
                       RAILS_CHEB_MAX_DEGREE);
         RAILS_REQUIRE(value == 0.0 || !it->amg, "rails_iter_set: poly_degree %g together with \"amg\": one preconditioner at a time", value);
         RAILS_REQUIRE(value == 0.0 || !it->block_jacobi, "rails_iter_set: poly_degree %g together with \"block_jacobi\": one preconditioner at a time", value);
+        RAILS_REQUIRE(value == 0.0 || !it->block_amg, "rails_iter_set: poly_degree %g together with \"block_amg\": one preconditioner at a time", value);
         RAILS_REQUIRE(value == 0.0 || it->method == RAILS_ITER_CG,
                       "rails_iter_set: poly_degree %g on a BiCGStab object: the polynomial preconditioner is for conjugate gradients (a real spectrum)", value);
         it->poly_degree = (int)value;
@@ -784,11 +901,15 @@ extern "C" int rails_iter_set(rails_iter *it, const char *name, double value)
             RAILS_REQUIRE(it->bj_dev, "rails_iter_set: \"block_jacobi\" 1 without blocks: install them first (rails_iter_block_jacobi)");
             RAILS_REQUIRE(it->poly_degree == 0, "rails_iter_set: \"block_jacobi\" together with poly_degree %d: one preconditioner at a time", it->poly_degree);
             RAILS_REQUIRE(!it->amg, "rails_iter_set: \"block_jacobi\" together with \"amg\": one preconditioner at a time");
+            RAILS_REQUIRE(!it->block_amg, "rails_iter_set: \"block_jacobi\" together with \"block_amg\": one preconditioner at a time");
         }
         it->block_jacobi = value != 0.0;
     } else if (n == "amg") {
         if (value != 0.0) RAILS_TRY(amg_check(it, "rails_iter_set"));
         it->amg = value != 0.0;
+    } else if (n == "block_amg") {
+        if (value != 0.0) RAILS_TRY(bamg_check(it, "rails_iter_set"));
+        it->block_amg = value != 0.0;
     } else if (n == "amg_degree") {
         RAILS_REQUIRE(value >= 0.0 && value <= 8.0 && value == std::floor(value), "rails_iter_set: amg_degree %g is not a whole number in 0 .. 8", value);
         it->amg_degree = (int)value;
@@ -806,7 +927,7 @@ extern "C" int rails_iter_set(rails_iter *it, const char *name, double value)
         it->amg_coarse = (int)value;
     } else {
         rails_set_error("rails_iter_set: no setting named '%s' (tolerance, max_iterations, jacobi, check_every, strict, poly_degree, poly_ratio, eig_max, poly_fused, amg, amg_degree, "
-                        "amg_ratio, amg_theta, amg_coarse, block_jacobi)", name);
+                        "amg_ratio, amg_theta, amg_coarse, block_jacobi, block_amg)", name);
         return RAILS_EINVAL;
     }
     return RAILS_OK;
@@ -856,6 +977,7 @@ extern "C" int rails_iter_block_jacobi(rails_ctx *c, rails_iter *it, int b, cons
     }
     RAILS_REQUIRE(it->poly_degree == 0, "rails_iter_block_jacobi: together with poly_degree %d: one preconditioner at a time", it->poly_degree);
     RAILS_REQUIRE(!it->amg, "rails_iter_block_jacobi: together with \"amg\": one preconditioner at a time");
+    RAILS_REQUIRE(!it->block_amg, "rails_iter_block_jacobi: together with \"block_amg\": one preconditioner at a time");
     const int64_t nb = m / be;
     const size_t n = (size_t)nb * be * be;
     std::vector<double> blocks, inv(n);
@@ -953,6 +1075,75 @@ extern "C" int rails_iter_amg_setup(rails_ctx *c, rails_iter *it)
     return RAILS_OK;
 }
 
+namespace {
+int hierarchy_info(const rails_iter *it, int block, int64_t *rows, int64_t *nnz, double *hi, int cap);
+}
+
+// Builds (or rebuilds) the block hierarchy from the block-CSR arrays the operator's handle keeps on the host (block_amg_host.h) and uploads
+// it: the level operators as block-CSR handles, P and R = P' as rectangular operators, the inverse diagonal blocks, the dense inverse.
+// Every refusal comes before any device work.
+extern "C" int rails_iter_block_amg_setup(rails_ctx *c, rails_iter *it)
+{
+    if (c) hipSetDevice(c->device);
+    RAILS_REQUIRE(c && it, "rails_iter_block_amg_setup: null argument");
+    RAILS_REQUIRE(c == it->ctx, "rails_iter_block_amg_setup: the object belongs to another context");
+    RAILS_TRY(bamg_check(it, "rails_iter_block_amg_setup"));
+    rails_csr *A = it->A;
+    int b = 0;
+    int64_t mb = 0;
+    const int64_t *browptr = nullptr;
+    const int32_t *bcol = nullptr;
+    const double *bval = nullptr;
+    RAILS_REQUIRE(rails_bsr_host_arrays(A, &b, &mb, &browptr, &bcol, &bval), "rails_iter_block_amg_setup: the block-CSR operator keeps no host copy");
+    const auto t0 = std::chrono::steady_clock::now();
+    rails_bamg_hierarchy h;
+    RAILS_TRY(rails_bamg_build_host(mb, b, browptr, bcol, bval, it->amg_theta, it->amg_coarse, &h));
+    const auto t1 = std::chrono::steady_clock::now();
+    amg_release(it); // (a refused rebuild leaves the hierarchy there was)
+    Amg *H = new Amg;
+    it->hier = H; // (released by amg_release, also when an upload below fails)
+    H->b = b;
+    H->n_coarse = h.coarse.mb * b;
+    H->coarse_nnz = h.coarse.nnzb() * b * b;
+    H->lv.resize(h.levels.size());
+    int rc = RAILS_OK;
+    hipError_t e = hipSuccess;
+    for (size_t l = 0; l < h.levels.size() && rc == RAILS_OK && e == hipSuccess; ++l) {
+        const rails_bamg_level &S = h.levels[l];
+        AmgLevel &L = H->lv[l];
+        L.n = S.A.mb * b;
+        L.nnz = S.A.nnzb() * b * b;
+        L.hi = S.hi;
+        if (l == 0)
+            L.A = A;
+        else
+            rc = rails_csr_create_bsr(c, S.A.mb, S.A.mb, b, S.A.browptr.data(), S.A.bcol.data(), S.A.bval.data(), &L.A);
+        if (rc == RAILS_OK) rc = rails_csr_create_rect(c, S.P.n_rows, S.P.n_cols, S.P.rowptr.data(), S.P.col.data(), S.P.val.data(), &L.P);
+        if (rc == RAILS_OK) rc = rails_csr_create_rect(c, S.R.n_rows, S.R.n_cols, S.R.rowptr.data(), S.R.col.data(), S.R.val.data(), &L.R);
+        if (rc == RAILS_OK) e = hipMalloc((void **)&L.ginv, S.ginv.size() * sizeof(double));
+        if (rc == RAILS_OK && e == hipSuccess) e = hipMemcpy(L.ginv, S.ginv.data(), S.ginv.size() * sizeof(double), hipMemcpyHostToDevice);
+    }
+    if (rc == RAILS_OK && e == hipSuccess) e = hipMalloc((void **)&H->Ainv, h.coarse_inv.size() * sizeof(double));
+    if (rc == RAILS_OK && e == hipSuccess) e = hipMemcpy(H->Ainv, h.coarse_inv.data(), h.coarse_inv.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (rc == RAILS_OK && e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (rc != RAILS_OK || e != hipSuccess) {
+        if (rc == RAILS_OK) rails_set_error("rails_iter_block_amg_setup: device allocation or upload failed: %s", hipGetErrorString(e));
+        amg_release(it);
+        return rc != RAILS_OK ? rc : RAILS_EHIP;
+    }
+    H->host_seconds = std::chrono::duration<double>(t1 - t0).count();
+    H->upload_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+    return RAILS_OK;
+}
+
+// rails_iter_amg_info's conventions on the block hierarchy: rows, scalar entries (blocks times b^2) and the smoother's bound per matrix,
+// then the two trailing entries.  0 when no block hierarchy has been built.
+extern "C" int rails_iter_block_amg_info(const rails_iter *it, int64_t *rows, int64_t *nnz, double *hi, int cap)
+{
+    RAILS_REQUIRE(it && cap >= 0, "rails_iter_block_amg_info: bad argument");
+    return hierarchy_info(it, 1, rows, nnz, hi, cap);
+}
+
 // The hierarchy by its matrices, the last (dense) one included: rows, entries and the Gershgorin bound hi of the smoother's interval (0 for
 // the last) of matrix l in rows[l], nnz[l], hi[l], l < n.  Two more entries where cap allows: [n] the last call's cycles, the products
 // inside them (with A_l, P and R) and the launches of the object's own kernels inside them; [n + 1] the set-up's host time and its upload
@@ -961,8 +1152,16 @@ extern "C" int rails_iter_amg_setup(rails_ctx *c, rails_iter *it)
 extern "C" int rails_iter_amg_info(const rails_iter *it, int64_t *rows, int64_t *nnz, double *hi, int cap)
 {
     RAILS_REQUIRE(it && cap >= 0, "rails_iter_amg_info: bad argument");
+    return hierarchy_info(it, 0, rows, nnz, hi, cap);
+}
+
+namespace {
+
+// rails_iter_amg_info (block 0) and rails_iter_block_amg_info (block 1) on the hierarchy of their kind
+int hierarchy_info(const rails_iter *it, int block, int64_t *rows, int64_t *nnz, double *hi, int cap)
+{
     const Amg *H = it->hier;
-    if (!H) return 0;
+    if (!H || (H->b != 0) != (block != 0)) return 0;
     const int n = (int)H->lv.size() + 1;
     double total = (double)H->coarse_nnz;
     for (const AmgLevel &L : H->lv) total += (double)L.nnz;
@@ -993,12 +1192,13 @@ extern "C" int rails_iter_amg_info(const rails_iter *it, int64_t *rows, int64_t 
     return n;
 }
 
-namespace {
-
 // before a solve or an application with "amg" on: the hierarchy when there is none yet, the level panels at the work panels' width
 int amg_prepare(rails_ctx *c, rails_iter *it)
 {
-    if (!it->hier) RAILS_TRY(rails_iter_amg_setup(c, it));
+    if (it->block_amg) {
+        if (!it->hier || !it->hier->b) RAILS_TRY(rails_iter_block_amg_setup(c, it));
+    } else if (!it->hier || it->hier->b)
+        RAILS_TRY(rails_iter_amg_setup(c, it));
     return amg_grow(c, it);
 }
 
@@ -1024,7 +1224,7 @@ int begin_call(rails_ctx *c, rails_iter *it, const char *who, bool solve, int tr
     if (solve) it->last.clear();
     if (nc == 0) return RAILS_OK;
     RAILS_TRY(grow_work(c, it, std::min(nc, RAILS_ITER_GROUP), also));
-    if (it->amg) RAILS_TRY(amg_prepare(c, it));
+    if (it->amg || it->block_amg) RAILS_TRY(amg_prepare(c, it));
     if (solve) RAILS_TRY(grow_cols(c, it, nc));
     run.c = c;
     run.it = it;

@@ -303,6 +303,8 @@ int rails_bsr_apply(rails_ctx *c, rails_csr *A, int trans, const rails_panel *X,
 void rails_bsr_release(rails_csr *A);
 // ... and the host copy the handle keeps: block size, block rows, the three arrays (false: not a block-CSR handle)
 bool rails_bsr_host_arrays(const rails_csr *A, int *b, int64_t *mb, const int64_t **browptr, const int32_t **bcol, const double **bval);
+// ... and its device arrays with the block rows and the longest block row (false: not a block-CSR handle)
+bool rails_bsr_device_arrays(const rails_csr *A, int64_t *mb, int64_t *max_brow, const int64_t **browptr, const int32_t **bcol, const double **bval);
 // dense_gram.hip: partial Gram into device memory (no host copy / all-reduce): C_dev (a x b col-major, ldc = a)
 int rails_gram_dev(rails_ctx *ctx, const double *X, int ldx, const double *Y, int ldy, int64_t m, int a, int b,
                    double *C_dev);

@@ -36,6 +36,9 @@ class IterativeInverse:
     blocks instead of the diagonal's, for a matrix with b unknowns per cell whose coupling inside a cell is the stiff part.  True: the
     blocks of the operator -- a block-CSR operator's own, or for a CSR operator those of block_size=b; an array of shape (m / b, b, b):
     these blocks (any operator).  See block_jacobi().
+    block_amg=True (conjugate gradients on a block-CSR operator, one GPU, not together with poly_degree, amg or block_jacobi):
+    precondition with one V-cycle of smoothed aggregation on the cells, G the inverses of the diagonal blocks of every level; amg_degree,
+    amg_ratio, amg_theta and amg_coarse serve it as they serve amg.  The hierarchy is built by the first solve, or by block_amg_setup().
 
     On a row-partitioned context (Context.set_partition with more than one rank) A is the rank's operator wrapper with its halo plan set,
     the all-reduce hook or the communicator is installed before the object is made, and making it, set(), solve() and precondition() are
@@ -44,7 +47,7 @@ class IterativeInverse:
 
     def __init__(self, ctx, A, method="auto", tol=1e-10, maxit=1000, jacobi=True, strict=False, diag=None, check_every=None, poly_degree=0,
                  poly_ratio=None, eig_max=None, amg=False, amg_degree=None, amg_ratio=None, amg_theta=None, amg_coarse=None, block_jacobi=False,
-                 block_size=0):
+                 block_size=0, block_amg=False):
         self.ctx = ctx
         self._owned = None
         if isinstance(A, HipOperatorWrapper):
@@ -103,6 +106,8 @@ class IterativeInverse:
             self.block_jacobi(b=block_size)
         elif block_jacobi is not False and block_jacobi is not None:
             self.block_jacobi(block_jacobi, b=block_size)
+        if block_amg:
+            self.set("block_amg", 1)
         oh = C.c_void_p()
         check(ctx.lib.rails_csr_create_iter(ctx.h, h, C.byref(oh)), "rails_csr_create_iter")
         self.op = HipOperatorWrapper(ctx, None, None, None, _handle=_Handle(ctx, oh))
@@ -113,7 +118,7 @@ class IterativeInverse:
         off; conjugate gradients only), "poly_ratio" (hi / lo of its interval, above 1), "eig_max" (hi; 0: the Gershgorin bound),
         "poly_fused" (0: never the fused step kernel); the multigrid preconditioner: "amg" (1: on), "amg_degree" (0 .. 8), "amg_ratio"
         (above 1), "amg_theta" (in [0, 1)), "amg_coarse" (1 .. 1024); "block_jacobi" (1: the installed diagonal blocks precondition, 0: "jacobi"
-        decides again; block_jacobi() installs them) (rails_iter_set)"""
+        decides again; block_jacobi() installs them); "block_amg" (1: the block multigrid cycle, with the "amg_..." settings) (rails_iter_set)"""
         check(self.ctx.lib.rails_iter_set(self.h, name.encode(), float(value)), "rails_iter_set")
 
     def solve(self, X, Y=None, trans=False):
@@ -165,14 +170,26 @@ class IterativeInverse:
         check(self.ctx.lib.rails_iter_amg_setup(self.ctx.h, self.h), "rails_iter_amg_setup")
         return self.amg_info()
 
+    def block_amg_setup(self):
+        """builds (or rebuilds) the block multigrid hierarchy now and uploads it (rails_iter_block_amg_setup); returns block_amg_info()"""
+        check(self.ctx.lib.rails_iter_block_amg_setup(self.ctx.h, self.h), "rails_iter_block_amg_setup")
+        return self.block_amg_info()
+
+    def block_amg_info(self):
+        """amg_info() of the block hierarchy (rails_iter_block_amg_info): "nnz" counts scalar entries, "hi" is the bound on G A"""
+        return self._hierarchy_info(self.ctx.lib.rails_iter_block_amg_info, "rails_iter_block_amg_info")
+
     def amg_info(self):
         """the hierarchy and the last call (rails_iter_amg_info): "levels" (matrices, the dense last one included; 0: none built), per
         matrix "rows", "nnz" and "hi", "operator_complexity", the last call's "cycles", "cycle_products" and "cycle_launches", and the
         "host_seconds" and "upload_seconds" of the set-up"""
+        return self._hierarchy_info(self.ctx.lib.rails_iter_amg_info, "rails_iter_amg_info")
+
+    def _hierarchy_info(self, fn, who):
         cap = 20
         rows, nnz, hi = (C.c_int64 * cap)(), (C.c_int64 * cap)(), (C.c_double * cap)()
-        n = self.ctx.lib.rails_iter_amg_info(self.h, rows, nnz, hi, cap)
-        check(min(n, 0), "rails_iter_amg_info")
+        n = fn(self.h, rows, nnz, hi, cap)
+        check(min(n, 0), who)
         if n == 0:
             return {"levels": 0, "rows": [], "nnz": [], "hi": [], "operator_complexity": 0.0, "cycles": 0, "cycle_products": 0, "cycle_launches": 0,
                     "host_seconds": 0.0, "upload_seconds": 0.0}

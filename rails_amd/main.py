@@ -4,7 +4,7 @@
                                [--eigs K] [--variance FILE] [--pairs FILE [--pairs-out FILE]]
                                [--maps R1,R2,... [--correlation] [--maps-out FILE.mtx]] [--sparse-B] [--warm-start V.mtx | --start-space S.mtx] [--restart-upon-start]
                                [--inverse {lu,cg,bicgstab,iterative}] [--inverse-tol T] [--inverse-poly K] [--inverse-amg] [--block-size b]
-                               [--inverse-block-jacobi]
+                               [--inverse-block-jacobi] [--inverse-block-amg]
     python -m torch.distributed.run --nproc-per-node N -m rails_amd.main ... [--backend {nccl,gloo}] [--one-device]
                                                                                   (one rank per GPU, rows partitioned)
 
@@ -43,6 +43,13 @@ says little).  The driver prints b, the number of blocks and, after the solve, t
 took (the solver reaches the inverse through a callback handle that notes them); it refuses the flag without `--block-size`, together
 with `--inverse-poly` or `--inverse-amg`, with the sparse LU and on more than one rank, and says so when "Projection method" 1 makes it
 moot.
+
+`--inverse-block-amg` (with `--block-size b` and a conjugate-gradients inverse, `--inverse cg` or `iterative` on a symmetric matrix)
+iterates on the block-CSR operator as well and preconditions with one V-cycle of block multigrid
+(rails_amd.IterativeInverse(block_amg=True): for a diffusion-dominated system on a fine grid, where block Jacobi's iteration count grows
+with the grid).  The driver prints b, the rows of the levels, the operator complexity and the set-up time, and after the solve the cycles,
+products and launches of the last application; it refuses the flag without `--block-size`, together with `--inverse-poly`,
+`--inverse-amg` or `--inverse-block-jacobi`, with the sparse LU or BiCGStab and on more than one rank.
 
 `--backend gloo` runs the collectives through torch.distributed's gloo backend, staged through host memory, and `--one-device` puts every
 rank on device 0: a rehearsal of the multi-process path on a machine with one GPU, as bench.py has it.
@@ -173,6 +180,9 @@ def main(argv=None):
     ap.add_argument("--inverse-block-jacobi", action="store_true", help="build an iterative inverse on the block-CSR operator of --block-size b and precondition it with "
                                                                       "the inverses of the b x b diagonal blocks (one rank; not together with --inverse-poly or "
                                                                       "--inverse-amg)")
+    ap.add_argument("--inverse-block-amg", action="store_true", help="build a conjugate-gradients inverse on the block-CSR operator of --block-size b and precondition "
+                                                                   "it with one V-cycle of block multigrid (one rank; not together with --inverse-poly, "
+                                                                   "--inverse-amg or --inverse-block-jacobi)")
     ap.add_argument("--block-size", type=int, default=0, metavar="b", help="keep A (and M) as block-CSR operators of b x b blocks, 2 .. 8; the rows must be a multiple of b; "
                                                                           "one rank")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend of a run on several ranks; gloo = rehearsal of the "
@@ -197,6 +207,22 @@ def main(argv=None):
         if args.inverse == "lu":
             raise SystemExit("--inverse-block-jacobi: the block-Jacobi preconditioner is for an iterative inverse (--inverse cg, bicgstab or iterative), and the "
                              "inverse chosen is a sparse LU")
+    if args.inverse_block_amg:  # what the arguments alone decide, before anything is read or built
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit("--inverse-block-amg on %s ranks: the block multigrid preconditioner is single GPU" % os.environ["WORLD_SIZE"])
+        if not args.block_size:
+            raise SystemExit("--inverse-block-amg needs --block-size b: the hierarchy is built from the block-CSR operator")
+        if args.inverse_poly:
+            raise SystemExit("--inverse-block-amg together with --inverse-poly %d: one preconditioner at a time" % args.inverse_poly)
+        if args.inverse_amg:
+            raise SystemExit("--inverse-block-amg together with --inverse-amg: one preconditioner at a time")
+        if args.inverse_block_jacobi:
+            raise SystemExit("--inverse-block-amg together with --inverse-block-jacobi: one preconditioner at a time")
+        if args.inverse == "lu":
+            raise SystemExit("--inverse-block-amg: the block multigrid preconditioner is for a conjugate-gradients inverse (--inverse cg or iterative), and the "
+                             "inverse chosen is a sparse LU")
+        if args.inverse == "bicgstab":
+            raise SystemExit("--inverse-block-amg: the block multigrid preconditioner is for conjugate gradients, and the inverse chosen is bicgstab")
 
     import torch
 
@@ -362,6 +388,10 @@ def main(argv=None):
         _log(rank, "--inverse-block-jacobi has no effect: 'Projection method' %g applies no inverse" % method)
     if args.inverse_block_jacobi and schur is not None:  # (the other refusals of the flag need the arguments alone: above)
         raise SystemExit("--inverse-block-jacobi: a Schur-complement problem keeps the sparse LU inverse of its Schur operator")
+    if args.inverse_block_amg and method <= 1:
+        _log(rank, "--inverse-block-amg has no effect: 'Projection method' %g applies no inverse" % method)
+    if args.inverse_block_amg and schur is not None:
+        raise SystemExit("--inverse-block-amg: a Schur-complement problem keeps the sparse LU inverse of its Schur operator")
     if method > 1:
         if world > 1 and args.inverse == "lu":
             raise SystemExit("'Projection method' %g on %d ranks: the sparse LU inverse runs on one rank; use --inverse iterative (or cg, bicgstab), "
@@ -373,10 +403,11 @@ def main(argv=None):
         elif args.inverse == "lu":
             inverse = rails_amd.SparseLU(ctx, (rowptr, col.astype(np.int32), val))
             what = "a sparse LU of A"
-        elif world > 1 or args.inverse_block_jacobi:
+        elif world > 1 or args.inverse_block_jacobi or args.inverse_block_amg:
             # the rank's own row block with its halo plan; the all-reduce hook is in place (above).  Symmetry is a property of the whole
             # matrix, which every rank has read: every rank reaches the same method.  With --inverse-block-jacobi (one rank): the
-            # block-CSR operator itself, whose diagonal blocks precondition
+            # block-CSR operator itself, whose diagonal blocks precondition; with --inverse-block-amg the same handle, whose blocks the
+            # hierarchy is built from
             how = args.inverse
             if how == "iterative":
                 import scipy.sparse as sp
@@ -397,6 +428,11 @@ def main(argv=None):
                 raise SystemExit("--inverse-amg: the multigrid preconditioner is for conjugate gradients, and the inverse chosen is %s" % inverse.method)
             inverse.set("amg", 1)
             amg = inverse.amg_setup()
+        if isinstance(inverse, rails_amd.IterativeInverse) and args.inverse_block_amg:
+            if inverse.method != "cg":
+                raise SystemExit("--inverse-block-amg: the block multigrid preconditioner is for conjugate gradients, and the inverse chosen is %s" % inverse.method)
+            inverse.set("block_amg", 1)
+            bamg = inverse.block_amg_setup()
         if isinstance(inverse, rails_amd.IterativeInverse) and args.inverse_block_jacobi:
             bj = inverse.block_jacobi()
             bj_first = {}
@@ -414,11 +450,14 @@ def main(argv=None):
             solver.set_inverse(inverse)
         if isinstance(inverse, rails_amd.IterativeInverse):
             _log(rank, "Projection method %g: A^-1 is an iterative solve on the device, method %s, %s, tolerance %g" % (
-                method, inverse.method, "block Jacobi" if args.inverse_block_jacobi else "Jacobi", args.inverse_tol))
+                method, inverse.method, "block Jacobi" if args.inverse_block_jacobi else "block multigrid" if args.inverse_block_amg else "Jacobi", args.inverse_tol))
             if args.inverse_poly:
                 _log(rank, "its preconditioner: a Chebyshev polynomial of degree %d in the Jacobi-scaled matrix" % args.inverse_poly)
             if args.inverse_block_jacobi:
                 _log(rank, "its preconditioner: block Jacobi on the block-CSR operator, b = %d, %d blocks" % (bj["b"], bj["blocks"]))
+            if args.inverse_block_amg:
+                _log(rank, "its preconditioner: a block multigrid V-cycle on the block-CSR operator, b = %d, %d levels of %s rows, operator complexity %.2f, set up in %.3f s" % (
+                    args.block_size, bamg["levels"], " / ".join(str(r) for r in bamg["rows"]), bamg["operator_complexity"], bamg["host_seconds"] + bamg["upload_seconds"]))
             if args.inverse_amg:
                 _log(rank, "its preconditioner: a smoothed-aggregation multigrid V-cycle, %d levels of %s rows, operator complexity %.2f, set up in %.3f s" % (
                     amg["levels"], " / ".join(str(r) for r in amg["rows"]), amg["operator_complexity"], amg["host_seconds"] + amg["upload_seconds"]))
@@ -448,6 +487,10 @@ def main(argv=None):
         if args.inverse_poly:  # what the object itself counted in its last solve, not what was asked for
             _log(rank, "its last solve: %d applications of the polynomial, %d products with A, %d of them in fused steps" % (
                 st["poly_applications"], st["products"], st["fused_launches"]))
+        if args.inverse_block_amg:
+            bamg = inverse.block_amg_info()
+            _log(rank, "its last solve: %d inner iterations at most, %d block multigrid cycles, %d products and %d launches inside them" % (
+                st["max_iterations_of_a_column"], bamg["cycles"], bamg["cycle_products"], bamg["cycle_launches"]))
         if args.inverse_amg:
             amg = inverse.amg_info()
             _log(rank, "its last solve: %d inner iterations at most, %d multigrid cycles, %d products and %d launches inside them" % (

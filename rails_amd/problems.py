@@ -164,6 +164,58 @@ def block_coupled7(nx, ny, nz, b, spread, skew=0.0, seed=0):
     return (indptr, indices, data), (rowptr, col, val)
 
 
+def block_diffusion7(nx, ny, nz, b, spread, reaction, seed=0):
+    """7-point grid of b unknowns per cell whose coupling between the cells is the stiff part: the matrix -(L (x) K + reaction *
+    blockdiag(C_i)), symmetric negative definite.  L is the 7-point graph Laplacian of block_coupled7 (6 in every row, -1 per
+    neighbour); K = Q diag(10^U(0, log10 spread)) Q' is one symmetric positive definite b x b block and C_i = Q_i diag(10^U(0, log10
+    spread)) Q_i' one per cell, every Q from a QR of a standard normal block.  Drawn from default_rng(seed) in that order: the normal
+    blocks of all cells, the exponents of all cells, K's normal block, K's exponents.  Block Jacobi removes the stiffness inside a cell
+    and its iteration count still grows with the grid; the test matrix of the block multigrid preconditioner.
+    Returns the two-tuple of block_stencil7: ((indptr, indices, data[nnzb, b, b]), (rowptr, col, val))."""
+    mb = nx * ny * nz
+    g = np.random.default_rng(seed)
+    Q = np.linalg.qr(g.standard_normal((mb, b, b)))[0]
+    lam = 10.0 ** g.uniform(0.0, np.log10(spread), (mb, b))
+    Qk = np.linalg.qr(g.standard_normal((b, b)))[0]
+    lamk = 10.0 ** g.uniform(0.0, np.log10(spread), b)
+    Cd = (Q * lam[:, None, :]) @ Q.transpose(0, 2, 1)
+    Cd = 0.5 * (Cd + Cd.transpose(0, 2, 1))
+    K = (Qk * lamk[None, :]) @ Qk.T
+    K = 0.5 * (K + K.T)
+    idx = np.arange(mb, dtype=np.int64)
+    x = idx % nx
+    y = (idx // nx) % ny
+    z = idx // (nx * ny)
+    bcols = np.full((mb, 7), -1, dtype=np.int64)
+    specs = [(z > 0, -nx * ny), (y > 0, -nx), (x > 0, -1), (None, 0), (x < nx - 1, 1), (y < ny - 1, nx), (z < nz - 1, nx * ny)]
+    for s, (cond, off) in enumerate(specs):
+        if cond is None:
+            bcols[:, s] = idx
+        else:
+            bcols[cond, s] = idx[cond] + off
+    mask = bcols >= 0
+    counts = mask.sum(1)
+    indptr = np.zeros(mb + 1, dtype=np.int64)
+    np.cumsum(counts, out=indptr[1:])
+    indices = bcols[mask].astype(np.int32)
+    brow = np.repeat(idx, counts)
+    data = np.empty((indices.size, b, b))
+    data[indices != brow] = K  # L's entry is -1 off the diagonal; the whole matrix is negated
+    centre = indices == brow
+    data[centre] = -(6.0 * K + reaction * Cd)
+    rowptr = np.zeros(mb * b + 1, dtype=np.int64)
+    np.cumsum(np.repeat(counts, b) * b, out=rowptr[1:])
+    col = np.empty(indices.size * b * b, dtype=np.int32)
+    val = np.empty(indices.size * b * b)
+    within = np.arange(indices.size) - indptr[brow]
+    for r in range(b):
+        at = rowptr[brow * b + r] + within * b
+        for s in range(b):
+            col[at + s] = indices * b + s
+            val[at + s] = data[:, r, s]
+    return (indptr, indices, data), (rowptr, col, val)
+
+
 def banded_random(m, nnz_row=27, bandwidth=4096, seed=0):
     """nnz_row entries per row incl. the diagonal; off-diagonal columns uniform in |j - i| <= bandwidth
     (reflected at the boundary), values U(0,1); diagonal = -(row sum + 1).  Config C3 (primary)."""
