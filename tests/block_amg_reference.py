@@ -19,6 +19,7 @@ import scipy.sparse as sp
 
 import amg_reference as M
 import block_jacobi_reference as J
+import bsr_reference as K
 import cheb_reference as C
 import iter_reference as R
 
@@ -291,21 +292,7 @@ def pcg(A, Bm, prec, tol=1e-8, maxit=1000):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the launch decision
-def bsr_choice(b, nc, mb, max_brow, num_cu=256):
-    """bsr_choice.h: (lpr, threads, rpg, rows, bpx, grid, all_staged) or None"""
-    if b < 2 or b > 8 or nc < 1 or mb < 1 or max_brow < 0:
-        return None
-    lpr = 8 if nc <= 16 else 16 if nc <= 32 else 32
-    threads = 256 if b <= 4 else 128 if b <= 6 else 64
-    groups, cap = threads // lpr, 4096 // (b * b)
-    rpg = 1
-    while rpg < 4 and groups * 2 * rpg * max(max_brow, 1) <= cap and (mb + groups * 2 * rpg - 1) // (groups * 2 * rpg) >= 2 * max(num_cu, 1):
-        rpg *= 2
-    rows = groups * rpg
-    bpx = ((mb + rows - 1) // rows + 7) // 8
-    if bpx * 8 > 0x7fffffff:
-        return None
-    return lpr, threads, rpg, rows, bpx, bpx * 8, rows * max_brow <= cap
+bsr_choice = K.bsr_choice  # bsr_choice.h, restated once: tests/bsr_reference.py
 
 
 def rows_ok(m, b):

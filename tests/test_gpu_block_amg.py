@@ -4,12 +4,14 @@ k_cheb_step_bsr, k_amg_residual_bsr, k_cheb_init_bj, k_cheb_pass_bj on bsr_row_g
 restatement of tests/block_amg_reference.py: one cycle against a longdouble evaluation on the shapes at which the kernels take their
 different paths, the fused step against the unfused one bit for bit, converged solves against the restatement's iteration counts and
 against block Jacobi, "block_amg" 0 bit for bit, determinism, the counts per cycle of DESIGN.md section 16, the refusals, and one
-Lyapunov solve."""
+Lyapunov solve.  Three larger problems put the fine level's fused step and residual at 2 and 4 block rows per lane group
+(tests/bsr_reference.py::shape_for; tests/test_gpu_bsr_rounds.py has the product itself there)."""
 import numpy as np
 import pytest
 
 import block_amg_reference as B
 import block_jacobi_reference as BJ
+import bsr_reference as K
 import iter_reference as R
 
 pytestmark = pytest.mark.gpu
@@ -26,6 +28,11 @@ SENTINEL = 7.25
 ONES = ["one%d" % b for b in B.J.BS]
 SMALL = ["d4x4x3b%dc%d" % (b, 8 * b) for b in B.J.BS]
 PROBLEMS = ONES + SMALL + ["d6x6x6b3", "d5x5x4b6", "d8x8x8b4", "d4x4x3b3c24p", "long8"]
+# Fine levels with enough block rows for more than one round of the shared block-row body, at one degree: {width: block rows per lane group}
+# of k_cheb_step_bsr / k_amg_residual_bsr<b, 8 lanes up to 16 columns, 16 above>.  The names are the grids for 256 compute units (32768,
+# 16900 and 4096 cells; at b = 8 a workgroup is one wave of four lane groups); on another device rounds_problem sizes the grid instead.
+ROUNDS = {"d32x32x32b2": {16: 2, 15: 2, 17: 4, 32: 4}, "d26x26x25b3": {17: 2}, "d16x16x16b8": {17: 2, 32: 2}}
+ROUNDS_DEGREES = (1,)
 
 
 @pytest.fixture(scope="module")
@@ -38,6 +45,7 @@ def ctx():
 
 
 _inverses = {}
+_operators = {}
 
 
 def operator(ctx, tag):
@@ -53,7 +61,8 @@ def inverse(ctx, tag):
     import rails_amd
 
     if tag not in _inverses:
-        _inverses[tag] = rails_amd.IterativeInverse(ctx, operator(ctx, tag), method="cg", tol=TOL)
+        _operators[tag] = operator(ctx, tag)
+        _inverses[tag] = rails_amd.IterativeInverse(ctx, _operators[tag], method="cg", tol=TOL)
     inv = _inverses[tag]
     for name, value in (("tolerance", TOL), ("jacobi", 1), ("max_iterations", 1000), ("strict", 0), ("check_every", 8), ("poly_degree", 0), ("block_jacobi", 0),
                         ("poly_fused", 1), ("amg_degree", B.DEGREE), ("amg_ratio", B.RATIO), ("amg_theta", B.THETA), ("amg_coarse", B.problem(tag)[1]),
@@ -68,6 +77,7 @@ def _close_inverses(ctx):
     for inv in _inverses.values():
         inv.close()
     _inverses.clear()
+    _operators.clear()
 
 
 def window(mv, c0, nc):
@@ -88,6 +98,20 @@ def cycle_counts(tag, S):
 
 def block_size(tag):
     return B.hierarchy(tag)[1]["b"]
+
+
+def rounds_problem(tag, num_cu):
+    """the problem of ROUNDS[tag] for a device of num_cu compute units: the named grid where its cell count gives every width its rounds
+    (256 compute units), else the most cubic grid nx = ny >= nz that does"""
+    b = int(tag.split("b")[1])
+    lo = max(K.shape_for(b, K.lanes(nc), rpg, num_cu)[0] for nc, rpg in ROUNDS[tag].items())
+    hi = min(K.shape_for(b, K.lanes(nc), 2 * rpg, num_cu)[0] for nc, rpg in ROUNDS[tag].items() if rpg < 4)
+    nx, ny, nz = (int(v) for v in tag[1:].split("b")[0].split("x"))
+    if not lo <= nx * ny * nz < hi:
+        nx = ny = int(np.ceil(lo ** (1.0 / 3.0)))
+        nz = -(-lo // (nx * ny))
+    assert lo <= nx * ny * nz < hi, (tag, num_cu, lo, hi)
+    return "d%dx%dx%db%d" % (nx, ny, nz, b)
 
 
 def rule_fuses(tag, nc, ld=34):
@@ -165,17 +189,27 @@ def precondition_both_ways(ctx, inv, Xm):
     return full, Yh[:, YC0:YC0 + nc].copy()
 
 
-@pytest.mark.parametrize("tag", PROBLEMS)
+@pytest.mark.parametrize("tag", PROBLEMS + list(ROUNDS))
 def test_one_cycle_against_longdouble_fused_and_unfused(ctx, tag):
     """items 2, 3 and 7: the cycle within the restatement's bound at every degree and width, through full panels and windows bit for
-    bit; the fused and the unfused step give the same bits; launches and products per cycle and level are section 16's"""
+    bit; the fused and the unfused step give the same bits; launches and products per cycle and level are section 16's.  The problems
+    of ROUNDS at their own widths and one degree: the fine level's launch has the block rows per lane group named there, by the restated
+    rule at the context's compute units and by what the handle reports of the unfused step's product, the same launch."""
+    degrees, widths, rounds = DEGREES, WIDTHS, ROUNDS.get(tag)
+    if rounds:
+        num_cu = ctx.lib.rails_ctx_num_cu(ctx.h)
+        tag, degrees, widths = rounds_problem(tag, num_cu), ROUNDS_DEGREES, tuple(rounds)
+        fine = B.hierarchy(tag)[1]["levels"][0]["bsr"][0]
+        fine_mb, fine_longest = len(fine) - 1, int(np.diff(fine).max())
+        for nc in widths:
+            assert K.predicted_stats(block_size(tag), nc, fine_mb, fine_longest, num_cu)["rpg"] == rounds[nc], (tag, nc, num_cu)
     inv = inverse(ctx, tag)
     worst = 0.0
-    for S in DEGREES:
+    for S in degrees:
         Xall, Zall, ball = expected(tag, S)
         inv.set("amg_degree", S)
         launches, products, fused_steps = cycle_counts(tag, S)
-        for nc in WIDTHS:
+        for nc in widths:
             Xm, Zl, bound = np.ascontiguousarray(Xall[:, :nc]), Zall[:, :nc], ball[:nc]
             groups = (nc + 31) // 32
             got = {}
@@ -193,6 +227,10 @@ def test_one_cycle_against_longdouble_fused_and_unfused(ctx, tag):
                 worst = max(worst, (err.max(0) / bound).max())
                 assert np.all(err <= bound[None, :]), (tag, nc, S, fused, (err.max(0) / bound).max())
                 got[fused] = full
+                if rounds and not fused:  # the last product on the handle: the fine level's, in the second sweep
+                    st, want = _operators[tag].bsr_stats(), K.predicted_stats(block_size(tag), nc, fine_mb, fine_longest, num_cu)
+                    assert {k: st[k] for k in want} == want and st["rpg"] == rounds[nc], (st, want)
+                    print("problem %s, %d columns: the fine level's product reports rpg %d, all_staged %s" % (tag, nc, st["rpg"], st["all_staged"]))
             assert np.array_equal(got[1], got[0]), (tag, nc, S)  # the product is the row-gather order either way, the epilogue one function
     Xm, Zl, _ = expected(tag, 1)
     assert np.all(np.sign((Xm * Zl).sum(0)) == B.hierarchy(tag)[1]["defsign"])  # the cycle has the operator's own sign

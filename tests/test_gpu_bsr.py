@@ -3,7 +3,10 @@
 The reference everywhere is the expanded CSR matrix -- every entry of every block, zeros included, in stored order -- on a handle forced to
 the row-gather kernel (set_variant(3)), and the comparison is np.array_equal on the bits: the block-CSR product makes the same fused
 multiply-adds in the same order.  Only the magnitude test uses a bound, the one tests/test_gpu_kernels.py has for the row kernels
-(1e-14 * sqrt(entries per row) * 4, there on the largest entry, here also on the Frobenius norms)."""
+(1e-14 * sqrt(entries per row) * 4, there on the largest entry, here also on the Frobenius norms).
+
+Every shape here is small enough for one round of block rows per lane group (rpg == 1, asserted below where it matters).  The launches with
+2 and 4 rounds need thousands of block rows; tests/test_gpu_bsr_rounds.py has them, against an int64 host product instead of a kernel."""
 import ctypes as C
 import json
 import os
