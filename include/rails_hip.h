@@ -221,7 +221,7 @@ int rails_lu_stats(const rails_lu *lu, int64_t *info, int cap);
  * (HipOperatorWrapper, rails_solver_create, rails_solver_set_inverse).  The caller keeps the rails_lu alive while the handle is used. */
 int rails_csr_create_lu(rails_ctx *ctx, rails_lu *lu, rails_csr **out);
 
-/* ---- iterative solve as a library object (rails_amd/csrc/itsolve.hip, iter_scalars.h) --------------------------------------------------
+/* ---- iterative solve as a library object (rails_amd/csrc/itsolve.hip, iter_setup.hip, iter_hierarchy.hip, iter_precond.h, iter_scalars.h) --------------------------------------------------
  * The same operator A^-1 without a factorisation: the reference asks for no more than an approximate inverse (matlab/RAILSsolver.m:19-23,
  * opts.Ainv: "This can be approximate"), and at the sizes where the fill of L and U rules a sparse LU out an iteration on the device is
  * the only A^-1 there is.  A is any square operator handle rails_spmm accepts (a CSR matrix, a callback operator such as the Schur

@@ -1,4 +1,4 @@
-// amg_host.h -- the host set-up of the smoothed-aggregation multigrid preconditioner of the iterative A^-1 operator (itsolve.hip, "amg";
+// amg_host.h -- the host set-up of the smoothed-aggregation multigrid preconditioner of the iterative A^-1 operator (iter_hierarchy.hip: rails_iter_amg_setup, "amg";
 // DESIGN.md section 16).  No HIP in here: the library compiles amg_host.cpp for the host, tests/cpp/amg_host.cpp stands alone on it, and
 // tests/amg_reference.py restates it in numpy/scipy.
 //

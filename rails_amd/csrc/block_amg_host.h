@@ -1,4 +1,4 @@
-// block_amg_host.h -- the host set-up of the block multigrid preconditioner of the iterative A^-1 operator (itsolve.hip, "block_amg";
+// block_amg_host.h -- the host set-up of the block multigrid preconditioner of the iterative A^-1 operator (iter_hierarchy.hip: rails_iter_block_amg_setup, "block_amg";
 // DESIGN.md section 19): smoothed aggregation on the cells of a block-CSR operator with b unknowns per cell.  No HIP in here: the library
 // compiles block_amg_host.cpp for the host, tests/cpp/block_amg_host.cpp stands alone on it, and tests/block_amg_reference.py restates it
 // in numpy/scipy.

@@ -1,4 +1,4 @@
-// block_jacobi_host.h -- the host part of the block-Jacobi preconditioner of the iterative A^-1 operator (itsolve.hip, DESIGN.md section
+// block_jacobi_host.h -- the host part of the block-Jacobi preconditioner of the iterative A^-1 operator (iter_hierarchy.hip: rails_iter_block_jacobi; DESIGN.md section
 // 18): where the b x b diagonal blocks come from and what is refused (rails_bj_plan), their extraction from block-CSR and CSR arrays, and
 // their inverses in long double.  No HIP in here: tests/cpp/block_jacobi_host.cpp stands alone on it.
 #ifndef RAILS_BLOCK_JACOBI_HOST_H

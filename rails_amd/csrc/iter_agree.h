@@ -1,4 +1,4 @@
-// iter_agree.h -- what the ranks of a row partition must agree on before an iterative A^-1 object (itsolve.hip) may run: whether the
+// iter_agree.h -- what the ranks of a row partition must agree on before an iterative A^-1 object (iter_setup.hip: rails_iter_create) may run: whether the
 // Jacobi diagonal exists, the sign of the operator's diagonal, and the two Gershgorin bounds of the polynomial preconditioner.  Ranks
 // that disagree run different recurrences, and the all-reduced inner products mean nothing.  The library's only collective is a sum, so
 // the values are gathered through it: every rank writes RAILS_AGREE_SLOT doubles into its own slot of a zeroed vector of nranks slots,

@@ -184,7 +184,7 @@ extern "C" int rails_csr_bsr_stats(const rails_csr *A, int64_t *info, int cap)
 }
 
 // the block matrix of a BSR handle goes with the handle (rails_csr_destroy)
-// the host copy a block-CSR handle keeps (block Jacobi of the iterative A^-1 takes its diagonal blocks from it, itsolve.hip)
+// the host copy a block-CSR handle keeps (block Jacobi of the iterative A^-1 takes its diagonal blocks from it, iter_hierarchy.hip)
 bool rails_bsr_host_arrays(const rails_csr *A, int *b, int64_t *mb, const int64_t **browptr, const int32_t **bcol, const double **bval)
 {
     const rails_bsr *M = A->bsr();

@@ -1,4 +1,5 @@
-"""Iterative solves on the device as a library object (include/rails_hip.h: rails_iter_*, rails_amd/csrc/itsolve.hip): the approximate A^-1
+"""Iterative solves on the device as a library object (include/rails_hip.h: rails_iter_*, rails_amd/csrc/itsolve.hip with iter_setup.hip and
+iter_hierarchy.hip): the approximate A^-1
 the reference allows for its inverse and extended Krylov projections (opts.Ainv of matlab/RAILSsolver.m:19-23, "This can be approximate")
 where a sparse LU is latency-bound or cannot be formed.  Conjugate gradients for a definite matrix, BiCGStab for a general one, Jacobi
 preconditioning, for conjugate gradients also a Chebyshev polynomial in the Jacobi-scaled matrix; every column is a system of its own and

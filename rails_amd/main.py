@@ -195,6 +195,8 @@ def main(argv=None):
         raise SystemExit("--block-size %d: blocks of 2 .. 8" % args.block_size)
     if args.block_size and int(os.environ.get("WORLD_SIZE", "1")) > 1:  # refused before the ranks meet
         raise SystemExit("--block-size on %s ranks: a block-CSR operator is single GPU" % os.environ["WORLD_SIZE"])
+    # The early refusals of the preconditioner flags below (and of --inverse-amg further down) restate, for the command line and in its
+    # words, what the library's one rule decides for an object: rails_amd/csrc/iter_precond.h (one preconditioner at a time, single GPU).
     if args.inverse_block_jacobi:  # what the arguments alone decide, before anything is read or built
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             raise SystemExit("--inverse-block-jacobi on %s ranks: the block-Jacobi preconditioner is single GPU" % os.environ["WORLD_SIZE"])
@@ -376,7 +378,7 @@ def main(argv=None):
     # "Projection method" above 1 (opts.projection_method, matlab/RAILSsolver.m:7-24): the driver builds the inverse it needs
     method = next((float(v) for k, v in params.items() if k.lower() == "projection method"), 1.0)
     inverse = None
-    if method > 1 and args.inverse_amg:  # refused before anything is built
+    if method > 1 and args.inverse_amg:  # refused before anything is built (the rule itself: rails_amd/csrc/iter_precond.h)
         if args.inverse_poly:
             raise SystemExit("--inverse-amg together with --inverse-poly %d: one preconditioner at a time" % args.inverse_poly)
         if world > 1:

@@ -1,15 +1,17 @@
-"""Bits and counters of the iterative A^-1 operator (rails_amd/csrc/itsolve.hip) over a fixed list of cases, to compare two builds of the
+"""Bits and counters of the iterative A^-1 operator (rails_amd/csrc/itsolve.hip, iter_setup.hip, iter_hierarchy.hip) over a fixed list of cases, to compare two builds of the
 library: a refactoring of the host code must leave every result, every column's iterations, flags and residual and every counter as they
 were.
 
     python scripts/iter_identity.py --tree PATH --out ONE.json      # imports rails_amd from PATH in a fresh child process, runs the cases
     python scripts/iter_identity.py --compare PARENT.json NEW.json --out profiles/iter_refactor_identity.json
 
-The cases come from the fixtures of the tests (tests/iter_reference.py, cheb_reference.py, amg_reference.py, iter_partition_cases.py):
+The cases come from the fixtures of the tests (tests/iter_reference.py, cheb_reference.py, amg_reference.py, block_jacobi_reference.py, block_amg_reference.py,
+iter_partition_cases.py):
 solve and precondition at widths 1, 3, 16, 17, 32 and 33 (the pad column, the 8-lane against the 16-lane gather, the group loop); CG with
 and without Jacobi and on a negative definite matrix, BiCGStab with and without Jacobi and transposed; the polynomial at degrees 1, 2 and 5
-fused and unfused; the multigrid cycle on five problems at smoother degrees 0, 1 and 2 fused and unfused; check_every 8 and 1 at every
-width; the two-rank polynomial cases (the ghost-row form of the fused step) at degrees 1 and 4, ranks as threads on one device.
+fused and unfused; the multigrid cycle on five problems at smoother degrees 0, 1 and 2 fused and unfused; block Jacobi under CG and BiCGStab (plain
+and transposed) with the blocks taken from a CSR operator, from a block-CSR operator and passed in; the block multigrid cycle on six problems
+at smoother degrees 0, 1 and 2 fused and unfused; check_every 8 and 1 at every width; the two-rank polynomial cases (the ghost-row form of the fused step) at degrees 1 and 4, ranks as threads on one device.
 A case is one setting of the object and one call, solve or precondition, run at every width (two-rank cases: on both ranks), so that
 the file stays small.  Per case: the SHA-256 of the results' bytes in the order they were computed, the SHA-256 of the columns'
 iterations, flags and relative residuals after each call, and the counters launches, products, inner products, polynomial applications,
@@ -37,11 +39,11 @@ class Record:
         import numpy as np
 
         it, rel, flags = inv.columns()
-        st, amg = inv.stats(), inv.amg_info()
+        st, amg, bamg = inv.stats(), inv.amg_info(), inv.block_amg_info()  # (a hierarchy is of one kind: the other's counters read 0)
         self.result.update(np.ascontiguousarray(Y.to_host()).tobytes())
         for a in (it, flags, rel):
             self.columns.update(np.ascontiguousarray(a).tobytes())
-        self.counters = [c + v for c, v in zip(self.counters, [st[n] for n in COUNTERS] + [amg[n] for n in CYCLE_COUNTERS])]
+        self.counters = [c + v for c, v in zip(self.counters, [st[n] for n in COUNTERS] + [amg[n] + bamg[n] for n in CYCLE_COUNTERS])]
 
     def merge(self, other):
         """another rank's record, behind this one"""
@@ -97,6 +99,50 @@ def single_gpu(rails_amd, ctx, out):
                 inv.set("amg_degree", S)
                 inv.set("poly_fused", fused)
                 both_calls(rails_amd, ctx, inv, B, out, "amg %s S%d fused%d" % (tag, S, fused))
+        inv.close()
+    block_jacobi(rails_amd, ctx, out)
+    block_cycle(rails_amd, ctx, out)
+
+
+def block_jacobi(rails_amd, ctx, out):
+    """block Jacobi: CG, BiCGStab plain and transposed; the blocks of a CSR operator by block_size, a block-CSR operator's own, blocks
+    passed in (on the CSR handle)"""
+    import numpy as np
+
+    import block_jacobi_reference as BJ
+    import iter_reference as R
+
+    for variant in BJ.VARIANTS:
+        for shape in ((6, 5, 4, 2), (5, 5, 4, 6)):
+            c = BJ.Case(variant, shape + ((), (1,), ""), 1)
+            bsr, A = c.problem()
+            B = R.rhs(c.m, max(WIDTHS))
+            plain = rails_amd.HipOperatorWrapper(ctx, A.indptr.astype(np.int64), A.indices.astype(np.int32), A.data)
+            blocked = rails_amd.HipOperatorWrapper.from_bsr(ctx, *bsr)
+            for source, op, how in (("csr", plain, dict(block_jacobi=True, block_size=c.b)), ("bsr", blocked, dict(block_jacobi=True)),
+                                    ("blocks", plain, dict(block_jacobi=BJ.diagonal_blocks(A, c.b)))):
+                inv = rails_amd.IterativeInverse(ctx, op, method=c.method, tol=1e-10, maxit=2000, **how)
+                both_calls(rails_amd, ctx, inv, B, out, "block_jacobi %s %dx%dx%d b%d %s" % ((c.variant,) + shape + (source,)), trans=c.trans)
+                inv.close()
+
+
+def block_cycle(rails_amd, ctx, out):
+    """the block multigrid cycle: no level, two and three matrices, a positive definite operator, a block row longer than the LDS buffer"""
+    import numpy as np
+
+    import block_amg_reference as BA
+    import iter_reference as R
+
+    for tag in ("one4", "d4x4x3b3c24", "d6x6x6b3", "d8x8x8b4", "d4x4x3b3c24p", "long8"):
+        (ip, ix, dt), coarse = BA.problem(tag)
+        op = rails_amd.HipOperatorWrapper.from_bsr(ctx, np.asarray(ip, dtype=np.int64), np.asarray(ix, dtype=np.int32), np.ascontiguousarray(dt))
+        B = R.rhs(int(op.M()), max(WIDTHS))
+        inv = rails_amd.IterativeInverse(ctx, op, method="cg", tol=1e-10, maxit=2000, amg_coarse=coarse, block_amg=True)
+        for S in (0, 1, 2):
+            for fused in (1, 0):
+                inv.set("amg_degree", S)
+                inv.set("poly_fused", fused)
+                both_calls(rails_amd, ctx, inv, B, out, "block_amg %s S%d fused%d" % (tag, S, fused))
         inv.close()
 
 

@@ -1,4 +1,4 @@
-"""Restatement of the block-Jacobi preconditioner of the iterative A^-1 operator (rails_amd/csrc/block_jacobi_host.h, itsolve.hip,
+"""Restatement of the block-Jacobi preconditioner of the iterative A^-1 operator (rails_amd/csrc/block_jacobi_host.h, iter_hierarchy.hip, itsolve.hip,
 iter_kernels.inc: iter_pass_block).  Not a test module: tests/test_block_jacobi_host.py checks it on the CPU,
 tests/test_gpu_block_jacobi_steps.py and tests/test_gpu_block_jacobi.py compare the device against it.
 

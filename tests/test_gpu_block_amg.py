@@ -1,5 +1,5 @@
 """The block multigrid preconditioner of the iterative A^-1 operator (include/rails_hip.h: "block_amg", rails_iter_block_amg_setup,
-rails_iter_block_amg_info; rails_amd/csrc/block_amg_host.cpp for the set-up, itsolve.hip: Run::vcycle on block sweeps, iter_kernels.inc:
+rails_iter_block_amg_info; rails_amd/csrc/block_amg_host.cpp and iter_hierarchy.hip for the set-up, itsolve.hip: Run::vcycle on block sweeps, iter_kernels.inc:
 k_cheb_step_bsr, k_amg_residual_bsr, k_cheb_init_bj, k_cheb_pass_bj on bsr_row_gather.inc and iter_pass_block) on the GPU against the
 restatement of tests/block_amg_reference.py: one cycle against a longdouble evaluation on the shapes at which the kernels take their
 different paths, the fused step against the unfused one bit for bit, converged solves against the restatement's iteration counts and

@@ -1,5 +1,5 @@
 """The block-Jacobi preconditioner of the iterative A^-1 operator (include/rails_hip.h: rails_iter_block_jacobi, "block_jacobi";
-rails_amd/csrc/itsolve.hip, iter_kernels.inc) on the GPU: the preconditioner on its own against the library's own
+rails_amd/csrc/iter_hierarchy.hip for the install, itsolve.hip, iter_kernels.inc) on the GPU: the preconditioner on its own against the library's own
 inverse blocks within b eps (|Ginv| |X|), through windows bit for bit; converged solves on rails_amd.problems.block_coupled7 asked for
 four ways, against the float64 restatement's iteration counts and against point Jacobi on the same handle; the three sources of the
 blocks; the block-CSR handle against the CSR handle forced to row-gather; the toggle; every refusal that needs a device, each leaving

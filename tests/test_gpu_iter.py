@@ -1,4 +1,4 @@
-"""The iterative A^-1 operator (include/rails_hip.h: rails_iter_*, rails_amd/csrc/itsolve.hip) on the GPU against the numpy restatement of
+"""The iterative A^-1 operator (include/rails_hip.h: rails_iter_*, rails_amd/csrc/itsolve.hip, iter_setup.hip) on the GPU against the numpy restatement of
 tests/iter_reference.py: solves through the operator handle (rails_spmm) and through rails_iter_solve on full panels and on windows at odd
 columns of wide panels, the transposed solve, determinism and independence of check_every, columns of different speed in one solve, the
 iteration cap, the breakdown rule, the refusals, and the work panels.

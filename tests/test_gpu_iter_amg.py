@@ -1,5 +1,5 @@
 """The smoothed-aggregation multigrid preconditioner of the iterative A^-1 operator (include/rails_hip.h: "amg", rails_iter_amg_setup,
-rails_iter_amg_info; rails_amd/csrc/amg_host.cpp for the set-up, itsolve.hip: Run::vcycle on the sweeps plan_call made, iter_kernels.inc:
+rails_iter_amg_info; rails_amd/csrc/amg_host.cpp and iter_hierarchy.hip for the set-up, itsolve.hip: Run::vcycle on the sweeps plan_call made, iter_kernels.inc:
 k_amg_residual_csr, k_amg_prolong_add, k_amg_coarse_dense) on the GPU against the restatement of tests/amg_reference.py: one cycle against a longdouble evaluation on the shapes
 at which the kernels take their different paths, the preconditioned solves against the restatement's iteration counts, "amg" 0 bit for
 bit, determinism, the counts per cycle of DESIGN.md section 16, and the refusals."""
