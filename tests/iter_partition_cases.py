@@ -53,20 +53,25 @@ def csr_triple(A):
     return A.indptr.astype(np.int64), A.indices.astype(np.int64), A.data.astype(np.float64)
 
 
-def run_ranks(nranks, A, work, seed=3):
+def run_ranks(nranks, A, work, seed=3, starts=None, ranks=None, every_rank_has_ghosts=True):
     """work(r, ctx, op, plan, r0, r1) -> result on every rank of a row partition of the CSR triple A, one thread per rank; the contexts
-    are closed afterwards.  Returns the results in rank order."""
+    are closed afterwards.  Returns the results in rank order.  starts: the row blocks (default: balanced).  ranks: the emulation
+    (default: test_gpu_partition.Ranks; tests/partition_ranks.py's for plans in which not every rank exchanges -- those, and only those,
+    pass every_rank_has_ghosts=False)."""
     from rails_amd import partition
     from test_gpu_partition import Ranks, _rank_setup
 
     m = A[0].size - 1
-    starts = partition.row_ranges(m, nranks)
-    ranks = Ranks(nranks)
+    if starts is None:
+        starts = partition.row_ranges(m, nranks)
+    assert len(starts) == nranks + 1 and int(starts[-1]) == m
+    if ranks is None:
+        ranks = Ranks(nranks)
 
     def body(r):
         ctx, op, plan = _rank_setup(ranks, r, starts, A, seed=seed)
         try:
-            assert plan.n_ghost > 0  # rows really cross the partition, on every rank
+            assert plan.n_ghost > 0 or not every_rank_has_ghosts  # rows really cross the partition, on every rank
             return work(r, ctx, op, plan, int(starts[r]), int(starts[r + 1]))
         finally:
             ctx.close()
