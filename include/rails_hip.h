@@ -166,6 +166,13 @@ int rails_csr_sweep_stats(rails_csr *A, int nc, double *out);
  * [10] columns per chunk KC, [11] register slots per row NNZ, [12] staging slots per thread NL, [13] 16-byte vectors per lane V2,
  * [14] chunks in flight NS (zeros where a kernel has no such parameter); [15] 0. */
 int rails_csr_tile_stats(rails_csr *A, double *out);
+/* The plane-sweep kernel's plan and its most recent launch on this operator (out has room for 16):
+ * out[0] 1 once the plan has been looked at, [1] 1 if it was accepted (a complete 7- or 27-point grid stencil), [2] 1 for the 7-point form,
+ * [3..5] the grid gx, gy, gz (of a z-slab: its own planes), [6], [7] the output planes [z_lo, z_hi) the plan covers (all of them, or a
+ * z-slab's planes without ghost columns); the launch of k_spmm_planes<LPR, RW, WX, WY>: [8] lanes per row LPR (0: none yet), [9] rows per
+ * wave RW, [10], [11] waves WX x WY, [12] planes per z segment, [13] z segments, [14] column chunks, [15] 1 if Y's rows took one 16-byte
+ * store per lane (0: a window on an odd column, two 8-byte stores) + 2 if the launch was the interior planes of a row-partitioned product. */
+int rails_csr_planes_stats(rails_csr *A, double *out);
 /* A rectangular operator, n_rows x n_cols, all columns local: in rails_spmm X has n_cols rows and Y n_rows; no transposed apply, no
  * ghost rows.  Role: the off-diagonal blocks A12, A21 of the reference's Schur complement operator (src/SchurOperator.cpp:181-214). */
 int rails_csr_create_rect(rails_ctx *ctx, int64_t n_rows, int64_t n_cols, const int64_t *rowptr, const int32_t *col, const double *val,

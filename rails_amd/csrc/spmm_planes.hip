@@ -210,6 +210,10 @@ struct rails_planes_plan {
     bool last_interior = false; // the last product ran the interior planes only (row-partitioned operator, rails_spmm_planes_interior)
     int gx = 0, gy = 0, gz = 0;
     int z_lo = 0, z_hi = 0; // output planes the records are complete for: all of them, or a z-slab's planes without ghost columns
+    // the most recent launch (rails_csr_planes_stats): the instantiation, the z segments, column chunks, Y's store form; lpr 0 = none yet
+    struct {
+        int lpr, rw, wx, wy, seglen, nseg, nchunks, y_vec;
+    } last = {0, 0, 0, 0, 0, 0, 0, 0};
     double *cf = nullptr;
     double *zero = nullptr;
 };
@@ -314,7 +318,7 @@ static int planes_env(const char *name, int def)
 }
 
 template <int LPR, int RW, int WX, int WY>
-static int planes_launch(rails_ctx *c, const rails_planes_plan *P, const double *X, int ldx, double *Y, int ldy, int nc, hipStream_t st)
+static int planes_launch(rails_ctx *c, rails_planes_plan *P, const double *X, int ldx, double *Y, int ldy, int nc, hipStream_t st)
 {
     const int y_vec = ((((uintptr_t)Y) & 15) == 0 && ldy % 2 == 0) ? 1 : 0;
     constexpr int G = 64 / LPR, NW = WX * WY, PX = RW * WX, PY = WY * G, HXP = (PX + 2 + G - 1) / G * G, NXS = (PY + 2) * (HXP / G);
@@ -355,6 +359,7 @@ static int planes_launch(rails_ctx *c, const rails_planes_plan *P, const double 
     a.wg_per_xcd = a.nwg >= 64 ? (a.nwg + 7) / 8 : 0;
     const unsigned grid = a.wg_per_xcd ? (unsigned)a.wg_per_xcd * 8u : (unsigned)a.nwg;
     const size_t lds = (size_t)(2 * NXS + 3 * NCF) * 1024;
+    P->last = {LPR, RW, WX, WY, a.seglen, a.nseg, nchunks, y_vec};
     if (P->cross) {
         RAILS_HIP_CHECK(hipFuncSetAttribute((const void *)k_spmm_planes<LPR, RW, WX, WY, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         if (st == c->stream)
@@ -371,7 +376,7 @@ static int planes_launch(rails_ctx *c, const rails_planes_plan *P, const double 
     return RAILS_OK;
 }
 
-static int planes_dispatch(rails_ctx *c, const rails_planes_plan *P, const double *X, int ldx, double *Y, int ldy, int nc, hipStream_t st)
+static int planes_dispatch(rails_ctx *c, rails_planes_plan *P, const double *X, int ldx, double *Y, int ldy, int nc, hipStream_t st)
 {
     // lanes per row by the panel's width; patch shapes by what the LDS holds (two X planes + three planes of records)
     static const int shape = planes_env("RAILS_PLANES_SHAPE", 0);
@@ -435,3 +440,22 @@ int rails_spmm_planes_interior(rails_ctx *c, rails_csr *A, const double *X, int 
 }
 
 bool planes_last_interior(const rails_csr *A) { return A->planes && A->planes->last_interior; }
+
+extern "C" int rails_csr_planes_stats(rails_csr *A, double *out)
+{
+    RAILS_REQUIRE(A && out, "rails_csr_planes_stats: null argument");
+    for (int i = 0; i < 16; ++i) out[i] = 0.0;
+    const rails_planes_plan *P = A->planes;
+    if (!P) return RAILS_OK;
+    out[0] = 1.0;
+    if (P->ok) {
+        out[1] = 1.0;
+        out[2] = P->cross ? 1.0 : 0.0;
+        const int plan[5] = {P->gx, P->gy, P->gz, P->z_lo, P->z_hi};
+        for (int i = 0; i < 5; ++i) out[3 + i] = (double)plan[i];
+    }
+    const int last[7] = {P->last.lpr, P->last.rw, P->last.wx, P->last.wy, P->last.seglen, P->last.nseg, P->last.nchunks};
+    for (int i = 0; i < 7; ++i) out[8 + i] = (double)last[i];
+    out[15] = (double)((P->last.y_vec ? 1 : 0) + (P->last_interior ? 2 : 0));
+    return RAILS_OK;
+}

@@ -574,6 +574,16 @@ class HipOperatorWrapper:
                 "max_fp": int(out[5]), "max_pos": int(out[6]), "max_row_nnz": int(out[7]), "reuse": out[8], "kernel": kernels[int(out[9])],
                 "KC": int(out[10]), "NNZ": int(out[11]), "NL": int(out[12]), "V2": int(out[13]), "NS": int(out[14])}
 
+    def planes_stats(self):
+        """The plane-sweep kernel's plan and its most recent launch on this operator (rails_csr_planes_stats): the instantiation
+        k_spmm_planes<LPR, RW, WX, WY>, the z segments and column chunks it ran with; LPR 0 until the kernel has run."""
+        out = (C.c_double * 16)()
+        check(self.ctx.lib.rails_csr_planes_stats(self.h.h, out), "rails_csr_planes_stats")
+        flags = int(out[15])
+        return {"built": bool(out[0]), "accepted": bool(out[1]), "cross": bool(out[2]), "grid": (int(out[3]), int(out[4]), int(out[5])),
+                "z_lo": int(out[6]), "z_hi": int(out[7]), "LPR": int(out[8]), "RW": int(out[9]), "WX": int(out[10]), "WY": int(out[11]),
+                "seglen": int(out[12]), "nseg": int(out[13]), "chunks": int(out[14]), "y_vec": flags & 1, "interior": bool(flags & 2)}
+
     def set_halo(self, plan, pyfunc):
         """Install the ghost-row plan (rails_amd.partition.HaloPlan) and hook pyfunc(send_ptr, recv_ptr, ncols, stream)."""
         def tramp(user, send, recv, nc, stream):
